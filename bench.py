@@ -10,9 +10,9 @@ With --gpus N under torchrun (one process per GPU, the driver's launch) the
 sources are split over the N ranks (sharding.AllSourcesLayout: the locality
 partition on fabrics, contiguous id blocks on grids; the rule of the engine's
 spf_partition_sources), every rank's distance rows and next-hop bitmaps stay
-RESIDENT in its own HBM (no collective inside the step), and after the timed
-steps rank 0 gathers per-source digests (RCCL) and checks every source
-against the oracle (strong scaling: the work per step is fixed).
+RESIDENT in its own HBM (no collective inside the step), and with --full
+rank 0 gathers per-source digests (RCCL) after the timed steps and checks
+every source against the oracle (strong scaling: the work per step is fixed).
 --results gather (labelled extra) gathers the rows and bitmaps to rank 0
 inside the step instead; --scaling weak gives rank r its own LSDB snapshot
 (rack switch r drained, BM_DecisionFabric's per-iteration perturbation,
@@ -35,6 +35,15 @@ Other BASELINE configs (--workload):
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload fabric_full]
     python bench.py --devices 0,0,0,0 [--graphs]      (one process, 4 members)
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(metric, value, unit, ms_per_step, ...).  --full adds what takes work of its
+own: the check of the last step's output against the oracle's committed
+digests (`parity`; a mismatch exits 3), the per-kernel HIP-event times and the
+roofline block, the measured copy bandwidth, the CPU baseline (--cpu-budget)
+and, on multi-member runs, the host-enqueue figures.  --dump-outputs DIR (the
+all-sources workloads, one process) writes what the last timed step computed
+as DIR/<name>.npy (dump_outputs below).
 """
 
 from __future__ import annotations
@@ -308,6 +317,24 @@ class AllSources:
             out = list(self.recv[b].unbind(0)) if self.rank == 0 else None
             self.works[b] = dist.gather(buf.t, out, dst=0, async_op=True)
 
+    def reader(self):
+        """read(s) -> (u32 distances [n], next-hop matrix bool [k, n]) of
+        source s as the last step left them (one process: every source is
+        this rank's, u32 rows); the buffer is copied to the host once."""
+        from openr_amd.engine import nh_matrix
+
+        assert self.world == 1 and self.dist_bytes == 4
+        host = self.send[(self.i - 1) % self.nbuf].numpy().view(np.uint32)
+        row = {int(s): j for j, s in enumerate(self.srcs)}
+        pitch, n = self.eng.pitch, self.n
+        nh = host[self.dist_words:]
+
+        def read(s: int):
+            j = row[s]
+            return (host[j * pitch: j * pitch + n],
+                    nh_matrix(nh, int(self.plan.nh_off[j]), int(self.plan.words[j]), pitch, n))
+        return read
+
     def verify(self):
         """Untimed, after the timed steps: every rank digests the rows and
         bitmaps its last execute left in its HBM (spf_plan_digest, on the
@@ -499,6 +526,9 @@ class AllSourcesMulti(AllSources):
     def finish(self) -> None:
         self.plan.synchronize()
 
+    def reader(self):
+        return self.plan.read  # request index = source id (the plan holds every node)
+
     def verify(self):
         digest = self.plan.digest()
         gold = ROOT / "tests" / "golden" / f"fullsize_{self.name}.npz"
@@ -668,11 +698,15 @@ class Ksp2AllPairs:
                 "against": f"tests/golden/{gold.name} (oracle getKthPaths k=1,2 of every pair), "
                            "engine digests from spf_ksp2_digest on each rank's last execute"}
 
-    def kernel_ms(self):
-        a, b, cnt = self.plan.timing()
+    def check_pool(self):
         cnt_h = self.d_cnt.numpy()
         if cnt_h[2] & 1:
             raise SystemExit("KSP2 path pool overflowed: raise pool_words")
+        return cnt_h
+
+    def kernel_ms(self):
+        a, b, cnt = self.plan.timing()
+        cnt_h = self.check_pool()
         # path pool words = records [len, next, links]; output links ~ words
         self.survey_bytes = int(self.units * self.b_solve + len(self.srcs) * self.b_solve
                                 + 4 * int(cnt_h[0]))
@@ -1455,6 +1489,48 @@ def _dump_maps_at_exit(path: str) -> None:
     atexit.register(lambda: shutil.copy("/proc/self/maps", path))
 
 
+DUMP_SOURCES = 256  # sources sampled by --dump-outputs, fewer if they pass the budget
+DUMP_BUDGET = 48 << 20  # bytes of .npy data
+
+
+def dump_outputs(wl, out_dir: str) -> dict:
+    """--dump-outputs: what the last timed step left for a caller, for a fixed
+    sample of sources (the first DUMP_SOURCES of a seeded permutation of the
+    nodes, cut where the arrays would pass DUMP_BUDGET; the whole all-sources
+    result is ~0.5 GB), read back from the step's own output buffers:
+
+      sources.npy        [S]       f64  the sampled source node ids
+      dist.npy           [S, n]    f64  distances (4294967295 = unreachable)
+      next_hops.npy      [R, n/8]  f32  next-hop bitmaps, one row per (source,
+                                        neighbour in ascending id), destinations
+                                        packed 8 per value (bit d%8 of column d/8)
+      next_hop_rows.npy  [S + 1]   f64  source i's rows are [rows[i], rows[i+1])
+
+    The topologies and the sample are seeded, so two runs with the same
+    arguments write the same inputs' results."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    read = wl.reader()
+    order = np.random.default_rng(0).permutation(wl.n)[:DUMP_SOURCES]
+    srcs, dist, nh, rows, total = [], [], [], [0], 8
+    for s in order:
+        d, m = read(int(s))
+        bits = np.packbits(m, axis=1, bitorder="little").astype(np.float32)
+        total += 8 * d.size + bits.nbytes + 16
+        if total > DUMP_BUDGET:
+            break
+        srcs.append(int(s))
+        dist.append(d.astype(np.float64))
+        nh.append(bits)
+        rows.append(rows[-1] + len(bits))
+    arrays = {"sources": np.array(srcs, np.float64), "dist": np.array(dist),
+              "next_hops": np.concatenate(nh), "next_hop_rows": np.array(rows, np.float64)}
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
+    return {"dir": str(out), "sources": len(srcs),
+            "bytes": int(sum(a.nbytes for a in arrays.values()))}
+
+
 def main() -> None:
     if os.environ.get("BENCH_DUMP_MAPS"):
         _dump_maps_at_exit(os.environ["BENCH_DUMP_MAPS"])
@@ -1463,8 +1539,14 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="fabric_full", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="also check the output against the oracle's digests, time the kernels "
+                         "(roofline), measure the copy bandwidth and run the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="all-sources workloads, one process: write the last timed step's "
+                         "results for a seeded sample of sources as DIR/<name>.npy")
     ap.add_argument("--cpu-budget", type=float, default=12.0,
-                    help="seconds of CPU-baseline sampling (0 disables)")
+                    help="with --full: seconds of CPU-baseline sampling (0 disables)")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="all-sources workloads: split one LSDB's sources over ranks "
                          "(strong), or one LSDB snapshot per rank (weak)")
@@ -1479,8 +1561,12 @@ def main() -> None:
     ap.add_argument("--graphs", action="store_true",
                     help="multi-device run: replay each member's execute as a hipGraph")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps needs at least 1 timed step, --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.dump_outputs and (world > 1 or WORKLOADS[args.workload] is not AllSources):
+        ap.error("--dump-outputs covers the all-sources workloads run from one process")
     if world == 1 and (args.devices or args.gpus > 1):
         return main_multi(args)
     rank = int(os.environ.get("RANK", "0"))
@@ -1514,8 +1600,9 @@ def main() -> None:
     # (the roofline's per-kernel times).  A multi-GPU all-sources rank takes
     # ~0.07 ms per step, where 4 events per execute would add ~10 us: there
     # the events time separate executes after the timed region instead.
+    # A plain run records no events: its steps are production executes.
     events_in_timed = world == 1 or cls is not AllSources
-    if events_in_timed:
+    if args.full and events_in_timed:
         wl.enable_timing(max(1, args.steps))
 
     if world > 1:
@@ -1533,16 +1620,21 @@ def main() -> None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev.device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    if not events_in_timed:
-        k = max(1, min(args.steps, 10))
-        wl.enable_timing(k)
-        for _ in range(k):
-            wl.step()
-        getattr(wl, "finish", lambda: None)()
-        dev.sync()
-    kms = wl.kernel_ms()
-    launch_ms = sum(kms.values())
-    parity = wl.verify() if hasattr(wl, "verify") else None
+    dumped = dump_outputs(wl, args.dump_outputs) if args.dump_outputs else None
+    kms = parity = None
+    if args.full:
+        if not events_in_timed:
+            k = max(1, min(args.steps, 10))
+            wl.enable_timing(k)
+            for _ in range(k):
+                wl.step()
+            getattr(wl, "finish", lambda: None)()
+            dev.sync()
+        kms = wl.kernel_ms()
+        launch_ms = sum(kms.values())
+        parity = wl.verify() if hasattr(wl, "verify") else None
+    elif hasattr(wl, "check_pool"):
+        wl.check_pool()
     if hasattr(wl, "eng"):
         wl.eng.check()  # a grid-resident kernel's barrier gave up: the run is invalid
 
@@ -1555,7 +1647,7 @@ def main() -> None:
     value = units * args.steps / elapsed
     gteps = units * wl.edges_per_unit() * args.steps / elapsed / 1e9
 
-    roofline = roofline_block(wl, kms, launch_ms, args.workload, rank)
+    roofline = roofline_block(wl, kms, launch_ms, args.workload, rank) if args.full else None
     if parity and parity.get("mismatches"):
         print(f"bench: PARITY FAILURE: {parity['mismatches']} checked results differ from "
               f"the oracle ({parity})", file=sys.stderr)
@@ -1605,17 +1697,20 @@ def main() -> None:
         out["config"]["results"] = wl.results
     if isinstance(wl, AllSources):
         out["config"]["next_hop_rows"] = wl.narrow  # u32 | u8 | sliced (bit planes)
-    if isinstance(wl, (RoutesAllNodes, FacadeRouteBuild)):
+    if args.full and isinstance(wl, (RoutesAllNodes, FacadeRouteBuild)):
         out["config"]["phase_ms_per_step"] = wl.phase_ms
     if getattr(wl, "verify_ms", None):
         out["config"]["verify_ms"] = wl.verify_ms
     if isinstance(wl, FacadeLfa):
-        out["config"]["phase_ms_per_step"] = wl.phase_ms
+        if args.full:
+            out["config"]["phase_ms_per_step"] = wl.phase_ms
         out["config"]["batched_prefetch"] = wl.prefetch
-    if isinstance(wl, WhatIfAllLinks):
+    if args.full and isinstance(wl, WhatIfAllLinks):
         out["config"]["hot_failures_per_rank"] = wl.n_hot
         out["config"]["workgroup_team_failures_per_rank"] = wl.n_big
-    if rank == 0 and world == 1 and args.cpu_budget > 0:
+    if dumped:
+        out["dumped_outputs"] = dumped
+    if args.full and rank == 0 and world == 1 and args.cpu_budget > 0:
         out["cpu_baseline"] = wl.cpu_baseline(args.cpu_budget)
     if rank == 0:
         print(json.dumps(out), flush=True)
@@ -1653,9 +1748,10 @@ def main_multi(args) -> None:
         wl.step()
     wl.finish()
     elapsed = time.perf_counter() - t0
-    kms = wl.kernel_ms()
-    enq = enqueue_stagger(wl, max(5, args.steps))
-    parity = wl.verify()
+    dumped = dump_outputs(wl, args.dump_outputs) if args.dump_outputs else None
+    kms = wl.kernel_ms()  # per-member times of the timed steps' own events
+    enq = enqueue_stagger(wl, max(5, args.steps)) if args.full else None
+    parity = wl.verify() if args.full else None
     distinct = sorted(set(devices))
     value = wl.units * args.steps / elapsed
     slow = max(wl.member_ms)
@@ -1684,10 +1780,14 @@ def main_multi(args) -> None:
             "hip_graphs": wl.graphs,
             "host_enqueue": enq,
         },
-        "roofline": roofline_block(wl, kms, sum(kms.values()), args.workload, 0),
+        "roofline": (roofline_block(wl, kms, sum(kms.values()), args.workload, 0)
+                     if args.full else None),
         "cpu_baseline": None,
-        "parity": parity,
     }
+    if args.full:
+        out["parity"] = parity
+    if dumped:
+        out["dumped_outputs"] = dumped
     print(json.dumps(out), flush=True)
     from openr_amd.engine import close_all
 

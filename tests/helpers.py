@@ -10,6 +10,19 @@ from openr_amd.lsdb import AdjacencyDatabase, create_adj_db, create_adjacency
 _FAST_BKT = [2, 2, 2, 3, 5, 5, 7, 7, 11, 11, 11, 11, 13, 13]
 
 
+def gpu_visible() -> bool:
+    """Whether the HIP runtime the engine links sees a device, asked of that
+    runtime itself.  (torch ships its own copy of the runtime; a test that
+    asked torch.cuda.is_available() after the engine's library was loaded left
+    every later engine in the process with 'no HIP device visible'.)"""
+    import ctypes
+
+    from openr_amd import hiprt
+
+    n = ctypes.c_int(0)
+    return hiprt._lib.hipGetDeviceCount(ctypes.byref(n)) == 0 and n.value > 0
+
+
 def libstdcxx_int_map_order(keys: Sequence[int]) -> List[int]:
     """Iteration order of ``std::unordered_map<int, T>`` built from an
     initializer list holding ``keys`` in this order (libstdc++, identity

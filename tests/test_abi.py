@@ -41,9 +41,9 @@ def test_library_exports_every_declared_symbol():
 
 def test_no_device_is_reported_not_faked():
     """Without a GPU the engine refuses loudly instead of falling back."""
-    import torch
+    from helpers import gpu_visible
 
-    if torch.cuda.is_available():
+    if gpu_visible():
         return
     from openr_amd import _native as N
 

@@ -24,7 +24,7 @@ for s in ${STEPS:-tests}; do
     ptests) run pytest_sel 900 python -u -m pytest ${PYTEST_FILES} -m gpu --maxfail=15 -v --timeout 300 --timeout-method thread ${PYTEST_ARGS:-} ;;
     smoke) run smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
     bench) for w in ${WORKLOADS:-fabric_full}; do
-             run bench_$w 400 python -u bench.py --workload $w ${BENCH_ARGS:-}
+             run bench_$w 400 python -u bench.py --full --workload $w ${BENCH_ARGS:-}
              grep '^{' "$OUT/bench_$w.log" | tail -1 > "$OUT/bench_$w.json"
            done ;;
     wprof) SPF_WHATIF_PROF=1 SPF_WHATIF_DEBUG=1 run bench_ba_whatif_prof 400 python -u bench.py --workload ba_whatif --steps 2 --warmup 1 --cpu-budget 0 ;;
@@ -32,7 +32,7 @@ for s in ${STEPS:-tests}; do
     gwtests) SPF_WHATIF_PROF=global run pytest_whatif_gprof 900 python -u -m pytest tests/test_gpu_whatif.py "tests/test_gpu_fullsize.py::test_whatif_ba250k_16k_failures_match_oracle" "tests/test_gpu_fullsize.py::test_whatif_ba20k_every_failure_matches_oracle" -m gpu -x -v --timeout 300 --timeout-method thread ;;
     multi) for n in ${MULTI_WORLDS:-2 8}; do
              ids=$(python3 -c "print(','.join(['0']*$n))")
-             run multi_x$n 400 python -u bench.py --workload ${MW:-fabric_full} --devices $ids --steps 20 --cpu-budget 0
+             run multi_x$n 400 python -u bench.py --full --workload ${MW:-fabric_full} --devices $ids --steps 20 --cpu-budget 0
              grep '^{' "$OUT/multi_x$n.log" | tail -1 > "$OUT/multi_x$n.json"
            done ;;
     prof) for w in ${PROF_WORKLOADS:-fabric_full}; do
