@@ -564,6 +564,57 @@ spf_status spf_mplan_route_records(spf_mplan* mp, const uint32_t* me_req, uint32
  * count.  Waits. */
 spf_status spf_mplan_route_db(spf_mplan* mp, uint32_t t, uint64_t* hdr, uint64_t* rec, uint64_t cap,
                               uint64_t* n);
+/* Node-label MPLS routes (Decision.cpp:586-674) of every me from the resident
+ * pass.  node_label[v] = node v's segment label; 0 or a label outside the
+ * 20-bit space (isMplsLabelValid) = v advertises none (:592-603).
+ * spf_label_groups (host only): the distinct advertised labels in ascending
+ * order, labels[g], each with the nodes that advertise it in ascending id
+ * (= name): grp_nodes[grp_ptr[g] .. grp_ptr[g+1]).  This order is the public
+ * group index g of the calls below.  labels / grp_nodes = [n_nodes], grp_ptr =
+ * [n_nodes + 1] (any may be NULL); *n_groups = G. */
+spf_status spf_label_groups(const int32_t* node_label, uint32_t n_nodes, int32_t* labels,
+                            uint32_t* grp_ptr, uint32_t* grp_nodes, uint32_t* n_groups);
+/* Per me = srcs[me_req[t]] and label group g, on me's owning device:
+ *   owner  the candidate with the smallest name that is me itself or has a
+ *          finite distance in me's row; SPF_UNREACHABLE: none, no route.  (The
+ *          reference's collision loop, :605-618 with the no-route skip at
+ *          :641-647, gives this whatever order it visits the nodes in: a
+ *          smaller name replaces the holder only when it has a route.)
+ *   owner == me: POP_AND_LOOKUP (:620-633), no records.
+ *   otherwise the next hops of getNextHopsWithMetric(me, {owner}) +
+ *          getNextHopsThrift (:635-668; the selection of spf_mplan_route_records
+ *          for the set {owner}, SPF_ROUTE_LFA included), one u64 record each =
+ *          CSR edge | metric << 32 in me's link order.  The action is not
+ *          stored: PHP when the edge ends at the owner, SWAP to the label
+ *          otherwise (:1247-1257).
+ * Layout per member (CSR, no packed count): owner[n * G] u32, ptr[n * G + 1]
+ * u64, rec[ptr[n * G]] u64, n = the member's me slots; route (slot k, g) holds
+ * rec[ptr[k * G + g] .. ptr[k * G + g + 1]).  Built by three passes -- count,
+ * an exclusive scan, fill -- so the pool is sized exactly: *pool_bytes
+ * (optional) = over the members with a me, 8 records + 8 (n G + 1) + 4 n G.
+ * *n_labels = G, *n_records = records over every me, *kernel_ms = the slowest
+ * member's kernels (all optional).  SPF_E_UNSUPPORTED for SPF_FLAG_HOP_COUNT /
+ * SPF_FLAG_DIST64 plans and when a metric exceeds 2^32 - 1.  The databases
+ * stay resident until the next call.  Adjacency-label routes (:676-698: every
+ * link of me, no SPF) and static routes are the host's. */
+spf_status spf_mplan_label_routes(spf_mplan* mp, const uint32_t* me_req, uint32_t n_me,
+                                  const int32_t* node_label /* [n_nodes] */, uint32_t flags,
+                                  uint32_t* n_labels, uint64_t* n_records, uint64_t* pool_bytes,
+                                  double* kernel_ms);
+/* me t's label routes from the last spf_mplan_label_routes: owner = [G], ptr =
+ * [G + 1] rebased to 0, rec = its records (cap entries; SPF_E_NOMEM when fewer
+ * than *n); any may be NULL; *n = its record count.  Waits. */
+spf_status spf_mplan_label_route_db(spf_mplan* mp, uint32_t t, uint32_t* owner, uint64_t* ptr,
+                                    uint64_t* rec, uint64_t cap, uint64_t* n);
+/* A member's share of the last spf_mplan_label_routes, for device-side
+ * consumers: its owner / ptr / rec device arrays (NULL when it holds no me),
+ * its record count, and slots[k] = the index t (into that call's me_req) of
+ * its k-th me slot (cap entries; SPF_E_NOMEM when fewer than *n_slots).  Every
+ * output may be NULL. */
+spf_status spf_mplan_label_route_buffers(spf_mplan* mp, uint32_t member, const uint32_t** d_owner,
+                                         const uint64_t** d_ptr, const uint64_t** d_rec,
+                                         uint64_t* n_records, uint32_t* slots, uint32_t cap,
+                                         uint32_t* n_slots);
 /* HIP-event time of each member's executes: ms[member] summed over the last
  * executes since enable / the last call, *n = executes. */
 spf_status spf_mplan_enable_timing(spf_mplan* mp, uint32_t max_executes);

@@ -264,6 +264,15 @@ PROTOTYPES = {
                                           C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "spf_mplan_route_db": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                      C.c_uint64, C.POINTER(C.c_uint64)]),
+    "spf_label_groups": (C.c_int, [_i32p, C.c_uint32, _i32p, _u32p, _u32p, _u32p]),
+    "spf_mplan_label_routes": (C.c_int, [_vp, _u32p, C.c_uint32, _i32p, C.c_uint32, _u32p,
+                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_double)]),
+    "spf_mplan_label_route_db": (C.c_int, [_vp, C.c_uint32, _u32p, C.POINTER(C.c_uint64),
+                                           C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64)]),
+    "spf_mplan_label_route_buffers": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp), C.POINTER(_vp),
+                                                C.POINTER(_vp), C.POINTER(C.c_uint64), _u32p,
+                                                C.c_uint32, _u32p]),
     "spf_mplan_enqueue_ns": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_int)]),
     "spf_mplan_execute": (C.c_int, [_vp]),
     "spf_mplan_synchronize": (C.c_int, [_vp]),

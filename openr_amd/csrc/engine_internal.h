@@ -431,6 +431,20 @@ spf_status launch_route_sets(spf_ctx* c, const unsigned long long* d_rowp,
                              uint32_t* d_edge, uint64_t* d_metric, hipStream_t s,
                              const RouteDbOut* db = nullptr,
                              const unsigned long long* d_nrowp = nullptr);
+// Node-label MPLS routes of many `me` over resident rows (label_routes.hip):
+// the count pass (fill = false: d_owner[n_me * G], the counts into d_ptr) or
+// the fill pass (d_rec at the scanned d_ptr; d_flags bit 1: a metric past
+// 2^32 - 1).  Label group g = d_grp_nodes[d_grp_ptr[g] .. d_grp_ptr[g + 1]).
+spf_status launch_label_routes(spf_ctx* c, bool fill, const unsigned long long* d_rowp,
+                               const unsigned long long* d_nhp, const uint32_t* d_me, uint32_t n_me,
+                               const uint32_t* d_grp_ptr, const uint32_t* d_grp_nodes, uint32_t G,
+                               bool lfa, uint32_t* d_owner, unsigned long long* d_ptr,
+                               unsigned long long* d_rec, uint32_t* d_flags, hipStream_t s);
+// d_ptr[0 .. n) -> its exclusive scan in place, d_ptr[n] = the total; d_sums =
+// label_scan_tiles(n) words of scratch.  Deterministic.
+uint64_t label_scan_tiles(uint64_t n);
+spf_status launch_label_scan(spf_ctx* c, unsigned long long* d_ptr, uint64_t n,
+                             unsigned long long* d_sums, hipStream_t s);
 // pathLinks of `src` from its u32 distance row on the device (spf_preds
 // without the upload; spf_mplan_preds reads a resident row).
 spf_status preds_from_row(spf_ctx* c, uint32_t src, bool hop, const uint32_t* ign,

@@ -197,7 +197,18 @@ struct spf_mplan {
     std::vector<uint32_t> db_me, h_dbcnt;
     std::vector<unsigned long long> h_dbbase;
     uint64_t db_tiles = 0;  // sets rounded up to whole 256-set tiles
+    // node-label MPLS routes (spf_mplan_label_routes): per (me slot, label
+    // group) the owner and the u64 offset of its records (CSR form), the
+    // exactly sized record pool, the scan's tile sums
+    DevBuf<uint32_t> lr_owner, lr_gptr, lr_gnodes, lr_me, lr_flags;
+    DevBuf<unsigned long long> lr_ptr, lr_rec, lr_sums;
+    std::vector<uint32_t> lr_req;  // per me slot: its index t in the call's me list
+    uint64_t lr_records = 0;
   };
+  // the last spf_mplan_label_routes: request t -> (member, slot), its groups
+  std::vector<std::pair<uint32_t, uint32_t>> lr_loc;
+  std::vector<uint32_t> lr_gptr, lr_gnodes;
+  uint32_t lr_groups = 0;
   // the last spf_mplan_route_records: request t -> (member, slot), sets
   std::vector<std::pair<uint32_t, uint32_t>> db_loc;
   uint32_t db_sets = 0;
@@ -364,6 +375,30 @@ spf_status spf_partition_sources(const uint32_t* nb_ptr, const uint32_t* nb_id, 
     if (srcs[i] >= n_nodes) return mfail(nullptr, SPF_E_INVALID, "source %u out of range", srcs[i]);
   const uint32_t used = partition(nb_ptr, nb_id, n_nodes, srcs, n_src, n_parts, mode, part_out);
   if (mode_used) *mode_used = used;
+  return SPF_OK;
+}
+
+spf_status spf_label_groups(const int32_t* node_label, uint32_t n_nodes, int32_t* labels,
+                            uint32_t* grp_ptr, uint32_t* grp_nodes, uint32_t* n_groups) {
+  if ((n_nodes && !node_label) || !n_groups)
+    return mfail(nullptr, SPF_E_INVALID, "spf_label_groups: NULL argument");
+  // buildRouteDb (Decision.cpp:592-603): label 0 = none advertised, a label
+  // outside the 20-bit space (isMplsLabelValid) is skipped
+  std::vector<std::pair<int32_t, uint32_t>> adv;
+  for (uint32_t v = 0; v < n_nodes; ++v)
+    if (node_label[v] > 0 && node_label[v] <= (1 << 20) - 1) adv.emplace_back(node_label[v], v);
+  std::sort(adv.begin(), adv.end());
+  uint32_t g = 0;
+  for (size_t i = 0; i < adv.size(); ++i) {
+    if (i == 0 || adv[i].first != adv[i - 1].first) {
+      if (labels) labels[g] = adv[i].first;
+      if (grp_ptr) grp_ptr[g] = (uint32_t)i;
+      ++g;
+    }
+    if (grp_nodes) grp_nodes[i] = adv[i].second;
+  }
+  if (grp_ptr) grp_ptr[g] = (uint32_t)adv.size();
+  *n_groups = g;
   return SPF_OK;
 }
 
@@ -724,7 +759,9 @@ spf_status route_prepare(spf_mplan* mp, const uint32_t* set_ptr, const uint32_t*
     return mfail(m, SPF_E_UNSUPPORTED, "route selection reads u32 rows (SPF_FLAG_DIST64 plan)");
   if (mp->flags & SPF_FLAG_HOP_COUNT)
     return mfail(m, SPF_E_UNSUPPORTED, "route selection needs link-metric rows (useLinkMetric)");
-  for (uint32_t i = 0; i < set_ptr[n_sets]; ++i)
+  // (set_ptr NULL: a call without destination sets -- spf_mplan_label_routes
+  // brings its label groups itself and leaves the uploaded sets alone)
+  for (uint32_t i = 0; set_ptr && i < set_ptr[n_sets]; ++i)
     if (set_nodes[i] >= N) return mfail(m, SPF_E_INVALID, "set member %u out of range", set_nodes[i]);
   if (mp->peer < 0) {
     mp->peer = 1;
@@ -828,6 +865,7 @@ spf_status route_prepare(spf_mplan* mp, const uint32_t* set_ptr, const uint32_t*
       if (!mp->h_nrowp.empty()) M_HIP(m, p.nrowp.upload(mp->h_nrowp.data(), N, s));
       p.r_epoch = mp->executes;
     }
+    if (!set_ptr) continue;
     // the sets and link hashes of a call are usually the previous call's
     // (every route build of a node list): uploaded only when they changed
     const uint32_t n_mem = std::max<uint32_t>(1, set_ptr[n_sets]);
@@ -1056,6 +1094,169 @@ spf_status spf_mplan_route_db(spf_mplan* mp, uint32_t t, uint64_t* hdr, uint64_t
       for (uint64_t j = 0; j < c; ++j) rec[at + j] = tile[off + j * stride];
     if (hdr) hdr[q] = at | (c << 32);
     at += c;
+  }
+  return SPF_OK;
+}
+
+spf_status spf_mplan_label_routes(spf_mplan* mp, const uint32_t* me_req, uint32_t n_me,
+                                  const int32_t* node_label, uint32_t flags, uint32_t* n_labels,
+                                  uint64_t* n_records, uint64_t* pool_bytes, double* kernel_ms) {
+  if (!mp || (n_me && !me_req) || !node_label)
+    return mfail(mp ? mp->m : nullptr, SPF_E_INVALID, "spf_mplan_label_routes: NULL argument");
+  spf_mctx* m = mp->m;
+  spf_ctx* c0 = m->members[0];
+  for (uint32_t t = 0; t < n_me; ++t)
+    if (me_req[t] >= mp->n_src) return mfail(m, SPF_E_INVALID, "me %u is not a request index", me_req[t]);
+  const bool lfa = (flags & SPF_ROUTE_LFA) != 0;
+  if (const spf_status st = route_prepare(mp, nullptr, nullptr, 0, lfa, nullptr, 0, me_req, n_me);
+      st != SPF_OK)
+    return st;
+  mp->lr_loc.clear();  // (the previous call's databases are overwritten from here on)
+  const uint32_t N = c0->N;
+  mp->lr_gptr.assign((size_t)N + 1, 0);
+  mp->lr_gnodes.assign(std::max<uint32_t>(N, 1), 0);
+  uint32_t G = 0;
+  if (const spf_status st = spf_label_groups(node_label, N, nullptr, mp->lr_gptr.data(),
+                                             mp->lr_gnodes.data(), &G);
+      st != SPF_OK)
+    return st;
+  std::vector<std::pair<uint32_t, uint32_t>> loc(n_me);
+  std::vector<std::vector<uint32_t>> mine(mp->n_parts);
+  for (uint32_t r = 0; r < mp->n_parts; ++r) mp->parts[r].lr_req.clear();
+  for (uint32_t t = 0; t < n_me; ++t) {
+    const uint32_t r = mp->owner[me_req[t]];
+    loc[t] = {r, (uint32_t)mine[r].size()};
+    mine[r].push_back(mp->srcs[me_req[t]]);
+    mp->parts[r].lr_req.push_back(t);
+  }
+  // per member with work: [0] before the count, [1] after the scan, [2]
+  // before the fill, [3] after it (the pool is allocated in between, on the
+  // host, from the scan's total)
+  std::vector<hipEvent_t> ev(4 * mp->n_parts, nullptr);
+  std::vector<unsigned long long> tot(mp->n_parts, 0);
+  std::vector<uint32_t> fl(mp->n_parts, 0);
+  IssuedGuard guard{m, {}, &ev};  // declared after mine / tot / fl: drains before they are freed
+  for (uint32_t r = 0; r < mp->n_parts; ++r) {
+    spf_mplan::Part& p = mp->parts[r];
+    if (mine[r].empty()) continue;
+    spf_ctx* c = m->members[r];
+    M_HIP(m, hipSetDevice(c->device));
+    guard.members.push_back(r);
+    const hipStream_t s = m->exec[r];
+    const uint32_t n = (uint32_t)mine[r].size();
+    const uint64_t cells = (uint64_t)n * G;
+    M_HIP(m, p.lr_me.upload(mine[r].data(), n, s));
+    M_HIP(m, p.lr_gptr.upload(mp->lr_gptr.data(), (size_t)G + 1, s));
+    M_HIP(m, p.lr_gnodes.upload(mp->lr_gnodes.data(), std::max<uint32_t>(1, mp->lr_gptr[G]), s));
+    M_HIP(m, p.lr_owner.alloc(std::max<uint64_t>(cells, 1)));
+    M_HIP(m, p.lr_ptr.alloc(cells + 1));
+    M_HIP(m, p.lr_sums.alloc(std::max<uint64_t>(label_scan_tiles(cells), 1)));
+    M_HIP(m, p.lr_flags.alloc(1));
+    M_HIP(m, hipMemsetAsync(p.lr_flags.p, 0, 4, s));
+    if (kernel_ms) {
+      for (uint32_t k = 0; k < 4; ++k) M_HIP(m, hipEventCreate(&ev[4 * r + k]));
+      M_HIP(m, hipEventRecord(ev[4 * r], s));
+    }
+    spf_status st = launch_label_routes(c, false, p.rowp.p, p.nhp.p, p.lr_me.p, n, p.lr_gptr.p,
+                                        p.lr_gnodes.p, G, lfa, p.lr_owner.p, p.lr_ptr.p, nullptr,
+                                        p.lr_flags.p, s);
+    if (st == SPF_OK) st = launch_label_scan(c, p.lr_ptr.p, cells, p.lr_sums.p, s);
+    if (st != SPF_OK) return member_fail(m, r, st);
+    if (kernel_ms) M_HIP(m, hipEventRecord(ev[4 * r + 1], s));
+    M_HIP(m, hipMemcpyAsync(&tot[r], p.lr_ptr.p + cells, 8, hipMemcpyDeviceToHost, s));
+  }
+  for (uint32_t r = 0; r < mp->n_parts; ++r) {
+    spf_mplan::Part& p = mp->parts[r];
+    if (mine[r].empty()) continue;
+    spf_ctx* c = m->members[r];
+    M_HIP(m, hipSetDevice(c->device));
+    const hipStream_t s = m->exec[r];
+    M_HIP(m, hipStreamSynchronize(s));  // the scan's total
+    // the record pool: exactly the total (kept when the previous one is large enough)
+    M_HIP(m, p.lr_rec.alloc(std::max<unsigned long long>(tot[r], 1)));
+    p.lr_records = tot[r];
+    if (kernel_ms) M_HIP(m, hipEventRecord(ev[4 * r + 2], s));
+    const spf_status st = launch_label_routes(c, true, p.rowp.p, p.nhp.p, p.lr_me.p, (uint32_t)mine[r].size(),
+                                              p.lr_gptr.p, p.lr_gnodes.p, G, lfa, p.lr_owner.p,
+                                              p.lr_ptr.p, p.lr_rec.p, p.lr_flags.p, s);
+    if (st != SPF_OK) return member_fail(m, r, st);
+    if (kernel_ms) M_HIP(m, hipEventRecord(ev[4 * r + 3], s));
+    M_HIP(m, hipMemcpyAsync(&fl[r], p.lr_flags.p, 4, hipMemcpyDeviceToHost, s));
+  }
+  double worst = 0;
+  uint64_t total = 0, bytes = 0;
+  for (uint32_t r = 0; r < mp->n_parts; ++r) {
+    if (mine[r].empty()) continue;
+    M_HIP(m, hipSetDevice(m->members[r]->device));
+    M_HIP(m, hipStreamSynchronize(m->exec[r]));
+    if (fl[r] & 2u) return mfail(m, SPF_E_UNSUPPORTED, "a next-hop metric exceeds 2^32 - 1");
+    const uint64_t cells = (uint64_t)mine[r].size() * G;
+    total += tot[r];
+    bytes += 8 * tot[r] + 8 * (cells + 1) + 4 * cells;
+    if (kernel_ms) {
+      float a = 0, b = 0;
+      M_HIP(m, hipEventElapsedTime(&a, ev[4 * r], ev[4 * r + 1]));
+      M_HIP(m, hipEventElapsedTime(&b, ev[4 * r + 2], ev[4 * r + 3]));
+      worst = std::max(worst, (double)a + (double)b);
+    }
+  }
+  mp->lr_loc = std::move(loc);
+  mp->lr_groups = G;
+  if (n_labels) *n_labels = G;
+  if (n_records) *n_records = total;
+  if (pool_bytes) *pool_bytes = bytes;
+  if (kernel_ms) *kernel_ms = worst;
+  return SPF_OK;
+}
+
+spf_status spf_mplan_label_route_db(spf_mplan* mp, uint32_t t, uint32_t* owner, uint64_t* ptr,
+                                    uint64_t* rec, uint64_t cap, uint64_t* n) {
+  if (!mp || t >= mp->lr_loc.size())
+    return mfail(mp ? mp->m : nullptr, SPF_E_INVALID,
+                 "spf_mplan_label_route_db: no such me (call spf_mplan_label_routes)");
+  spf_mctx* m = mp->m;
+  const auto [r, k] = mp->lr_loc[t];
+  spf_mplan::Part& p = mp->parts[r];
+  const uint32_t G = mp->lr_groups;
+  M_HIP(m, hipSetDevice(m->members[r]->device));
+  const hipStream_t s = m->exec[r];
+  // me's G + 1 offsets (the next slot's first one, or the total, ends them)
+  std::vector<uint64_t> h((size_t)G + 1);
+  M_HIP(m, hipMemcpyAsync(h.data(), p.lr_ptr.p + (size_t)k * G, 8ull * (G + 1), hipMemcpyDeviceToHost, s));
+  M_HIP(m, hipStreamSynchronize(s));
+  const uint64_t cnt = h[G] - h[0];
+  if (n) *n = cnt;
+  if (rec && cap < cnt)
+    return mfail(m, SPF_E_NOMEM, "label route db of %llu records, room for %llu", (unsigned long long)cnt,
+                 (unsigned long long)cap);
+  if (owner && G)
+    M_HIP(m, hipMemcpyAsync(owner, p.lr_owner.p + (size_t)k * G, 4ull * G, hipMemcpyDeviceToHost, s));
+  if (rec && cnt)
+    M_HIP(m, hipMemcpyAsync(rec, p.lr_rec.p + h[0], 8ull * cnt, hipMemcpyDeviceToHost, s));
+  M_HIP(m, hipStreamSynchronize(s));
+  if (ptr)
+    for (uint32_t g = 0; g <= G; ++g) ptr[g] = h[g] - h[0];
+  return SPF_OK;
+}
+
+spf_status spf_mplan_label_route_buffers(spf_mplan* mp, uint32_t member, const uint32_t** d_owner,
+                                         const uint64_t** d_ptr, const uint64_t** d_rec,
+                                         uint64_t* n_records, uint32_t* slots, uint32_t cap,
+                                         uint32_t* n_slots) {
+  if (!mp || member >= mp->n_parts)
+    return mfail(mp ? mp->m : nullptr, SPF_E_INVALID, "spf_mplan_label_route_buffers: bad argument");
+  const spf_mplan::Part& p = mp->parts[member];
+  // (a member without a me of the last call holds nothing of it)
+  const bool has = !mp->lr_loc.empty() && !p.lr_req.empty();
+  const uint32_t k = has ? (uint32_t)p.lr_req.size() : 0u;
+  if (n_slots) *n_slots = k;
+  if (d_owner) *d_owner = has ? p.lr_owner.p : nullptr;
+  if (d_ptr) *d_ptr = has ? reinterpret_cast<const uint64_t*>(p.lr_ptr.p) : nullptr;
+  if (d_rec) *d_rec = has ? reinterpret_cast<const uint64_t*>(p.lr_rec.p) : nullptr;
+  if (n_records) *n_records = has ? p.lr_records : 0;
+  if (slots) {
+    if (cap < k) return mfail(mp->m, SPF_E_NOMEM, "%u me slots, room for %u", k, cap);
+    std::copy(p.lr_req.begin(), p.lr_req.begin() + k, slots);
   }
   return SPF_OK;
 }

@@ -561,6 +561,108 @@ class LinkState(N.NativeHandle):
                                              n.value, C.byref(n)), N.global_error())
         return hdr[: self._db_sets], rec[: n.value]
 
+    def allSourcesLabelRoutes(self, lfa: bool, mes=None):
+        """Every node's (or the csr ids in `mes`) node-label MPLS routes
+        (Decision.cpp:586-674) materialised on its owning GPU from the
+        resident all-sources pass (spf_mplan_label_routes), the labels taken
+        from getAdjacencyDatabaseLabels(): returns (labels int32 [G] ascending
+        -- the group index of allSourcesLabelRouteDb --, records over every
+        node, the pools' bytes, the slowest member's kernel ms)."""
+        import numpy as np
+
+        mp = N.lib.ls_all_sources_plan(self._h)
+        if not mp:
+            raise RuntimeError("allSourcesLabelRoutes: no resident all-sources pass")
+        names = self.flatten()[0]
+        n = len(names)
+        adv = self.getAdjacencyDatabaseLabels()
+        # (a label that does not fit the C-ABI's i32 is invalid either way)
+        node_label = np.array([adv.get(s, 0) if -(1 << 31) <= adv.get(s, 0) < (1 << 31) else -1
+                               for s in names] or [0], np.int32)
+        mes = np.arange(n, dtype=np.uint32) if mes is None else np.ascontiguousarray(mes, np.uint32)
+        labels = np.zeros(max(1, n), np.int32)
+        g = C.c_uint32()
+        N.raise_for(N.lib.spf_label_groups(N.ptr(node_label, C.c_int32), n, N.ptr(labels, C.c_int32),
+                                           None, None, C.byref(g)), N.global_error())
+        ng, tot, nbytes, ms = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_double()
+        st = N.lib.spf_mplan_label_routes(C.c_void_p(mp), N.ptr(mes), len(mes),
+                                          N.ptr(node_label, C.c_int32),
+                                          N.SPF_ROUTE_LFA if lfa else 0, C.byref(ng), C.byref(tot),
+                                          C.byref(nbytes), C.byref(ms))
+        N.raise_for(st, N.global_error())
+        assert ng.value == g.value
+        self._lr = (labels[: g.value].copy(), [int(v) for v in mes], names)
+        return self._lr[0], int(tot.value), int(nbytes.value), ms.value
+
+    def allSourcesLabelRouteDb(self, t: int):
+        """Node t's (index into the last allSourcesLabelRoutes' node list)
+        label routes: (owner u32 [G] -- the csr id of label g's owner,
+        SPF_UNREACHABLE: no route --, ptr u64 [G + 1], records u64 = CSR edge |
+        metric << 32): label g's next hops are rec[ptr[g] : ptr[g + 1]], none
+        when t itself owns it (POP_AND_LOOKUP)."""
+        import numpy as np
+
+        mp = N.lib.ls_all_sources_plan(self._h)
+        if not mp or getattr(self, "_lr", None) is None:
+            raise RuntimeError("allSourcesLabelRouteDb: no resident all-sources pass")
+        g = len(self._lr[0])
+        n = C.c_uint64()
+        owner = np.zeros(max(1, g), np.uint32)
+        ptr = np.zeros(g + 1, np.uint64)
+        N.raise_for(N.lib.spf_mplan_label_route_db(C.c_void_p(mp), int(t), N.ptr(owner),
+                                                   N.ptr(ptr, C.c_uint64), None, 0, C.byref(n)),
+                    N.global_error())
+        rec = np.zeros(max(1, n.value), np.uint64)
+        N.raise_for(N.lib.spf_mplan_label_route_db(C.c_void_p(mp), int(t), None, None,
+                                                   N.ptr(rec, C.c_uint64), n.value, C.byref(n)),
+                    N.global_error())
+        return owner[:g], ptr, rec[: n.value]
+
+    def allSourcesMplsRoutes(self, t: int):
+        """Node t's (index into the last allSourcesLabelRoutes' node list)
+        MPLS routes as ``SpfSolver.buildRouteDb(node).mplsRoutes`` holds them
+        ({label: RibMplsEntry}): its node-label routes expanded from the
+        GPU's records -- POP_AND_LOOKUP for its own label, else one next hop
+        per record, PHP over a link that ends at the label's owner and SWAP
+        otherwise (Decision.cpp:586-674, 1247-1257) -- plus its adjacency-label
+        routes from linksFromNode (:676-698, on the host: they need no SPF)."""
+        from .spf_solver import (MplsAction, NextHopThrift, RibMplsEntry, createNextHop,
+                                 isMplsLabelValid)
+
+        owner, ptr, rec = self.allSourcesLabelRouteDb(t)
+        labels, mes, names = self._lr
+        me_id = mes[int(t)]
+        me = names[me_id]
+        area = self.getArea()
+        _, _, col, _, lid, _ = self.flatten()
+        out = {}
+        php = MplsAction("PHP")
+        for g, label in enumerate(labels.tolist()):
+            o = int(owner[g])
+            if o == N.SPF_UNREACHABLE:
+                continue
+            if o == me_id:
+                out[label] = RibMplsEntry(label, {NextHopThrift(
+                    bytes(16), None, 0, MplsAction("POP_AND_LOOKUP"), area, None)})
+                continue
+            swap = MplsAction("SWAP", label, None)
+            nhs = set()
+            for r in rec[int(ptr[g]): int(ptr[g + 1])].tolist():
+                e, metric = r & 0xFFFFFFFF, r >> 32
+                link = self._link(int(lid[e]))
+                nhs.add(createNextHop(link.getNhV6FromNode(me), link.getIfaceFromNode(me), metric,
+                                      php if int(col[e]) == o else swap, link.getArea(),
+                                      link.getOtherNodeName(me)))
+            out[label] = RibMplsEntry(label, nhs)
+        for link in self.linksFromNode(me):
+            top = link.getAdjLabelFromNode(me)
+            if top == 0 or not isMplsLabelValid(top):
+                continue
+            out[top] = RibMplsEntry(top, {createNextHop(
+                link.getNhV6FromNode(me), link.getIfaceFromNode(me), link.getMetricFromNode(me),
+                php, link.getArea(), link.getOtherNodeName(me))})
+        return out
+
     def debugPhaseNs(self) -> Tuple[int, int, int, int]:
         """Cumulative getSpfResult cost (ns): plan build, GPU execute + copy
         back, pathLinks, host assembly (ls_debug_phase_ns)."""
