@@ -24,8 +24,8 @@
  *     source (LinkState.cpp:831-838).
  *   - Distances are u32 unless the plan asks for SPF_FLAG_DIST64 (u64, the
  *     reference's LinkStateMetric).  Weighted solves of graphs whose longest
- *     possible path (max metric x (n_nodes-1)) does not fit 32 bits, or with
- *     a negative metric (the reference's i32 -> u64 conversion wraps), need
+ *     possible path plus one more link (max metric x n_nodes) does not fit 32
+ *     bits, or with a negative metric (the reference's i32 -> u64 conversion wraps), need
  *     SPF_FLAG_DIST64.
  *   - Zero or negative metrics, u64 distances and graphs too large for the
  *     LDS-resident kernels run the exact kernel (exact.hip): runSpf replayed
@@ -66,7 +66,8 @@ typedef enum spf_status {
 #define SPF_FLAG_HOP_COUNT 0x1u /* useLinkMetric == false: every edge costs 1 */
 /* Distance rows are u64 (LinkStateMetric, LinkState.h:22): pitch entries of
  * 8 bytes, UINT64_MAX = unreachable.  Required for weighted solves of graphs
- * with a negative metric or max metric x (n_nodes-1) >= 2^32 - 1. */
+ * with a negative metric or max metric x n_nodes >= 2^32 - 1 (the longest
+ * possible path plus one more link: the u32 kernels add before they compare). */
 #define SPF_FLAG_DIST64 0x2u
 #define SPF_UNREACHABLE64 0xFFFFFFFFFFFFFFFFull
 
@@ -551,7 +552,11 @@ spf_status spf_mplan_routes(spf_mplan* mp, uint32_t me_req, const uint32_t* set_
  * sets (stride 1024), so consecutive routes' k-th next hops are adjacent; a
  * region holds ceil(n_sets / 1024) * 1024 * deg(me) record slots (unused ones
  * are never written).  Sets without a kept next hop have count 0.
- * SPF_E_UNSUPPORTED when a metric exceeds 2^32 - 1 or a region 2^32 slots.
+ * SPF_E_UNSUPPORTED when a metric exceeds 2^32 - 1 or a region 2^32 slots,
+ * and -- before anything is uploaded or launched, the error naming the node --
+ * for a me whose CSR row has 65536 or more slots (dead ones included): the
+ * header's count has 16 bits and a route keeps up to one next hop per slot.
+ * (spf_mplan_label_routes has 64-bit offsets and no such limit.)
  * *n_records (optional) = records over every me; *kernel_ms (optional) = the
  * slowest member's kernel.  The databases stay resident until the next call. */
 spf_status spf_mplan_route_records(spf_mplan* mp, const uint32_t* me_req, uint32_t n_me,

@@ -136,7 +136,7 @@ struct spf_ctx {
   bool loaded = false;
   uint32_t N = 0, E = 0, pitch = 0;
   bool nonpos = false;
-  bool needs64 = false;  // a negative metric or max metric x (N-1) >= 2^32 - 1: u64 labels
+  bool needs64 = false;  // a negative metric or max metric x N >= 2^32 - 1: u64 labels
   uint32_t max_metric = 0;
   // live directed edges with metric <= 0, < 0, and weight == max_metric: a
   // row patch updates the metric facts from these without a graph scan

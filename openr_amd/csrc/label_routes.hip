@@ -126,6 +126,14 @@ __global__ __launch_bounds__(kLrThreads) void label_routes_kernel(
       const uint64_t over = (uint64_t)s_w[t] + via;
       if (!lfa && over != shortest) continue;
       if constexpr (FILL) {
+        // A guard no resident pass can trip (and no test tries to): a pass
+        // exists only when max metric x N < 2^32 - 1 (needs64, metric_flags;
+        // ls_prefetch_all_sources makes no plan otherwise).  via
+        // is a loop-free path x -> owner that avoids me -- the shortest one's
+        // tail, or with LFA d_x(owner) < d_me(owner) + d_x(me), which no path
+        // through me satisfies -- so it has at most N - 2 links and over =
+        // w + via <= max metric x (N - 1).  (shortest + back above is at most
+        // max metric x N for the same reason: it fits 32 bits too.)
         wide |= (over >> 32) != 0;
         const unsigned long long r = (unsigned long long)(c0 + t) | (over << 32);
         if (nt)  // (block-uniform)

@@ -970,6 +970,16 @@ spf_status spf_mplan_route_records(spf_mplan* mp, const uint32_t* me_req, uint32
   spf_ctx* c0 = m->members[0];
   for (uint32_t t = 0; t < n_me; ++t)
     if (me_req[t] >= mp->n_src) return mfail(m, SPF_E_INVALID, "me %u is not a request index", me_req[t]);
+  // a header's count field has 16 bits (offset | count << 32 | stride << 48,
+  // read back in spf_mplan_route_db) and a route keeps at most one next hop
+  // per slot of me's row: refused here, before anything is uploaded or
+  // launched (the region limit below is per member and tile size)
+  for (uint32_t t = 0; t < n_me; ++t) {
+    const uint32_t v = mp->srcs[me_req[t]], slots = c0->row_ptr[v + 1] - c0->row_ptr[v];
+    if (slots >= (1u << 16))
+      return mfail(m, SPF_E_UNSUPPORTED, "route database of node %u: %u link slots (65535 max per node)", v,
+                   slots);
+  }
   const bool lfa = (flags & SPF_ROUTE_LFA) != 0;
   if (const spf_status st = route_prepare(mp, set_ptr, set_nodes, n_sets, lfa, nullptr, 0, me_req, n_me);
       st != SPF_OK)

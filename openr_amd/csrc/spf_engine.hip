@@ -1701,8 +1701,13 @@ void spf_ctx_destroy(spf_ctx* c) {
 static void metric_flags(spf_ctx* c) {
   c->nonpos = c->n_nonpos > 0;
   // i32 -> u64 wraps (LinkState.h:22); the longest possible path beyond 32
-  // bits takes the exact kernel's u64 labels (SPF_FLAG_DIST64)
-  c->needs64 = c->n_neg > 0 || (uint64_t)c->max_metric * (uint64_t)(c->N - 1) >= (uint64_t)kInf;
+  // bits takes the exact kernel's u64 labels (SPF_FLAG_DIST64).  The bound is
+  // on max metric x N, not x (N - 1): the u32 kernels form d(u) + w(u, v) for
+  // every edge of a settled u, d(u) <= max metric x (N - 1), before they
+  // compare it, and that sum must neither wrap nor reach kInf (a 50-node
+  // chain at 87,652,393 per link has d = 2^32 - 39 at its far end, and the
+  // relaxation back from there wrapped to a "shorter" distance)
+  c->needs64 = c->n_neg > 0 || (uint64_t)c->max_metric * (uint64_t)c->N >= (uint64_t)kInf;
   c->unit = !c->nonpos && c->max_metric <= 1;
 }
 static void metric_facts(spf_ctx* c) {

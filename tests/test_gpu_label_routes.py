@@ -80,13 +80,13 @@ def graph_b(shared=True):
     return topo.lsdb, dict(zip(topo.nodes, lab.tolist())), None
 
 
-def graph_c():
-    """A hub with 300 leaves and a second, parallel link to 20 of them (10 at
-    the same metric, 10 at a larger one): 320 links at the hub (more than one
-    256-link staging chunk), 301 labels (more than one 256-thread block)."""
-    nodes = ["hub"] + [f"l{i:03d}" for i in range(300)]
+def hub_graph(leaves=300, n_me=8):
+    """A hub with `leaves` leaves and a second, parallel link to 20 of them (10
+    at the same metric, 10 at a larger one); me: the hub and n_me seeded
+    leaves."""
+    nodes = ["hub"] + [f"l{i:03d}" for i in range(leaves)]
     src, dst, met, ifs, oifs = [], [], [], [], []
-    for i in range(1, 301):
+    for i in range(1, leaves + 1):
         for k in range(2 if i <= 20 else 1):
             m = 2 if (k == 1 and i > 10) else 1
             for a, b in ((0, i), (i, 0)):
@@ -99,8 +99,15 @@ def graph_c():
     lsdb = pack_fast(nodes, np.asarray(src), np.asarray(dst), ifs, oifs, np.asarray(met, np.int32),
                      node_label=lab)
     rng = np.random.default_rng(5)
-    mes = ["hub"] + [nodes[int(i)] for i in rng.choice(np.arange(1, 301), 8, replace=False)]
+    mes = ["hub"] + [nodes[int(i)] for i in rng.choice(np.arange(1, leaves + 1), n_me, replace=False)]
     return lsdb, dict(zip(nodes, lab.tolist())), mes
+
+
+def graph_c():
+    """A hub with 300 leaves and a second, parallel link to 20 of them (10 at
+    the same metric, 10 at a larger one): 320 links at the hub (more than one
+    256-link staging chunk), 301 labels (more than one 256-thread block)."""
+    return hub_graph(300)
 
 
 def graph_d():
@@ -132,14 +139,10 @@ def label_candidates(label_of):
     return dict(sorted(out.items()))
 
 
-@functools.lru_cache(maxsize=None)
-def expected(key, lfa):
+def expected_from(orc, label_of, mes, lfa):
     """{(me, label): (owner name, {(ifName, metric, neighbour, action, swap)})}
-    for the pairs with a route, from the oracle alone; computed once per
-    (graph, lfa) and shared by the member counts."""
-    lsdb, label_of, mes = graph(key)
-    orc = OracleLinkState()
-    orc.update_packed(lsdb)
+    for the pairs with a route, from the oracle alone (mes: names; None =
+    every node)."""
     cands = label_candidates(label_of)
     mes = sorted(label_of) if mes is None else mes
     out = {}
@@ -156,6 +159,16 @@ def expected(key, lfa):
     # the inputs are chosen so that most pairs have a route
     assert 2 * len(out) >= len(mes) * len(cands), (len(out), len(mes), len(cands))
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def expected(key, lfa):
+    """expected_from for a graph of GRAPHS; computed once per (graph, lfa) and
+    shared by the member counts."""
+    lsdb, label_of, mes = graph(key)
+    orc = OracleLinkState()
+    orc.update_packed(lsdb)
+    return expected_from(orc, label_of, mes, lfa)
 
 
 def expand(ls, flat, me, labels, owner, ptr, rec):
