@@ -171,6 +171,15 @@ spf_status ls_prefetch_all_sources(ls_state* ls, int use_link_metric);
 /* The resident pass (NULL when none is valid): per-source digests
  * (spf_mplan_digest), owners, device buffers. */
 spf_mplan* ls_all_sources_plan(ls_state* ls);
+/* The resident pass's route databases kept as the old generation of a later
+ * spf_mplan_route_delta (spf_mplan_route_snapshot on ls_all_sources_plan;
+ * link_hash as there).  The LinkState drops its resident plan on every row
+ * patch and reload; the snapshot outlives that: it belongs to the ls_state
+ * and is closed by ls_route_snapshot_close or, at the latest, by ls_destroy
+ * before the engine context.  SPF_E_STATE when no resident pass is valid. */
+spf_status ls_all_sources_route_snapshot(ls_state* ls, const uint64_t* link_hash, uint32_t n_links,
+                                         spf_route_snapshot** out);
+void ls_route_snapshot_close(ls_state* ls, spf_route_snapshot* snap);
 /* Cumulative getSpfResult cost by phase in ns since creation: out[0] plan
  * build, [1] GPU execute + copy back, [2] pathLinks, [3] host result
  * assembly (diagnostics; no reference counterpart). */

@@ -620,6 +620,85 @@ spf_status spf_mplan_label_route_buffers(spf_mplan* mp, uint32_t member, const u
                                          const uint64_t** d_ptr, const uint64_t** d_rec,
                                          uint64_t* n_records, uint32_t* slots, uint32_t cap,
                                          uint32_t* n_slots);
+/* ---- route-database delta between two passes ------------------------------ */
+/* What Decision publishes after a rebuild is not the database but its
+ * difference from the previous one: DecisionRouteDb::calculateUpdate
+ * (Decision.cpp:111-146) -- routes to update (new, or the entry differs) and
+ * routes to delete.  For every me at once, on the devices that hold the
+ * databases:
+ *
+ * spf_mplan_route_snapshot: the old generation, kept.  The device pools of the
+ * last spf_mplan_route_records (headers, tiled record regions) and, when there
+ * was one, of the last spf_mplan_label_routes (owner / ptr / rec) are MOVED
+ * into the snapshot, nothing is copied: the plan holds no database afterwards
+ * (spf_mplan_route_db / _label_route_db / _label_route_buffers' pools:
+ * SPF_E_STATE / none until the next materialising call, which allocates
+ * afresh).  The snapshot also keeps, by value, what reads them later: the me
+ * list (node ids), n_nodes, n_sets, the route flags, the labels, each member's
+ * slot tables, the row starts, and on every member's device key_old[e] =
+ * link_hash[link_id[e]] for every CSR edge of the graph as it is now.
+ * link_hash[id] identifies link `id` by value (as for spf_mplan_route_digests;
+ * n_links entries covering every link id): records name CSR edges, a row patch
+ * reorders slots and a reload may re-issue link ids, so only this key compares
+ * across generations.  The snapshot belongs to the plan's spf_mctx: it
+ * outlives the plan (spf_mplan_destroy, graph patches and reloads) and is
+ * destroyed by spf_route_snapshot_destroy or, at the latest, with the mctx.
+ * SPF_E_STATE when the plan holds no route records; SPF_E_INVALID when the
+ * label routes were materialised for another me list than the records.
+ * spf_route_snapshot_bytes: the device memory it holds. */
+typedef struct spf_route_snapshot spf_route_snapshot;
+spf_status spf_mplan_route_snapshot(spf_mplan* mp, const uint64_t* link_hash, uint32_t n_links,
+                                    spf_route_snapshot** out);
+void spf_route_snapshot_destroy(spf_route_snapshot* snap);
+uint64_t spf_route_snapshot_bytes(const spf_route_snapshot* snap);
+/* spf_mplan_route_delta: the plan's current databases (new; the last
+ * spf_mplan_route_records and spf_mplan_label_routes) against the snapshot
+ * (old), per me on the device that owns it now; an old database on another
+ * member is read in place (over peer access when that is another device).
+ * A route's value is its set of next hops, each a (link identity, metric)
+ * pair -- interface, neighbour, address and area follow from the link as seen
+ * from me.
+ *   IP route (me, set p): unchanged when both have no next hop or the two
+ *     sets are equal; DELETE when only the old one has next hops; UPDATE when
+ *     the new one has and the route is new or its set differs.
+ *   Label route (me, label): the same with the owner part of the value (the
+ *     PHP / SWAP action follows from it): owner SPF_UNREACHABLE = no route, an
+ *     owner change is an UPDATE whatever the next hops, owner == me on both
+ *     sides (POP_AND_LOOKUP) is unchanged.  Labels are matched by value, not
+ *     by group index; a label of one generation only is a DELETE or an UPDATE.
+ * A me whose CSR row has the same key sequence in both generations compares
+ * records position by position; any other me by set equality on (key, metric).
+ * Output per member (CSR, exactly sized, built by count / scan / fill, no
+ * atomics per route), one pair for IP routes and one for labels: dptr[n + 1]
+ * u64 offsets over the member's n me slots and dset[] u32 entries = the set
+ * index (IP) or the label, | SPF_DELTA_DELETE on a delete, ascending within a
+ * me.  totals (optional) = [5]: IP updates, IP deletes, label updates, label
+ * deletes, me that took the set path; *kernel_ms (optional) = the slowest
+ * member's kernels.  The snapshot is only read: a second call gives the same
+ * lists.  SPF_E_INVALID when the me list, n_nodes, n_sets, the LFA flag or the
+ * presence of label routes differ from the snapshot (a changed node set shifts
+ * node ids: out of scope); SPF_E_STATE when the plan holds no databases;
+ * SPF_E_UNSUPPORTED for SPF_FLAG_HOP_COUNT / SPF_FLAG_DIST64 plans and for
+ * members on distinct devices without peer access.  The lists stay resident
+ * until the next call. */
+#define SPF_DELTA_DELETE 0x80000000u
+spf_status spf_mplan_route_delta(spf_mplan* mp, const spf_route_snapshot* snap, const uint64_t* link_hash,
+                                 uint32_t n_links, uint64_t* totals /* [5] */, double* kernel_ms);
+/* me t's lists from the last spf_mplan_route_delta: ip / label = its entries
+ * (cap entries each; SPF_E_NOMEM when fewer than *n_ip / *n_label; may be
+ * NULL).  Waits. */
+spf_status spf_mplan_route_delta_db(spf_mplan* mp, uint32_t t, uint32_t* ip, uint64_t ip_cap,
+                                    uint64_t* n_ip, uint32_t* label, uint64_t label_cap,
+                                    uint64_t* n_label);
+/* A member's share of the last spf_mplan_route_delta, for device-side
+ * consumers: its dptr / dset device arrays for IP routes and for labels (NULL
+ * when it holds no me) and slots[k] = the index t (into the records call's
+ * me_req) of its k-th me slot (cap entries; SPF_E_NOMEM when fewer than
+ * *n_slots).  Every output may be NULL. */
+spf_status spf_mplan_route_delta_buffers(spf_mplan* mp, uint32_t member, const uint64_t** d_ip_ptr,
+                                         const uint32_t** d_ip_set, const uint64_t** d_label_ptr,
+                                         const uint32_t** d_label_set, uint32_t* slots, uint32_t cap,
+                                         uint32_t* n_slots);
 /* HIP-event time of each member's executes: ms[member] summed over the last
  * executes since enable / the last call, *n = executes. */
 spf_status spf_mplan_enable_timing(spf_mplan* mp, uint32_t max_executes);

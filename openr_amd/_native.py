@@ -32,6 +32,7 @@ SPF_FLAG_DIST64 = 0x2
 SPF_UNREACHABLE64 = 0xFFFFFFFFFFFFFFFF
 SPF_KSP2_NONE = 0xFFFFFFFF
 SPF_ROUTE_LFA = 0x1
+SPF_DELTA_DELETE = 0x80000000
 SPF_PARTITION_AUTO = 0
 SPF_PARTITION_CONTIGUOUS = 1
 SPF_PARTITION_LOCALITY = 2
@@ -273,6 +274,15 @@ PROTOTYPES = {
     "spf_mplan_label_route_buffers": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp), C.POINTER(_vp),
                                                 C.POINTER(_vp), C.POINTER(C.c_uint64), _u32p,
                                                 C.c_uint32, _u32p]),
+    "spf_mplan_route_snapshot": (C.c_int, [_vp, _u64p, C.c_uint32, C.POINTER(_vp)]),
+    "spf_route_snapshot_destroy": (None, [_vp]),
+    "spf_route_snapshot_bytes": (C.c_uint64, [_vp]),
+    "spf_mplan_route_delta": (C.c_int, [_vp, _vp, _u64p, C.c_uint32, _u64p, C.POINTER(C.c_double)]),
+    "spf_mplan_route_delta_db": (C.c_int, [_vp, C.c_uint32, _u32p, C.c_uint64, C.POINTER(C.c_uint64),
+                                           _u32p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "spf_mplan_route_delta_buffers": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp), C.POINTER(_vp),
+                                                C.POINTER(_vp), C.POINTER(_vp), _u32p, C.c_uint32,
+                                                _u32p]),
     "spf_mplan_enqueue_ns": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_int)]),
     "spf_mplan_execute": (C.c_int, [_vp]),
     "spf_mplan_synchronize": (C.c_int, [_vp]),
@@ -290,6 +300,8 @@ PROTOTYPES = {
     "ls_create_multi": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.c_uint32, C.POINTER(_vp)]),
     "ls_prefetch_all_sources": (C.c_int, [_vp, C.c_int]),
     "ls_all_sources_plan": (_vp, [_vp]),
+    "ls_all_sources_route_snapshot": (C.c_int, [_vp, _u64p, C.c_uint32, C.POINTER(_vp)]),
+    "ls_route_snapshot_close": (None, [_vp, _vp]),
     "ls_destroy": (None, [_vp]),
     "ls_last_error": (C.c_char_p, [_vp]),
     "ls_get_area": (C.c_char_p, [_vp]),

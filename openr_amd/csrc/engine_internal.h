@@ -38,6 +38,14 @@ struct DevBuf {
     p = nullptr;
     n = 0;
   }
+  // o's allocation moved here (nothing copied); o is left empty
+  void take(DevBuf& o) {
+    reset();
+    p = o.p;
+    n = o.n;
+    o.p = nullptr;
+    o.n = 0;
+  }
   hipError_t alloc(size_t count) {
     if (count <= n && p) return hipSuccess;
     reset();
@@ -445,6 +453,43 @@ spf_status launch_label_routes(spf_ctx* c, bool fill, const unsigned long long* 
 uint64_t label_scan_tiles(uint64_t n);
 spf_status launch_label_scan(spf_ctx* c, unsigned long long* d_ptr, uint64_t n,
                              unsigned long long* d_sums, hipStream_t s);
+// Route-database delta between two generations (route_delta.hip), per member:
+// its me slots' node ids, where each me's OLD row started and how long it was,
+// key[e] = link_hash[link_id[e]] over the old and the new CSR, and same[slot]
+// (written by launch_delta_rows: me's row has one key sequence in both).
+struct RouteDeltaIn {
+  const uint32_t* me = nullptr;
+  const uint32_t* old_e0 = nullptr;
+  const uint32_t* old_deg = nullptr;
+  const unsigned long long* key_old = nullptr;
+  const unsigned long long* key_new = nullptr;
+  uint32_t* same = nullptr;
+};
+// blocks per me of the count / fill passes over `cells` routes per me
+uint32_t route_delta_chunks(uint32_t cells);
+spf_status launch_delta_rows(spf_ctx* c, const RouteDeltaIn& in, uint32_t n_me, hipStream_t s);
+// count passes: kind[n_me * cells] (0 unchanged, 1 update, 2 delete) and the
+// changed routes of every block into blk[n_me * route_delta_chunks(cells)].
+// old_*: per me slot the device address of its old headers / region (IP), of
+// its old owner and offset rows and the old record pool (labels); map_old /
+// map_new[u]: label u of the union's group index in its generation.
+spf_status launch_delta_ip(spf_ctx* c, const RouteDeltaIn& in, uint32_t n_me, uint32_t S,
+                           const unsigned long long* new_hdr, const unsigned long long* new_pool,
+                           const unsigned long long* new_base, const unsigned long long* old_hdr,
+                           const unsigned long long* old_pool, uint8_t* kind, unsigned long long* blk,
+                           hipStream_t s);
+spf_status launch_delta_labels(spf_ctx* c, const RouteDeltaIn& in, uint32_t n_me, uint32_t U,
+                               const uint32_t* new_owner, const unsigned long long* new_ptr,
+                               const unsigned long long* new_rec, uint32_t Gn,
+                               const unsigned long long* old_owner, const unsigned long long* old_ptr,
+                               const unsigned long long* old_rec, const uint32_t* map_old,
+                               const uint32_t* map_new, uint8_t* kind, unsigned long long* blk,
+                               hipStream_t s);
+// fill pass over the scanned blk: entries (vals[cell] or the cell index, |
+// SPF_DELTA_DELETE) into dset, dptr[n_me + 1], *deletes += the deleted routes
+spf_status launch_delta_fill(spf_ctx* c, const uint8_t* kind, uint32_t cells, uint32_t n_me,
+                             const unsigned long long* blk, const uint32_t* vals, uint32_t* dset,
+                             unsigned long long* dptr, unsigned long long* deletes, hipStream_t s);
 // pathLinks of `src` from its u32 distance row on the device (spf_preds
 // without the upload; spf_mplan_preds reads a resident row).
 spf_status preds_from_row(spf_ctx* c, uint32_t src, bool hop, const uint32_t* ign,

@@ -206,6 +206,7 @@ struct ls_state {
   spf_mctx* meng = nullptr;
   spf_mplan* all = nullptr;
   bool all_valid = false;  // `all` holds results of the current graph
+  std::vector<spf_route_snapshot*> snaps;  // open route snapshots (ls_all_sources_route_snapshot)
   int all_ulm = 1;
   uint64_t spf_runs = 0;
 
@@ -1197,6 +1198,26 @@ spf_status ls_prefetch_all_sources(ls_state* ls, int ulm) {
 
 spf_mplan* ls_all_sources_plan(ls_state* ls) { return ls && ls->all_valid ? ls->all : nullptr; }
 
+spf_status ls_all_sources_route_snapshot(ls_state* ls, const uint64_t* link_hash, uint32_t n_links,
+                                         spf_route_snapshot** out) {
+  if (!ls || !out) return SPF_E_INVALID;
+  *out = nullptr;
+  if (!ls->all || !ls->all_valid)
+    return lfail(ls, SPF_E_STATE, "ls_all_sources_route_snapshot: no resident all-sources pass");
+  const spf_status st = spf_mplan_route_snapshot(ls->all, link_hash, n_links, out);
+  if (st != SPF_OK) return eng_fail(ls, st);
+  ls->snaps.push_back(*out);
+  return SPF_OK;
+}
+
+void ls_route_snapshot_close(ls_state* ls, spf_route_snapshot* snap) {
+  if (!ls || !snap) return;
+  auto it = std::find(ls->snaps.begin(), ls->snaps.end(), snap);
+  if (it == ls->snaps.end()) return;  // not this state's, or closed already
+  ls->snaps.erase(it);
+  spf_route_snapshot_destroy(snap);
+}
+
 spf_status ls_create(const char* area, int device, ls_state** out) {
   if (!out) return SPF_E_INVALID;
   *out = nullptr;
@@ -1214,6 +1235,7 @@ spf_status ls_create(const char* area, int device, ls_state** out) {
 void ls_destroy(ls_state* ls) {
   if (!ls) return;
   spf_mplan_destroy(ls->all);
+  for (spf_route_snapshot* s : ls->snaps) spf_route_snapshot_destroy(s);  // before their context
   if (ls->meng)
     spf_mctx_destroy(ls->meng);  // owns eng
   else

@@ -156,14 +156,50 @@ uint32_t partition(const uint32_t* nb_ptr, const uint32_t* nb_id, uint32_t n_nod
 
 }  // namespace
 
+// One generation of every me's route databases, moved out of the plan that
+// materialised them (spf_mplan_route_snapshot): the pools per member, and by
+// value what reads them once that plan and its graph are gone.
+struct spf_route_snapshot {
+  spf_mctx* m = nullptr;
+  uint32_t n_nodes = 0, n_sets = 0, flags = 0;
+  std::vector<uint32_t> me;                          // node id of request t
+  std::vector<std::pair<uint32_t, uint32_t>> db_loc;  // request t -> (member, slot)
+  std::vector<uint32_t> row_ptr;                     // the CSR rows as they were
+  bool has_labels = false;
+  uint32_t lr_flags = 0, lr_groups = 0;
+  std::vector<int32_t> labels;                        // labels[g], ascending
+  std::vector<std::pair<uint32_t, uint32_t>> lr_loc;  // request t -> (member, slot)
+  struct Part {
+    DevBuf<unsigned long long> dbhdr, dbpool, lr_ptr, lr_rec, key;
+    DevBuf<uint32_t> lr_owner;
+    std::vector<unsigned long long> h_dbbase;  // per slot: its region's start in dbpool
+    uint64_t bytes = 0;                        // device memory held (allocations' sizes)
+  };
+  std::unique_ptr<Part[]> parts;
+  uint32_t n_parts = 0;
+  ~spf_route_snapshot();
+};
+
 struct spf_mctx {
   std::vector<spf_ctx*> members;
   std::vector<hipStream_t> exec;  // per member: its device's execute stream (shared by repeats)
   std::string err;
+  std::vector<spf_route_snapshot*> snaps;  // live route snapshots (they unlist themselves)
   ~spf_mctx() {
+    while (!snaps.empty()) delete snaps.back();
     for (spf_ctx* c : members) spf_ctx_destroy(c);
   }
 };
+
+spf_route_snapshot::~spf_route_snapshot() {
+  if (!m) return;
+  // (a delta's kernels may still read the pools)
+  for (uint32_t r = 0; r < n_parts && r < m->members.size(); ++r) {
+    (void)hipSetDevice(m->members[r]->device);
+    (void)hipStreamSynchronize(m->exec[r]);
+  }
+  m->snaps.erase(std::remove(m->snaps.begin(), m->snaps.end(), this), m->snaps.end());
+}
 
 struct spf_mplan {
   spf_mctx* m = nullptr;
@@ -204,7 +240,24 @@ struct spf_mplan {
     DevBuf<unsigned long long> lr_ptr, lr_rec, lr_sums;
     std::vector<uint32_t> lr_req;  // per me slot: its index t in the call's me list
     uint64_t lr_records = 0;
+    // route-database delta (spf_mplan_route_delta): per me slot where its old
+    // database lives, the kind bytes and scanned block counts of the IP ([0])
+    // and label ([1]) passes, the lists
+    DevBuf<unsigned long long> dl_ohdr, dl_opool, dl_oown, dl_optr, dl_orec, dl_key, dl_tot;
+    DevBuf<unsigned long long> dl_blk[2], dl_sums[2], dl_ptr[2];
+    DevBuf<uint32_t> dl_e0, dl_deg, dl_same, dl_mold, dl_mnew, dl_lab, dl_set[2];
+    DevBuf<uint8_t> dl_kind[2];
+    std::vector<uint32_t> dl_req;  // per me slot: its index t in the records call's me list
   };
+  // the last spf_mplan_route_delta: request t -> (member, slot)
+  std::vector<std::pair<uint32_t, uint32_t>> dl_loc;
+  // what the last materialising calls were asked (a snapshot keeps them; a
+  // delta checks them): node id of request t, route flags, the labels; *_moved:
+  // a snapshot took the pools
+  std::vector<uint32_t> db_nodes, lr_nodes;
+  std::vector<int32_t> lr_labels;
+  uint32_t db_flags = 0, lr_rflags = 0;
+  bool db_moved = false, lr_moved = false;
   // the last spf_mplan_label_routes: request t -> (member, slot), its groups
   std::vector<std::pair<uint32_t, uint32_t>> lr_loc;
   std::vector<uint32_t> lr_gptr, lr_gnodes;
@@ -986,11 +1039,14 @@ spf_status spf_mplan_route_records(spf_mplan* mp, const uint32_t* me_req, uint32
     return st;
   mp->db_loc.assign(n_me, {0u, 0u});
   mp->db_sets = n_sets;
+  mp->db_flags = flags & SPF_ROUTE_LFA;
+  mp->db_nodes.resize(n_me);
   std::vector<std::vector<uint32_t>> mine(mp->n_parts);
   for (uint32_t t = 0; t < n_me; ++t) {
     const uint32_t r = mp->owner[me_req[t]];
     mp->db_loc[t] = {r, (uint32_t)mine[r].size()};
     mine[r].push_back(mp->srcs[me_req[t]]);
+    mp->db_nodes[t] = mp->srcs[me_req[t]];
   }
   // me's region: one [deg(me)][ts] tile per chunk of ts sets (route_quads_kernel<kRsDb>)
   const uint64_t ts = route_db_tile_sets();
@@ -1067,6 +1123,7 @@ spf_status spf_mplan_route_records(spf_mplan* mp, const uint32_t* me_req, uint32
       worst = std::max(worst, (double)t);
     }
   }
+  mp->db_moved = false;  // (only now: a call that failed after a snapshot leaves SPF_E_STATE standing)
   if (n_records) *n_records = total;
   if (kernel_ms) *kernel_ms = worst;
   return SPF_OK;
@@ -1074,6 +1131,8 @@ spf_status spf_mplan_route_records(spf_mplan* mp, const uint32_t* me_req, uint32
 
 spf_status spf_mplan_route_db(spf_mplan* mp, uint32_t t, uint64_t* hdr, uint64_t* rec, uint64_t cap,
                               uint64_t* n) {
+  if (mp && mp->db_moved)
+    return mfail(mp->m, SPF_E_STATE, "spf_mplan_route_db: a snapshot took the databases (call spf_mplan_route_records)");
   if (!mp || t >= mp->db_loc.size())
     return mfail(mp ? mp->m : nullptr, SPF_E_INVALID, "spf_mplan_route_db: no such me (call spf_mplan_route_records)");
   spf_mctx* m = mp->m;
@@ -1125,8 +1184,9 @@ spf_status spf_mplan_label_routes(spf_mplan* mp, const uint32_t* me_req, uint32_
   const uint32_t N = c0->N;
   mp->lr_gptr.assign((size_t)N + 1, 0);
   mp->lr_gnodes.assign(std::max<uint32_t>(N, 1), 0);
+  mp->lr_labels.assign(std::max<uint32_t>(N, 1), 0);
   uint32_t G = 0;
-  if (const spf_status st = spf_label_groups(node_label, N, nullptr, mp->lr_gptr.data(),
+  if (const spf_status st = spf_label_groups(node_label, N, mp->lr_labels.data(), mp->lr_gptr.data(),
                                              mp->lr_gnodes.data(), &G);
       st != SPF_OK)
     return st;
@@ -1211,7 +1271,12 @@ spf_status spf_mplan_label_routes(spf_mplan* mp, const uint32_t* me_req, uint32_
     }
   }
   mp->lr_loc = std::move(loc);
+  mp->lr_moved = false;
   mp->lr_groups = G;
+  mp->lr_labels.resize(G);
+  mp->lr_rflags = flags & SPF_ROUTE_LFA;
+  mp->lr_nodes.resize(n_me);
+  for (uint32_t t = 0; t < n_me; ++t) mp->lr_nodes[t] = mp->srcs[me_req[t]];
   if (n_labels) *n_labels = G;
   if (n_records) *n_records = total;
   if (pool_bytes) *pool_bytes = bytes;
@@ -1221,6 +1286,9 @@ spf_status spf_mplan_label_routes(spf_mplan* mp, const uint32_t* me_req, uint32_
 
 spf_status spf_mplan_label_route_db(spf_mplan* mp, uint32_t t, uint32_t* owner, uint64_t* ptr,
                                     uint64_t* rec, uint64_t cap, uint64_t* n) {
+  if (mp && mp->lr_moved)
+    return mfail(mp->m, SPF_E_STATE,
+                 "spf_mplan_label_route_db: a snapshot took the databases (call spf_mplan_label_routes)");
   if (!mp || t >= mp->lr_loc.size())
     return mfail(mp ? mp->m : nullptr, SPF_E_INVALID,
                  "spf_mplan_label_route_db: no such me (call spf_mplan_label_routes)");
@@ -1267,6 +1335,335 @@ spf_status spf_mplan_label_route_buffers(spf_mplan* mp, uint32_t member, const u
   if (slots) {
     if (cap < k) return mfail(mp->m, SPF_E_NOMEM, "%u me slots, room for %u", k, cap);
     std::copy(p.lr_req.begin(), p.lr_req.begin() + k, slots);
+  }
+  return SPF_OK;
+}
+
+// ---- route-database delta between two passes -------------------------------
+namespace {
+
+// key[e] = link_hash[link_id[e]] over the member's CSR as it is now
+spf_status edge_keys(spf_mctx* m, const spf_ctx* c, const uint64_t* link_hash, uint32_t n_links,
+                     std::vector<unsigned long long>* out) {
+  out->assign(std::max<uint32_t>(c->E, 1), 0ull);
+  for (uint32_t e = 0; e < c->E; ++e) {
+    if (c->link[e] >= n_links) return mfail(m, SPF_E_INVALID, "link_hash shorter than the link ids");
+    (*out)[e] = link_hash[c->link[e]];
+  }
+  return SPF_OK;
+}
+
+}  // namespace
+
+spf_status spf_mplan_route_snapshot(spf_mplan* mp, const uint64_t* link_hash, uint32_t n_links,
+                                    spf_route_snapshot** out) {
+  if (!mp || !link_hash || !out)
+    return mfail(mp ? mp->m : nullptr, SPF_E_INVALID, "spf_mplan_route_snapshot: NULL argument");
+  *out = nullptr;
+  spf_mctx* m = mp->m;
+  spf_ctx* c0 = m->members[0];
+  if (mp->db_loc.empty() || mp->db_moved)
+    return mfail(m, SPF_E_STATE, "spf_mplan_route_snapshot: the plan holds no route records");
+  const bool labels = !mp->lr_loc.empty() && !mp->lr_moved;
+  if (labels && mp->lr_nodes != mp->db_nodes)
+    return mfail(m, SPF_E_INVALID, "spf_mplan_route_snapshot: label routes and route records of different me lists");
+  std::vector<unsigned long long> key;
+  if (const spf_status st = edge_keys(m, c0, link_hash, n_links, &key); st != SPF_OK) return st;
+  auto sn = std::make_unique<spf_route_snapshot>();
+  sn->n_nodes = c0->N;
+  sn->n_sets = mp->db_sets;
+  sn->flags = mp->db_flags;
+  sn->me = mp->db_nodes;
+  sn->db_loc = mp->db_loc;
+  sn->row_ptr = c0->row_ptr;
+  sn->parts.reset(new spf_route_snapshot::Part[mp->n_parts]);
+  sn->n_parts = mp->n_parts;
+  // the keys first, to every member (the next plan may place a me anywhere):
+  // nothing has moved when an upload fails
+  for (uint32_t r = 0; r < mp->n_parts; ++r) {
+    M_HIP(m, hipSetDevice(m->members[r]->device));
+    M_HIP(m, sn->parts[r].key.upload(key.data(), key.size(), m->exec[r]));
+    M_HIP(m, hipStreamSynchronize(m->exec[r]));  // (`key` is this call's; the databases are complete)
+  }
+  // the members the last call placed a me on (an earlier call's pools on
+  // another member are stale: they stay with the plan)
+  std::vector<uint8_t> used(mp->n_parts, 0);
+  for (const auto& loc : mp->db_loc) used[loc.first] = 1;
+  for (uint32_t r = 0; r < mp->n_parts; ++r) {
+    spf_mplan::Part& p = mp->parts[r];
+    spf_route_snapshot::Part& q = sn->parts[r];
+    q.bytes = 8 * q.key.n;
+    if (!used[r]) continue;
+    q.dbhdr.take(p.dbhdr);
+    q.dbpool.take(p.dbpool);
+    q.h_dbbase = p.h_dbbase;
+    q.bytes += 8 * (q.dbhdr.n + q.dbpool.n);
+    p.db_me.clear();  // the next spf_mplan_route_records allocates afresh
+    p.db_tiles = 0;
+    if (labels) {
+      q.lr_owner.take(p.lr_owner);
+      q.lr_ptr.take(p.lr_ptr);
+      q.lr_rec.take(p.lr_rec);
+      q.bytes += 4 * q.lr_owner.n + 8 * (q.lr_ptr.n + q.lr_rec.n);
+      p.lr_records = 0;
+    }
+  }
+  mp->db_loc.clear();
+  mp->db_moved = true;
+  if (labels) {
+    sn->has_labels = true;
+    sn->lr_flags = mp->lr_rflags;
+    sn->lr_groups = mp->lr_groups;
+    sn->labels = mp->lr_labels;
+    sn->lr_loc = mp->lr_loc;
+    mp->lr_loc.clear();
+    mp->lr_moved = true;
+  }
+  sn->m = m;
+  m->snaps.push_back(sn.get());
+  *out = sn.release();
+  return SPF_OK;
+}
+
+void spf_route_snapshot_destroy(spf_route_snapshot* snap) { delete snap; }
+
+uint64_t spf_route_snapshot_bytes(const spf_route_snapshot* snap) {
+  uint64_t b = 0;
+  for (uint32_t r = 0; snap && r < snap->n_parts; ++r) b += snap->parts[r].bytes;
+  return b;
+}
+
+spf_status spf_mplan_route_delta(spf_mplan* mp, const spf_route_snapshot* snap, const uint64_t* link_hash,
+                                 uint32_t n_links, uint64_t* totals, double* kernel_ms) {
+  if (!mp || !snap || !link_hash)
+    return mfail(mp ? mp->m : nullptr, SPF_E_INVALID, "spf_mplan_route_delta: NULL argument");
+  spf_mctx* m = mp->m;
+  spf_ctx* c0 = m->members[0];
+  if (mp->flags & (SPF_FLAG_DIST64 | SPF_FLAG_HOP_COUNT))
+    return mfail(m, SPF_E_UNSUPPORTED, "route databases need u32 link-metric rows");
+  if (snap->m != m) return mfail(m, SPF_E_INVALID, "spf_mplan_route_delta: the snapshot is another context's");
+  if (mp->db_loc.empty() || mp->db_moved)
+    return mfail(m, SPF_E_STATE, "spf_mplan_route_delta: the plan holds no databases (call spf_mplan_route_records)");
+  const bool labels = !mp->lr_loc.empty() && !mp->lr_moved;
+  if (snap->n_nodes != c0->N || snap->n_sets != mp->db_sets || snap->flags != mp->db_flags ||
+      snap->me != mp->db_nodes)
+    return mfail(m, SPF_E_INVALID, "spf_mplan_route_delta: me list, n_nodes, n_sets or route flags differ from the snapshot");
+  if (labels != snap->has_labels || (labels && (mp->lr_nodes != mp->db_nodes || mp->lr_rflags != snap->lr_flags)))
+    return mfail(m, SPF_E_INVALID, "spf_mplan_route_delta: label routes (presence, me list or flags) differ from the snapshot");
+  std::vector<unsigned long long> key;
+  if (const spf_status st = edge_keys(m, c0, link_hash, n_links, &key); st != SPF_OK) return st;
+  const uint32_t n_me = (uint32_t)mp->db_nodes.size(), S = mp->db_sets;
+  // an old database on another device is read over peer access
+  // (route_prepare of the materialising call tried to enable it)
+  for (uint32_t t = 0; t < n_me; ++t) {
+    const int dn = m->members[mp->db_loc[t].first]->device, dold = m->members[snap->db_loc[t].first]->device;
+    if (dn != dold && mp->peer != 1)
+      return mfail(m, SPF_E_UNSUPPORTED, "route delta across devices needs peer access");
+  }
+  // labels of either generation, ascending, and each one's group index there
+  std::vector<uint32_t> lab, mold, mnew;
+  if (labels) {
+    size_t i = 0, j = 0;
+    const auto& a = snap->labels;
+    const auto& b = mp->lr_labels;
+    while (i < a.size() || j < b.size()) {
+      const bool ta = j == b.size() || (i < a.size() && a[i] <= b[j]);
+      const bool tb = i == a.size() || (j < b.size() && b[j] <= a[i]);
+      lab.push_back((uint32_t)(ta ? a[i] : b[j]));
+      mold.push_back(ta ? (uint32_t)i : 0xFFFFFFFFu);
+      mnew.push_back(tb ? (uint32_t)j : 0xFFFFFFFFu);
+      i += ta;
+      j += tb;
+    }
+  }
+  const uint32_t U = (uint32_t)lab.size(), Gn = mp->lr_groups, Go = snap->lr_groups;
+  const uint32_t cells[2] = {S, U};
+  mp->dl_loc.clear();
+  // per member with work: [0] before the counts, [1] after the scans, [2]
+  // before the fills, [3] after them (the lists are allocated in between, on
+  // the host, from the scans' totals)
+  std::vector<hipEvent_t> ev(4 * mp->n_parts, nullptr);
+  struct Host {
+    std::vector<unsigned long long> ohdr, opool, oown, optr, orec;
+    std::vector<uint32_t> e0, deg, same;
+    unsigned long long tot[2] = {0, 0}, del[2] = {0, 0};
+  };
+  std::vector<Host> host(mp->n_parts);
+  IssuedGuard guard{m, {}, &ev};  // declared after key / host / lab ...: drains before they are freed
+  for (uint32_t r = 0; r < mp->n_parts; ++r) mp->parts[r].dl_req.clear();
+  for (uint32_t t = 0; t < n_me; ++t) mp->parts[mp->db_loc[t].first].dl_req.push_back(t);
+  for (uint32_t r = 0; r < mp->n_parts; ++r) {
+    spf_mplan::Part& p = mp->parts[r];
+    const uint32_t n = (uint32_t)p.dl_req.size();
+    if (!n) continue;
+    spf_ctx* c = m->members[r];
+    Host& h = host[r];
+    for (uint32_t k = 0; k < n; ++k) {  // (slot k of the records call is its k-th me of this member)
+      const uint32_t t = p.dl_req[k], v = mp->db_nodes[t];
+      const auto [ro, ko] = snap->db_loc[t];
+      const spf_route_snapshot::Part& q = snap->parts[ro];
+      h.ohdr.push_back((unsigned long long)(uintptr_t)(q.dbhdr.p + (size_t)ko * S));
+      h.opool.push_back((unsigned long long)(uintptr_t)(q.dbpool.p + q.h_dbbase[ko]));
+      h.e0.push_back(snap->row_ptr[v]);
+      h.deg.push_back(snap->row_ptr[v + 1] - snap->row_ptr[v]);
+      if (labels) {
+        const auto [rl, kl] = snap->lr_loc[t];
+        const spf_route_snapshot::Part& ql = snap->parts[rl];
+        h.oown.push_back((unsigned long long)(uintptr_t)(ql.lr_owner.p + (size_t)kl * Go));
+        h.optr.push_back((unsigned long long)(uintptr_t)(ql.lr_ptr.p + (size_t)kl * Go));
+        h.orec.push_back((unsigned long long)(uintptr_t)ql.lr_rec.p);
+      }
+    }
+    M_HIP(m, hipSetDevice(c->device));
+    guard.members.push_back(r);
+    const hipStream_t s = m->exec[r];
+    M_HIP(m, p.rme.upload(p.db_me.data(), n, s));
+    M_HIP(m, p.dl_ohdr.upload(h.ohdr.data(), n, s));
+    M_HIP(m, p.dl_opool.upload(h.opool.data(), n, s));
+    M_HIP(m, p.dl_e0.upload(h.e0.data(), n, s));
+    M_HIP(m, p.dl_deg.upload(h.deg.data(), n, s));
+    M_HIP(m, p.dl_key.upload(key.data(), key.size(), s));
+    M_HIP(m, p.dl_same.alloc(n));
+    M_HIP(m, p.dl_tot.alloc(2));
+    M_HIP(m, hipMemsetAsync(p.dl_tot.p, 0, 16, s));
+    if (labels) {
+      M_HIP(m, p.dl_oown.upload(h.oown.data(), n, s));
+      M_HIP(m, p.dl_optr.upload(h.optr.data(), n, s));
+      M_HIP(m, p.dl_orec.upload(h.orec.data(), n, s));
+      M_HIP(m, p.dl_mold.upload(mold.data(), U, s));
+      M_HIP(m, p.dl_mnew.upload(mnew.data(), U, s));
+      M_HIP(m, p.dl_lab.upload(lab.data(), U, s));
+    }
+    for (uint32_t w = 0; w < 2; ++w) {
+      const uint64_t nb = (uint64_t)n * route_delta_chunks(cells[w]);
+      M_HIP(m, p.dl_kind[w].alloc(std::max<uint64_t>((uint64_t)n * cells[w], 1)));
+      M_HIP(m, p.dl_blk[w].alloc(nb + 1));
+      M_HIP(m, p.dl_sums[w].alloc(std::max<uint64_t>(label_scan_tiles(nb), 1)));
+      M_HIP(m, p.dl_ptr[w].alloc((size_t)n + 1));
+      M_HIP(m, hipMemsetAsync(p.dl_ptr[w].p, 0, 8ull * (n + 1), s));  // (a pass without cells writes none)
+    }
+    if (kernel_ms) {
+      for (uint32_t k = 0; k < 4; ++k) M_HIP(m, hipEventCreate(&ev[4 * r + k]));
+      M_HIP(m, hipEventRecord(ev[4 * r], s));
+    }
+    RouteDeltaIn in;
+    in.me = p.rme.p;
+    in.old_e0 = p.dl_e0.p;
+    in.old_deg = p.dl_deg.p;
+    in.key_old = snap->parts[r].key.p;
+    in.key_new = p.dl_key.p;
+    in.same = p.dl_same.p;
+    spf_status st = launch_delta_rows(c, in, n, s);
+    if (st == SPF_OK)
+      st = launch_delta_ip(c, in, n, S, p.dbhdr.p, p.dbpool.p, p.dbbase.p, p.dl_ohdr.p, p.dl_opool.p,
+                           p.dl_kind[0].p, p.dl_blk[0].p, s);
+    if (st == SPF_OK) st = launch_label_scan(c, p.dl_blk[0].p, (uint64_t)n * route_delta_chunks(S), p.dl_sums[0].p, s);
+    if (st == SPF_OK && labels)
+      st = launch_delta_labels(c, in, n, U, p.lr_owner.p, p.lr_ptr.p, p.lr_rec.p, Gn, p.dl_oown.p,
+                               p.dl_optr.p, p.dl_orec.p, p.dl_mold.p, p.dl_mnew.p, p.dl_kind[1].p,
+                               p.dl_blk[1].p, s);
+    if (st == SPF_OK) st = launch_label_scan(c, p.dl_blk[1].p, (uint64_t)n * route_delta_chunks(U), p.dl_sums[1].p, s);
+    if (st != SPF_OK) return member_fail(m, r, st);
+    if (kernel_ms) M_HIP(m, hipEventRecord(ev[4 * r + 1], s));
+    for (uint32_t w = 0; w < 2; ++w)
+      M_HIP(m, hipMemcpyAsync(&h.tot[w], p.dl_blk[w].p + (uint64_t)n * route_delta_chunks(cells[w]), 8,
+                              hipMemcpyDeviceToHost, s));
+    h.same.resize(n);
+    M_HIP(m, hipMemcpyAsync(h.same.data(), p.dl_same.p, 4ull * n, hipMemcpyDeviceToHost, s));
+  }
+  for (uint32_t r = 0; r < mp->n_parts; ++r) {
+    spf_mplan::Part& p = mp->parts[r];
+    const uint32_t n = (uint32_t)p.dl_req.size();
+    if (!n) continue;
+    spf_ctx* c = m->members[r];
+    Host& h = host[r];
+    M_HIP(m, hipSetDevice(c->device));
+    const hipStream_t s = m->exec[r];
+    M_HIP(m, hipStreamSynchronize(s));  // the scans' totals
+    for (uint32_t w = 0; w < 2; ++w) M_HIP(m, p.dl_set[w].alloc(std::max<unsigned long long>(h.tot[w], 1)));
+    if (kernel_ms) M_HIP(m, hipEventRecord(ev[4 * r + 2], s));
+    spf_status st = launch_delta_fill(c, p.dl_kind[0].p, S, n, p.dl_blk[0].p, nullptr, p.dl_set[0].p,
+                                      p.dl_ptr[0].p, p.dl_tot.p, s);
+    if (st == SPF_OK && labels)
+      st = launch_delta_fill(c, p.dl_kind[1].p, U, n, p.dl_blk[1].p, p.dl_lab.p, p.dl_set[1].p, p.dl_ptr[1].p,
+                             p.dl_tot.p + 1, s);
+    if (st != SPF_OK) return member_fail(m, r, st);
+    if (kernel_ms) M_HIP(m, hipEventRecord(ev[4 * r + 3], s));
+    M_HIP(m, hipMemcpyAsync(h.del, p.dl_tot.p, 16, hipMemcpyDeviceToHost, s));
+  }
+  double worst = 0;
+  uint64_t out[5] = {0, 0, 0, 0, 0};
+  for (uint32_t r = 0; r < mp->n_parts; ++r) {
+    if (mp->parts[r].dl_req.empty()) continue;
+    M_HIP(m, hipSetDevice(m->members[r]->device));
+    M_HIP(m, hipStreamSynchronize(m->exec[r]));
+    const Host& h = host[r];
+    for (uint32_t w = 0; w < 2; ++w) {
+      out[2 * w] += h.tot[w] - h.del[w];
+      out[2 * w + 1] += h.del[w];
+    }
+    for (uint32_t x : h.same) out[4] += x ? 0u : 1u;
+    if (kernel_ms) {
+      float a = 0, b = 0;
+      M_HIP(m, hipEventElapsedTime(&a, ev[4 * r], ev[4 * r + 1]));
+      M_HIP(m, hipEventElapsedTime(&b, ev[4 * r + 2], ev[4 * r + 3]));
+      worst = std::max(worst, (double)a + (double)b);
+    }
+  }
+  mp->dl_loc = mp->db_loc;
+  if (totals) std::copy(out, out + 5, totals);
+  if (kernel_ms) *kernel_ms = worst;
+  return SPF_OK;
+}
+
+spf_status spf_mplan_route_delta_db(spf_mplan* mp, uint32_t t, uint32_t* ip, uint64_t ip_cap,
+                                    uint64_t* n_ip, uint32_t* label, uint64_t label_cap,
+                                    uint64_t* n_label) {
+  if (!mp || t >= mp->dl_loc.size())
+    return mfail(mp ? mp->m : nullptr, SPF_E_INVALID,
+                 "spf_mplan_route_delta_db: no such me (call spf_mplan_route_delta)");
+  spf_mctx* m = mp->m;
+  const auto [r, k] = mp->dl_loc[t];
+  spf_mplan::Part& p = mp->parts[r];
+  M_HIP(m, hipSetDevice(m->members[r]->device));
+  const hipStream_t s = m->exec[r];
+  uint64_t h[2][2];
+  for (uint32_t w = 0; w < 2; ++w)
+    M_HIP(m, hipMemcpyAsync(h[w], p.dl_ptr[w].p + k, 16, hipMemcpyDeviceToHost, s));
+  M_HIP(m, hipStreamSynchronize(s));
+  uint32_t* const dst[2] = {ip, label};
+  const uint64_t cap[2] = {ip_cap, label_cap};
+  uint64_t* const cnt[2] = {n_ip, n_label};
+  for (uint32_t w = 0; w < 2; ++w) {
+    const uint64_t c = h[w][1] - h[w][0];
+    if (cnt[w]) *cnt[w] = c;
+    if (dst[w] && cap[w] < c)
+      return mfail(m, SPF_E_NOMEM, "route delta of %llu entries, room for %llu", (unsigned long long)c,
+                   (unsigned long long)cap[w]);
+    if (dst[w] && c)
+      M_HIP(m, hipMemcpyAsync(dst[w], p.dl_set[w].p + h[w][0], 4 * c, hipMemcpyDeviceToHost, s));
+  }
+  M_HIP(m, hipStreamSynchronize(s));
+  return SPF_OK;
+}
+
+spf_status spf_mplan_route_delta_buffers(spf_mplan* mp, uint32_t member, const uint64_t** d_ip_ptr,
+                                         const uint32_t** d_ip_set, const uint64_t** d_label_ptr,
+                                         const uint32_t** d_label_set, uint32_t* slots, uint32_t cap,
+                                         uint32_t* n_slots) {
+  if (!mp || member >= mp->n_parts)
+    return mfail(mp ? mp->m : nullptr, SPF_E_INVALID, "spf_mplan_route_delta_buffers: bad argument");
+  const spf_mplan::Part& p = mp->parts[member];
+  const bool has = !mp->dl_loc.empty() && !p.dl_req.empty();
+  const uint32_t k = has ? (uint32_t)p.dl_req.size() : 0u;
+  if (n_slots) *n_slots = k;
+  if (d_ip_ptr) *d_ip_ptr = has ? reinterpret_cast<const uint64_t*>(p.dl_ptr[0].p) : nullptr;
+  if (d_ip_set) *d_ip_set = has ? p.dl_set[0].p : nullptr;
+  if (d_label_ptr) *d_label_ptr = has ? reinterpret_cast<const uint64_t*>(p.dl_ptr[1].p) : nullptr;
+  if (d_label_set) *d_label_set = has ? p.dl_set[1].p : nullptr;
+  if (slots) {
+    if (cap < k) return mfail(mp->m, SPF_E_NOMEM, "%u me slots, room for %u", k, cap);
+    std::copy(p.dl_req.begin(), p.dl_req.begin() + k, slots);
   }
   return SPF_OK;
 }

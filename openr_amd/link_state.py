@@ -10,6 +10,7 @@ reference's ``LinkStateTest.cpp`` / ``DecisionTest.cpp`` drive the C++ one.
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 from dataclasses import dataclass
 from collections.abc import Mapping
 from typing import Dict, Iterable, List, Optional, Sequence, Set, Tuple, Union
@@ -260,6 +261,7 @@ class LinkState(N.NativeHandle):
         self._spf_cache: Dict[Tuple[str, bool], SpfResult] = {}
         self._ksp_cache: Dict[Tuple[str, str, int], List[Path]] = {}
         self._link_cache: Dict[int, Link] = {}
+        self._snaps: "weakref.WeakSet[RouteSnapshot]" = weakref.WeakSet()
 
     # -- helpers ---------------------------------------------------------------
     def _err(self, st: int) -> None:
@@ -541,6 +543,7 @@ class LinkState(N.NativeHandle):
                                            C.byref(ms))
         N.raise_for(st, N.global_error())
         self._db_sets = len(sp) - 1
+        self._db_mes = len(mes)
         return int(tot.value), ms.value
 
     def allSourcesRouteDb(self, t: int):
@@ -617,6 +620,67 @@ class LinkState(N.NativeHandle):
                                                    N.ptr(rec, C.c_uint64), n.value, C.byref(n)),
                     N.global_error())
         return owner[:g], ptr, rec[: n.value]
+
+    def allSourcesRouteSnapshot(self) -> "RouteSnapshot":
+        """The resident pass's route databases (the last
+        allSourcesRouteRecords and, when there was one, allSourcesLabelRoutes)
+        kept as the old generation of a later allSourcesRouteDelta
+        (ls_all_sources_route_snapshot): the device pools move into the
+        snapshot, nothing is copied, and allSourcesRouteDb / LabelRouteDb raise
+        SPF_E_STATE until the next materialising call.  Links are identified by
+        linkValueHashes() as of now.  The snapshot survives this LinkState
+        dropping its resident plan (a row patch, a reload); it is closed with
+        the LinkState at the latest, before the engine context."""
+        lh = self.linkValueHashes()
+        h = C.c_void_p()
+        self._err(N.lib.ls_all_sources_route_snapshot(self._h, N.ptr(lh, C.c_uint64), len(lh),
+                                                      C.byref(h)))
+        snap = RouteSnapshot(self, h)
+        self._snaps.add(snap)
+        return snap
+
+    def allSourcesRouteDelta(self, snapshot: "RouteSnapshot"):
+        """What changed since `snapshot` in every node's route database
+        (spf_mplan_route_delta: DecisionRouteDb::calculateUpdate,
+        Decision.cpp:111-146, for every node on its GPU): the current
+        databases -- allSourcesRouteRecords and allSourcesLabelRoutes called
+        again with the snapshot's node list, sets and LFA choice -- against
+        the snapshot's.  Returns (per node t a tuple (updated sets, deleted
+        sets, updated labels, deleted labels) of ascending int lists, totals
+        [IP updates, IP deletes, label updates, label deletes, nodes compared
+        as sets], the slowest member's kernel ms)."""
+        import numpy as np
+
+        mp = N.lib.ls_all_sources_plan(self._h)
+        if not mp:
+            raise RuntimeError("allSourcesRouteDelta: no resident all-sources pass")
+        if snapshot.closed or snapshot._ls is not self:
+            raise ValueError("allSourcesRouteDelta: not an open snapshot of this LinkState")
+        lh = self.linkValueHashes()
+        tot = np.zeros(5, np.uint64)
+        ms = C.c_double()
+        N.raise_for(N.lib.spf_mplan_route_delta(C.c_void_p(mp), snapshot._h, N.ptr(lh, C.c_uint64),
+                                                len(lh), N.ptr(tot, C.c_uint64), C.byref(ms)),
+                    N.global_error())
+        out = []
+        for t in range(self._db_mes):  # (the delta checked the me list against the records call's)
+            ni, nl = C.c_uint64(), C.c_uint64()
+            N.raise_for(N.lib.spf_mplan_route_delta_db(C.c_void_p(mp), t, None, 0, C.byref(ni), None, 0,
+                                                       C.byref(nl)), N.global_error())
+            ip = np.zeros(max(1, ni.value), np.uint32)
+            lb = np.zeros(max(1, nl.value), np.uint32)
+            N.raise_for(N.lib.spf_mplan_route_delta_db(C.c_void_p(mp), t, N.ptr(ip), ni.value, None,
+                                                       N.ptr(lb), nl.value, None), N.global_error())
+            ip, lb = ip[: ni.value], lb[: nl.value]
+            D, M = N.SPF_DELTA_DELETE, N.SPF_DELTA_DELETE - 1
+            out.append(tuple([int(v & M) for v in a if bool(v & D) == dele]
+                             for a, dele in ((ip, False), (ip, True), (lb, False), (lb, True))))
+        return out, [int(v) for v in tot], ms.value
+
+    def close(self) -> None:
+        for s in list(getattr(self, "_snaps", ())):
+            s.close()
+        super().close()
 
     def allSourcesMplsRoutes(self, t: int):
         """Node t's (index into the last allSourcesLabelRoutes' node list)
@@ -743,6 +807,32 @@ class LinkState(N.NativeHandle):
 
     def engine_handle(self) -> C.c_void_p:
         return C.c_void_p(N.lib.ls_engine(self._h))
+
+
+class RouteSnapshot(N.NativeHandle):
+    """One generation of every node's route databases on the GPUs
+    (``spf_route_snapshot``, from LinkState.allSourcesRouteSnapshot): owned by
+    its LinkState, closed with it at the latest."""
+
+    _LEVEL = 0
+
+    def __init__(self, ls: "LinkState", h: C.c_void_p) -> None:
+        self._ls = ls
+        self._adopt(h)
+
+    @property
+    def deviceBytes(self) -> int:
+        """Device memory the snapshot holds."""
+        return int(N.lib.spf_route_snapshot_bytes(self._h))
+
+    def close(self) -> None:
+        h = getattr(self, "_h", None)
+        ls = getattr(self, "_ls", None)
+        lib = getattr(N, "lib", None)
+        if h is not None and h.value and lib is not None and ls is not None and not ls.closed:
+            lib.ls_route_snapshot_close(ls._h, h)
+        self._h = C.c_void_p()
+        N._LIVE.discard(self)
 
 
 class OwnedLink(N.NativeHandle):

@@ -293,6 +293,53 @@ class DecisionRouteDb:
     def addMplsRoute(self, r: RibMplsEntry) -> None:
         self.mplsRoutes[r.label] = r
 
+    def calculateUpdate(self, newDb: "DecisionRouteDb") -> "DecisionRouteUpdate":
+        """``DecisionRouteDb::calculateUpdate`` (Decision.cpp:111-146): what
+        turns this database into ``newDb`` -- entries of ``newDb`` that are new
+        or compare unequal, and keys of this one that ``newDb`` lacks.  Routes
+        are visited in ascending key order (the reference walks unordered
+        maps: no order to reproduce)."""
+        delta = DecisionRouteUpdate()
+        for prefix in sorted(newDb.unicastRoutes):
+            entry = newDb.unicastRoutes[prefix]
+            if prefix not in self.unicastRoutes or self.unicastRoutes[prefix] != entry:
+                delta.unicastRoutesToUpdate[prefix] = entry
+        delta.unicastRoutesToDelete = [p for p in sorted(self.unicastRoutes)
+                                       if p not in newDb.unicastRoutes]
+        for label in sorted(newDb.mplsRoutes):
+            entry = newDb.mplsRoutes[label]
+            if label not in self.mplsRoutes or self.mplsRoutes[label] != entry:
+                delta.mplsRoutesToUpdate.append(entry)
+        delta.mplsRoutesToDelete = [l for l in sorted(self.mplsRoutes) if l not in newDb.mplsRoutes]
+        return delta
+
+    def update(self, update: "DecisionRouteUpdate") -> None:
+        """``DecisionRouteDb::update`` (Decision.cpp:148-162): deletes first,
+        then insert_or_assign of every updated entry."""
+        for prefix in update.unicastRoutesToDelete:
+            self.unicastRoutes.pop(prefix, None)
+        for entry in update.unicastRoutesToUpdate.values():
+            self.unicastRoutes[entry.prefix] = entry
+        for label in update.mplsRoutesToDelete:
+            self.mplsRoutes.pop(label, None)
+        for entry in update.mplsRoutesToUpdate:
+            self.mplsRoutes[entry.label] = entry
+
+
+@dataclass
+class DecisionRouteUpdate:
+    """``DecisionRouteUpdate`` (RouteUpdate.h): the difference Decision
+    publishes after a rebuild."""
+
+    unicastRoutesToUpdate: Dict[str, RibUnicastEntry] = field(default_factory=dict)
+    unicastRoutesToDelete: List[str] = field(default_factory=list)
+    mplsRoutesToUpdate: List[RibMplsEntry] = field(default_factory=list)
+    mplsRoutesToDelete: List[int] = field(default_factory=list)
+
+    def empty(self) -> bool:
+        return not (self.unicastRoutesToUpdate or self.unicastRoutesToDelete
+                    or self.mplsRoutesToUpdate or self.mplsRoutesToDelete)
+
 
 # enum values of OpenrConfig.thrift:77-85 (getPrefixForwardingTypeAndAlgorithm
 # takes the minimum over the best entries)
