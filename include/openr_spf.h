@@ -699,6 +699,67 @@ spf_status spf_mplan_route_delta_buffers(spf_mplan* mp, uint32_t member, const u
                                          const uint32_t** d_ip_set, const uint64_t** d_label_ptr,
                                          const uint32_t** d_label_set, uint32_t* slots, uint32_t cap,
                                          uint32_t* n_slots);
+/* spf_mplan_route_update: the payload of the last spf_mplan_route_delta -- what
+ * a DecisionRouteUpdate carries besides the routes' names (Decision.cpp:111-146):
+ * the next hops of every listed route, for a label route its owner too --
+ * gathered per member on its device out of the plan's CURRENT databases (the
+ * new generation; the snapshot is not read) into exactly sized, contiguous
+ * pools parallel to the delta's lists.  Per member and kind (IP, labels), over
+ * its `entries` list entries in list order:
+ *   uptr[entries + 1]  u64 offsets; entry j's records are urec[uptr[j] ..
+ *                      uptr[j + 1]): an UPDATE's next hops as its database holds
+ *                      them (u64 = CSR edge | metric << 32 of the current graph,
+ *                      in me's link order), none for a DELETE
+ *   uowner[entries]    labels only: the label's new owner (csr id; me itself:
+ *                      POP_AND_LOOKUP, no records), SPF_UNREACHABLE for a DELETE
+ * Built by count / scan / fill over ordinary launches, no atomics per route;
+ * the pools are allocated from the scan's totals and kept while large enough.
+ * totals (optional) = [4]: IP update entries, IP records, label update entries,
+ * label records; *pool_bytes (optional) = over the members that hold a me,
+ * 8 x records + 8 x (entries + 1) for IP plus the same + 4 x entries for labels;
+ * *kernel_ms (optional) = the slowest member's count + scan + fill
+ * (spf_mplan_route_update_timing: the three apart, ms[3], of the last call that
+ * asked for kernel_ms).  A second call gives identical arrays; a delta without
+ * label routes gives empty label outputs.  SPF_E_STATE when there is no delta,
+ * or when the plan's databases are no longer the ones it compared: a later
+ * spf_mplan_route_records or spf_mplan_label_routes, or a
+ * spf_mplan_route_snapshot that moved the pools away (call the delta again).
+ * The delta's SPF_E_UNSUPPORTED cases are the delta's.  Waits. */
+spf_status spf_mplan_route_update(spf_mplan* mp, uint64_t* totals /* [4] */, uint64_t* pool_bytes,
+                                  double* kernel_ms);
+spf_status spf_mplan_route_update_timing(const spf_mplan* mp, double* ms /* [3]: count, scan, fill */);
+/* me t's payload from the last spf_mplan_route_update, parallel to
+ * spf_mplan_route_delta_db's lists (n_ip / n_label entries come from there):
+ * ip_ptr[n_ip + 1] / label_ptr[n_label + 1] rebased to 0, label_owner[n_label],
+ * the records (ip_cap / label_cap records; SPF_E_NOMEM when fewer than
+ * *n_ip_rec / *n_label_rec).  Every output may be NULL.  SPF_E_STATE without an
+ * update of the last delta.  Waits. */
+spf_status spf_mplan_route_update_db(spf_mplan* mp, uint32_t t, uint64_t* ip_ptr, uint64_t* ip_rec,
+                                     uint64_t ip_cap, uint64_t* n_ip_rec, uint32_t* label_owner,
+                                     uint64_t* label_ptr, uint64_t* label_rec, uint64_t label_cap,
+                                     uint64_t* n_label_rec);
+/* A member's whole share of the last delta and update in one copy per array
+ * (a flap's payload is a few MB; reading it me by me costs a round trip per
+ * me): n (optional) = [5]: its me slots, IP entries, IP records, label entries,
+ * label records -- known on the host, so a first call with every array NULL
+ * sizes the second --, then the delta's dptr[slots + 1] / dset[entries] and the
+ * update's uptr[entries + 1] / urec[records] for IP routes and for labels, and
+ * uowner[label entries]; offsets are the member's (not rebased), slot k's me is
+ * spf_mplan_route_delta_buffers' slots[k].  Every output may be NULL; the
+ * caller's arrays hold at least what n says.  SPF_E_STATE without an update of
+ * the last delta.  Waits. */
+spf_status spf_mplan_route_update_read(spf_mplan* mp, uint32_t member, uint64_t* n /* [5] */,
+                                       uint64_t* ip_dptr, uint32_t* ip_dset, uint64_t* ip_uptr,
+                                       uint64_t* ip_urec, uint64_t* label_dptr, uint32_t* label_dset,
+                                       uint32_t* label_uowner, uint64_t* label_uptr, uint64_t* label_urec);
+/* A member's share of the last spf_mplan_route_update, for device-side
+ * consumers: its uptr / urec device arrays for IP routes, uowner / uptr / urec
+ * for labels (over the entries of spf_mplan_route_delta_buffers' lists; NULL
+ * when it holds no me) and its record totals.  Every output may be NULL. */
+spf_status spf_mplan_route_update_buffers(spf_mplan* mp, uint32_t member, const uint64_t** d_ip_uptr,
+                                          const uint64_t** d_ip_urec, const uint32_t** d_label_uowner,
+                                          const uint64_t** d_label_uptr, const uint64_t** d_label_urec,
+                                          uint64_t* n_ip_rec, uint64_t* n_label_rec);
 /* HIP-event time of each member's executes: ms[member] summed over the last
  * executes since enable / the last call, *n = executes. */
 spf_status spf_mplan_enable_timing(spf_mplan* mp, uint32_t max_executes);

@@ -283,6 +283,16 @@ PROTOTYPES = {
     "spf_mplan_route_delta_buffers": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp), C.POINTER(_vp),
                                                 C.POINTER(_vp), C.POINTER(_vp), _u32p, C.c_uint32,
                                                 _u32p]),
+    "spf_mplan_route_update": (C.c_int, [_vp, _u64p, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "spf_mplan_route_update_timing": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "spf_mplan_route_update_db": (C.c_int, [_vp, C.c_uint32, _u64p, _u64p, C.c_uint64,
+                                            C.POINTER(C.c_uint64), _u32p, _u64p, _u64p, C.c_uint64,
+                                            C.POINTER(C.c_uint64)]),
+    "spf_mplan_route_update_read": (C.c_int, [_vp, C.c_uint32, _u64p, _u64p, _u32p, _u64p, _u64p, _u64p,
+                                              _u32p, _u32p, _u64p, _u64p]),
+    "spf_mplan_route_update_buffers": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp), C.POINTER(_vp),
+                                                 C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
+                                                 C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "spf_mplan_enqueue_ns": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_int)]),
     "spf_mplan_execute": (C.c_int, [_vp]),
     "spf_mplan_synchronize": (C.c_int, [_vp]),

@@ -490,6 +490,28 @@ spf_status launch_delta_labels(spf_ctx* c, const RouteDeltaIn& in, uint32_t n_me
 spf_status launch_delta_fill(spf_ctx* c, const uint8_t* kind, uint32_t cells, uint32_t n_me,
                              const unsigned long long* blk, const uint32_t* vals, uint32_t* dset,
                              unsigned long long* dptr, unsigned long long* deletes, hipStream_t s);
+// The delta's payload (route_update.hip), per member and kind over its delta
+// lists dptr[n_me + 1] / dset[entries].  Count passes: entry j's records into
+// uptr[j] (scanned in place afterwards with launch_label_scan), its first source
+// record | stride << 48 into src[j]; IP from the headers and region starts of
+// the current database, labels (dset holds label values: searched in the
+// delta's union lab[U], mapped by map_new to the new generation's group) from
+// its owner / offset arrays, with the new owner into uowner[j].  Fill: entry j's
+// records from pool into urec[uptr[j] .. uptr[j + 1]), route_update_group()
+// lanes per entry.
+uint32_t route_update_group();
+spf_status launch_update_count_ip(spf_ctx* c, const unsigned long long* dptr, const uint32_t* dset,
+                                  uint32_t n_me, uint64_t entries, const unsigned long long* hdr,
+                                  const unsigned long long* base, uint32_t S, unsigned long long* uptr,
+                                  unsigned long long* src, hipStream_t s);
+spf_status launch_update_count_labels(spf_ctx* c, const unsigned long long* dptr, const uint32_t* dset,
+                                      uint32_t n_me, uint64_t entries, const uint32_t* lab,
+                                      const uint32_t* map_new, uint32_t U, const uint32_t* owner,
+                                      const unsigned long long* ptr, uint32_t G, unsigned long long* uptr,
+                                      unsigned long long* src, uint32_t* uowner, hipStream_t s);
+spf_status launch_update_fill(spf_ctx* c, const unsigned long long* uptr, const unsigned long long* src,
+                              uint64_t entries, const unsigned long long* pool, unsigned long long* urec,
+                              hipStream_t s);
 // pathLinks of `src` from its u32 distance row on the device (spf_preds
 // without the upload; spf_mplan_preds reads a resident row).
 spf_status preds_from_row(spf_ctx* c, uint32_t src, bool hop, const uint32_t* ign,

@@ -248,9 +248,26 @@ struct spf_mplan {
     DevBuf<uint32_t> dl_e0, dl_deg, dl_same, dl_mold, dl_mnew, dl_lab, dl_set[2];
     DevBuf<uint8_t> dl_kind[2];
     std::vector<uint32_t> dl_req;  // per me slot: its index t in the records call's me list
+    uint64_t dl_n[2] = {0, 0};      // entries of the IP / label lists
+    // the delta's payload (spf_mplan_route_update), parallel to dl_set[w]: the
+    // records' u64 offsets, the exactly sized record pools, the new owners of
+    // the label entries; up_src / up_sums: the passes' scratch
+    DevBuf<unsigned long long> up_ptr[2], up_rec[2], up_src[2], up_sums[2];
+    DevBuf<uint32_t> up_owner;
+    uint64_t up_nrec[2] = {0, 0};
   };
   // the last spf_mplan_route_delta: request t -> (member, slot)
   std::vector<std::pair<uint32_t, uint32_t>> dl_loc;
+  // db_gen counts the calls that replace or move the plan's databases
+  // (spf_mplan_route_records, spf_mplan_label_routes, spf_mplan_route_snapshot);
+  // dl_gen: its value at the last delta, whose lists spf_mplan_route_update
+  // resolves in those same databases.  dl_labels / dl_union / dl_tot: whether
+  // that delta had label routes, its label union's size, its totals.
+  uint64_t db_gen = 0, dl_gen = 0;
+  bool dl_labels = false, up_done = false;
+  uint32_t dl_union = 0;
+  uint64_t dl_tot[5] = {0, 0, 0, 0, 0};
+  double up_ms[3] = {0, 0, 0};  // the last update's count / scan / fill (slowest member each)
   // what the last materialising calls were asked (a snapshot keeps them; a
   // delta checks them): node id of request t, route flags, the labels; *_moved:
   // a snapshot took the pools
@@ -1034,6 +1051,7 @@ spf_status spf_mplan_route_records(spf_mplan* mp, const uint32_t* me_req, uint32
                    slots);
   }
   const bool lfa = (flags & SPF_ROUTE_LFA) != 0;
+  ++mp->db_gen;  // (the databases a delta compared are overwritten from here on)
   if (const spf_status st = route_prepare(mp, set_ptr, set_nodes, n_sets, lfa, nullptr, 0, me_req, n_me);
       st != SPF_OK)
     return st;
@@ -1177,6 +1195,7 @@ spf_status spf_mplan_label_routes(spf_mplan* mp, const uint32_t* me_req, uint32_
   for (uint32_t t = 0; t < n_me; ++t)
     if (me_req[t] >= mp->n_src) return mfail(m, SPF_E_INVALID, "me %u is not a request index", me_req[t]);
   const bool lfa = (flags & SPF_ROUTE_LFA) != 0;
+  ++mp->db_gen;
   if (const spf_status st = route_prepare(mp, nullptr, nullptr, 0, lfa, nullptr, 0, me_req, n_me);
       st != SPF_OK)
     return st;
@@ -1410,6 +1429,7 @@ spf_status spf_mplan_route_snapshot(spf_mplan* mp, const uint64_t* link_hash, ui
   }
   mp->db_loc.clear();
   mp->db_moved = true;
+  ++mp->db_gen;
   if (labels) {
     sn->has_labels = true;
     sn->lr_flags = mp->lr_rflags;
@@ -1479,6 +1499,7 @@ spf_status spf_mplan_route_delta(spf_mplan* mp, const spf_route_snapshot* snap, 
   const uint32_t U = (uint32_t)lab.size(), Gn = mp->lr_groups, Go = snap->lr_groups;
   const uint32_t cells[2] = {S, U};
   mp->dl_loc.clear();
+  mp->up_done = false;
   // per member with work: [0] before the counts, [1] after the scans, [2]
   // before the fills, [3] after them (the lists are allocated in between, on
   // the host, from the scans' totals)
@@ -1580,7 +1601,10 @@ spf_status spf_mplan_route_delta(spf_mplan* mp, const spf_route_snapshot* snap, 
     M_HIP(m, hipSetDevice(c->device));
     const hipStream_t s = m->exec[r];
     M_HIP(m, hipStreamSynchronize(s));  // the scans' totals
-    for (uint32_t w = 0; w < 2; ++w) M_HIP(m, p.dl_set[w].alloc(std::max<unsigned long long>(h.tot[w], 1)));
+    for (uint32_t w = 0; w < 2; ++w) {
+      M_HIP(m, p.dl_set[w].alloc(std::max<unsigned long long>(h.tot[w], 1)));
+      p.dl_n[w] = h.tot[w];
+    }
     if (kernel_ms) M_HIP(m, hipEventRecord(ev[4 * r + 2], s));
     spf_status st = launch_delta_fill(c, p.dl_kind[0].p, S, n, p.dl_blk[0].p, nullptr, p.dl_set[0].p,
                                       p.dl_ptr[0].p, p.dl_tot.p, s);
@@ -1611,6 +1635,10 @@ spf_status spf_mplan_route_delta(spf_mplan* mp, const spf_route_snapshot* snap, 
     }
   }
   mp->dl_loc = mp->db_loc;
+  mp->dl_gen = mp->db_gen;
+  mp->dl_labels = labels;
+  mp->dl_union = U;
+  std::copy(out, out + 5, mp->dl_tot);
   if (totals) std::copy(out, out + 5, totals);
   if (kernel_ms) *kernel_ms = worst;
   return SPF_OK;
@@ -1665,6 +1693,210 @@ spf_status spf_mplan_route_delta_buffers(spf_mplan* mp, uint32_t member, const u
     if (cap < k) return mfail(mp->m, SPF_E_NOMEM, "%u me slots, room for %u", k, cap);
     std::copy(p.dl_req.begin(), p.dl_req.begin() + k, slots);
   }
+  return SPF_OK;
+}
+
+// ---- the delta's payload: updated routes with their next hops ----------------
+spf_status spf_mplan_route_update(spf_mplan* mp, uint64_t* totals, uint64_t* pool_bytes, double* kernel_ms) {
+  if (!mp) return mfail(nullptr, SPF_E_INVALID, "spf_mplan_route_update: NULL argument");
+  spf_mctx* m = mp->m;
+  if (mp->dl_loc.empty())
+    return mfail(m, SPF_E_STATE, "spf_mplan_route_update: no delta (call spf_mplan_route_delta)");
+  if (mp->dl_gen != mp->db_gen || mp->db_moved || mp->db_loc.empty())
+    return mfail(m, SPF_E_STATE,
+                 "spf_mplan_route_update: the plan's databases are not the ones the delta compared "
+                 "(call spf_mplan_route_delta again)");
+  const bool labels = mp->dl_labels;
+  const uint32_t S = mp->db_sets, U = mp->dl_union, G = mp->lr_groups;
+  mp->up_done = false;
+  // per member with work: [0] before the counts, [1] after them, [2] after the
+  // scans, [3] before the fills, [4] after them (the pools are allocated in
+  // between, on the host, from the scans' totals)
+  std::vector<hipEvent_t> ev(5 * mp->n_parts, nullptr);
+  std::vector<unsigned long long> tot(2 * mp->n_parts, 0);
+  IssuedGuard guard{m, {}, &ev};  // declared after tot: drains before it is freed
+  for (uint32_t r = 0; r < mp->n_parts; ++r) {
+    spf_mplan::Part& p = mp->parts[r];
+    const uint32_t n = (uint32_t)p.dl_req.size();
+    if (!n) continue;
+    spf_ctx* c = m->members[r];
+    M_HIP(m, hipSetDevice(c->device));
+    guard.members.push_back(r);
+    const hipStream_t s = m->exec[r];
+    for (uint32_t w = 0; w < 2; ++w) {
+      M_HIP(m, p.up_ptr[w].alloc(p.dl_n[w] + 1));
+      M_HIP(m, p.up_src[w].alloc(std::max<uint64_t>(p.dl_n[w], 1)));
+      M_HIP(m, p.up_sums[w].alloc(std::max<uint64_t>(label_scan_tiles(p.dl_n[w]), 1)));
+    }
+    M_HIP(m, p.up_owner.alloc(std::max<uint64_t>(p.dl_n[1], 1)));
+    if (kernel_ms) {
+      for (uint32_t k = 0; k < 5; ++k) M_HIP(m, hipEventCreate(&ev[5 * r + k]));
+      M_HIP(m, hipEventRecord(ev[5 * r], s));
+    }
+    spf_status st = launch_update_count_ip(c, p.dl_ptr[0].p, p.dl_set[0].p, n, p.dl_n[0], p.dbhdr.p, p.dbbase.p,
+                                           S, p.up_ptr[0].p, p.up_src[0].p, s);
+    if (st == SPF_OK && labels)
+      st = launch_update_count_labels(c, p.dl_ptr[1].p, p.dl_set[1].p, n, p.dl_n[1], p.dl_lab.p, p.dl_mnew.p, U,
+                                      p.lr_owner.p, p.lr_ptr.p, G, p.up_ptr[1].p, p.up_src[1].p,
+                                      p.up_owner.p, s);
+    if (st != SPF_OK) return member_fail(m, r, st);
+    if (kernel_ms) M_HIP(m, hipEventRecord(ev[5 * r + 1], s));
+    for (uint32_t w = 0; w < 2 && st == SPF_OK; ++w)
+      st = launch_label_scan(c, p.up_ptr[w].p, p.dl_n[w], p.up_sums[w].p, s);
+    if (st != SPF_OK) return member_fail(m, r, st);
+    if (kernel_ms) M_HIP(m, hipEventRecord(ev[5 * r + 2], s));
+    for (uint32_t w = 0; w < 2; ++w)
+      M_HIP(m, hipMemcpyAsync(&tot[2 * r + w], p.up_ptr[w].p + p.dl_n[w], 8, hipMemcpyDeviceToHost, s));
+  }
+  for (uint32_t r = 0; r < mp->n_parts; ++r) {
+    spf_mplan::Part& p = mp->parts[r];
+    if (p.dl_req.empty()) continue;
+    spf_ctx* c = m->members[r];
+    M_HIP(m, hipSetDevice(c->device));
+    const hipStream_t s = m->exec[r];
+    M_HIP(m, hipStreamSynchronize(s));  // the scans' totals
+    // the record pools: exactly the totals (kept when the previous ones are large enough)
+    for (uint32_t w = 0; w < 2; ++w) {
+      M_HIP(m, p.up_rec[w].alloc(std::max<unsigned long long>(tot[2 * r + w], 1)));
+      p.up_nrec[w] = tot[2 * r + w];
+    }
+    if (kernel_ms) M_HIP(m, hipEventRecord(ev[5 * r + 3], s));
+    spf_status st = launch_update_fill(c, p.up_ptr[0].p, p.up_src[0].p, p.dl_n[0], p.dbpool.p, p.up_rec[0].p, s);
+    if (st == SPF_OK && labels)
+      st = launch_update_fill(c, p.up_ptr[1].p, p.up_src[1].p, p.dl_n[1], p.lr_rec.p, p.up_rec[1].p, s);
+    if (st != SPF_OK) return member_fail(m, r, st);
+    if (kernel_ms) M_HIP(m, hipEventRecord(ev[5 * r + 4], s));
+  }
+  double ms[3] = {0, 0, 0};
+  uint64_t out[4] = {mp->dl_tot[0], 0, mp->dl_tot[2], 0}, bytes = 0;
+  for (uint32_t r = 0; r < mp->n_parts; ++r) {
+    const spf_mplan::Part& p = mp->parts[r];
+    if (p.dl_req.empty()) continue;
+    M_HIP(m, hipSetDevice(m->members[r]->device));
+    M_HIP(m, hipStreamSynchronize(m->exec[r]));
+    out[1] += p.up_nrec[0];
+    out[3] += p.up_nrec[1];
+    bytes += 8 * p.up_nrec[0] + 8 * (p.dl_n[0] + 1) + 8 * p.up_nrec[1] + 8 * (p.dl_n[1] + 1) + 4 * p.dl_n[1];
+    if (kernel_ms) {
+      const uint32_t from[3] = {0, 1, 3};
+      for (uint32_t k = 0; k < 3; ++k) {
+        float t = 0;
+        M_HIP(m, hipEventElapsedTime(&t, ev[5 * r + from[k]], ev[5 * r + from[k] + 1]));
+        ms[k] = std::max(ms[k], (double)t);
+      }
+    }
+  }
+  mp->up_done = true;
+  if (kernel_ms) std::copy(ms, ms + 3, mp->up_ms);
+  if (totals) std::copy(out, out + 4, totals);
+  if (pool_bytes) *pool_bytes = bytes;
+  if (kernel_ms) *kernel_ms = ms[0] + ms[1] + ms[2];
+  return SPF_OK;
+}
+
+spf_status spf_mplan_route_update_timing(const spf_mplan* mp, double* ms) {
+  if (!mp || !ms) return mfail(mp ? mp->m : nullptr, SPF_E_INVALID, "spf_mplan_route_update_timing: NULL argument");
+  std::copy(mp->up_ms, mp->up_ms + 3, ms);
+  return SPF_OK;
+}
+
+spf_status spf_mplan_route_update_db(spf_mplan* mp, uint32_t t, uint64_t* ip_ptr, uint64_t* ip_rec,
+                                     uint64_t ip_cap, uint64_t* n_ip_rec, uint32_t* label_owner,
+                                     uint64_t* label_ptr, uint64_t* label_rec, uint64_t label_cap,
+                                     uint64_t* n_label_rec) {
+  if (mp && (mp->dl_loc.empty() || !mp->up_done))
+    return mfail(mp->m, SPF_E_STATE, "spf_mplan_route_update_db: no update (call spf_mplan_route_update)");
+  if (!mp || t >= mp->dl_loc.size())
+    return mfail(mp ? mp->m : nullptr, SPF_E_INVALID, "spf_mplan_route_update_db: no such me");
+  spf_mctx* m = mp->m;
+  const auto [r, k] = mp->dl_loc[t];
+  spf_mplan::Part& p = mp->parts[r];
+  M_HIP(m, hipSetDevice(m->members[r]->device));
+  const hipStream_t s = m->exec[r];
+  uint64_t e[2][2];  // me's entries [e[w][0], e[w][1]) of either list
+  for (uint32_t w = 0; w < 2; ++w) M_HIP(m, hipMemcpyAsync(e[w], p.dl_ptr[w].p + k, 16, hipMemcpyDeviceToHost, s));
+  M_HIP(m, hipStreamSynchronize(s));
+  uint64_t* const optr[2] = {ip_ptr, label_ptr};
+  uint64_t* const orec[2] = {ip_rec, label_rec};
+  const uint64_t cap[2] = {ip_cap, label_cap};
+  uint64_t* const cnt[2] = {n_ip_rec, n_label_rec};
+  std::vector<uint64_t> h[2];
+  for (uint32_t w = 0; w < 2; ++w) {  // the entries' offsets (the next entry's, or the total, ends the last)
+    h[w].resize(e[w][1] - e[w][0] + 1);
+    M_HIP(m, hipMemcpyAsync(h[w].data(), p.up_ptr[w].p + e[w][0], 8 * h[w].size(), hipMemcpyDeviceToHost, s));
+  }
+  M_HIP(m, hipStreamSynchronize(s));
+  for (uint32_t w = 0; w < 2; ++w) {
+    const uint64_t c = h[w].back() - h[w][0];
+    if (cnt[w]) *cnt[w] = c;
+    if (orec[w] && cap[w] < c)
+      return mfail(m, SPF_E_NOMEM, "route update of %llu records, room for %llu", (unsigned long long)c,
+                   (unsigned long long)cap[w]);
+  }
+  for (uint32_t w = 0; w < 2; ++w) {
+    const uint64_t c = h[w].back() - h[w][0];
+    if (orec[w] && c)
+      M_HIP(m, hipMemcpyAsync(orec[w], p.up_rec[w].p + h[w][0], 8 * c, hipMemcpyDeviceToHost, s));
+    if (optr[w])
+      for (size_t j = 0; j < h[w].size(); ++j) optr[w][j] = h[w][j] - h[w][0];
+  }
+  if (label_owner && e[1][1] > e[1][0])
+    M_HIP(m, hipMemcpyAsync(label_owner, p.up_owner.p + e[1][0], 4 * (e[1][1] - e[1][0]), hipMemcpyDeviceToHost, s));
+  M_HIP(m, hipStreamSynchronize(s));
+  return SPF_OK;
+}
+
+spf_status spf_mplan_route_update_read(spf_mplan* mp, uint32_t member, uint64_t* n, uint64_t* ip_dptr,
+                                       uint32_t* ip_dset, uint64_t* ip_uptr, uint64_t* ip_urec,
+                                       uint64_t* label_dptr, uint32_t* label_dset, uint32_t* label_uowner,
+                                       uint64_t* label_uptr, uint64_t* label_urec) {
+  if (!mp || member >= mp->n_parts)
+    return mfail(mp ? mp->m : nullptr, SPF_E_INVALID, "spf_mplan_route_update_read: bad argument");
+  spf_mctx* m = mp->m;
+  if (mp->dl_loc.empty() || !mp->up_done)
+    return mfail(m, SPF_E_STATE, "spf_mplan_route_update_read: no update (call spf_mplan_route_update)");
+  spf_mplan::Part& p = mp->parts[member];
+  const uint64_t slots = p.dl_req.size();
+  const uint64_t size[5] = {slots, slots ? p.dl_n[0] : 0, slots ? p.up_nrec[0] : 0, slots ? p.dl_n[1] : 0,
+                            slots ? p.up_nrec[1] : 0};
+  if (n) std::copy(size, size + 5, n);
+  if (!slots) return SPF_OK;
+  M_HIP(m, hipSetDevice(m->members[member]->device));
+  const hipStream_t s = m->exec[member];
+  uint64_t* const dptr[2] = {ip_dptr, label_dptr};
+  uint32_t* const dset[2] = {ip_dset, label_dset};
+  uint64_t* const uptr[2] = {ip_uptr, label_uptr};
+  uint64_t* const urec[2] = {ip_urec, label_urec};
+  for (uint32_t w = 0; w < 2; ++w) {
+    const uint64_t e = p.dl_n[w], r = p.up_nrec[w];
+    if (dptr[w]) M_HIP(m, hipMemcpyAsync(dptr[w], p.dl_ptr[w].p, 8 * (slots + 1), hipMemcpyDeviceToHost, s));
+    if (dset[w] && e) M_HIP(m, hipMemcpyAsync(dset[w], p.dl_set[w].p, 4 * e, hipMemcpyDeviceToHost, s));
+    if (uptr[w]) M_HIP(m, hipMemcpyAsync(uptr[w], p.up_ptr[w].p, 8 * (e + 1), hipMemcpyDeviceToHost, s));
+    if (urec[w] && r) M_HIP(m, hipMemcpyAsync(urec[w], p.up_rec[w].p, 8 * r, hipMemcpyDeviceToHost, s));
+  }
+  if (label_uowner && p.dl_n[1])
+    M_HIP(m, hipMemcpyAsync(label_uowner, p.up_owner.p, 4 * p.dl_n[1], hipMemcpyDeviceToHost, s));
+  M_HIP(m, hipStreamSynchronize(s));
+  return SPF_OK;
+}
+
+spf_status spf_mplan_route_update_buffers(spf_mplan* mp, uint32_t member, const uint64_t** d_ip_uptr,
+                                          const uint64_t** d_ip_urec, const uint32_t** d_label_uowner,
+                                          const uint64_t** d_label_uptr, const uint64_t** d_label_urec,
+                                          uint64_t* n_ip_rec, uint64_t* n_label_rec) {
+  if (!mp || member >= mp->n_parts)
+    return mfail(mp ? mp->m : nullptr, SPF_E_INVALID, "spf_mplan_route_update_buffers: bad argument");
+  if (mp->dl_loc.empty() || !mp->up_done)
+    return mfail(mp->m, SPF_E_STATE, "spf_mplan_route_update_buffers: no update (call spf_mplan_route_update)");
+  const spf_mplan::Part& p = mp->parts[member];
+  const bool has = !p.dl_req.empty();  // (a member without a me of the delta holds nothing of it)
+  if (d_ip_uptr) *d_ip_uptr = has ? reinterpret_cast<const uint64_t*>(p.up_ptr[0].p) : nullptr;
+  if (d_ip_urec) *d_ip_urec = has ? reinterpret_cast<const uint64_t*>(p.up_rec[0].p) : nullptr;
+  if (d_label_uowner) *d_label_uowner = has ? p.up_owner.p : nullptr;
+  if (d_label_uptr) *d_label_uptr = has ? reinterpret_cast<const uint64_t*>(p.up_ptr[1].p) : nullptr;
+  if (d_label_urec) *d_label_urec = has ? reinterpret_cast<const uint64_t*>(p.up_rec[1].p) : nullptr;
+  if (n_ip_rec) *n_ip_rec = has ? p.up_nrec[0] : 0;
+  if (n_label_rec) *n_label_rec = has ? p.up_nrec[1] : 0;
   return SPF_OK;
 }
 

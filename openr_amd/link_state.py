@@ -256,6 +256,7 @@ class LinkState(N.NativeHandle):
         N.raise_for(st, N.global_error())
         self._adopt(h)
         self._area = area
+        self._n_members = len(devices) if devices else 1
         self._names: List[Optional[str]] = []
         self._gen = 0
         self._spf_cache: Dict[Tuple[str, bool], SpfResult] = {}
@@ -544,6 +545,7 @@ class LinkState(N.NativeHandle):
         N.raise_for(st, N.global_error())
         self._db_sets = len(sp) - 1
         self._db_mes = len(mes)
+        self._db_me_ids = [int(v) for v in mes]
         return int(tot.value), ms.value
 
     def allSourcesRouteDb(self, t: int):
@@ -676,6 +678,114 @@ class LinkState(N.NativeHandle):
             out.append(tuple([int(v & M) for v in a if bool(v & D) == dele]
                              for a, dele in ((ip, False), (ip, True), (lb, False), (lb, True))))
         return out, [int(v) for v in tot], ms.value
+
+    def allSourcesRouteUpdate(self, snapshot: "RouteSnapshot"):
+        """allSourcesRouteDelta(snapshot) with its payload
+        (spf_mplan_route_update: what a DecisionRouteUpdate carries besides the
+        routes' names): returns the delta's (lists, totals, kernel ms), then
+        per node t a pair ({updated set: u64 records}, {updated label: (owner
+        csr id, u64 records)}) -- the records as allSourcesRouteDb /
+        allSourcesLabelRouteDb hold them, CSR edge | metric << 32 in t's link
+        order, gathered on the GPU into one pool per member, read back in one
+        copy per member and split here for the nodes that have entries -- and a dict of the update's own figures:
+        totals [IP update entries, IP records, label update entries, label
+        records], pool_bytes, kernel_ms, phase_ms [count, scan, fill]."""
+        import numpy as np
+
+        mp = N.lib.ls_all_sources_plan(self._h)
+        if not mp:
+            raise RuntimeError("allSourcesRouteUpdate: no resident all-sources pass")
+        if snapshot.closed or snapshot._ls is not self:
+            raise ValueError("allSourcesRouteUpdate: not an open snapshot of this LinkState")
+        mp = C.c_void_p(mp)
+        lh = self.linkValueHashes()
+        dtot, ms = np.zeros(5, np.uint64), C.c_double()
+        N.raise_for(N.lib.spf_mplan_route_delta(mp, snapshot._h, N.ptr(lh, C.c_uint64), len(lh),
+                                                N.ptr(dtot, C.c_uint64), C.byref(ms)), N.global_error())
+        tot, nbytes, ums = np.zeros(4, np.uint64), C.c_uint64(), C.c_double()
+        N.raise_for(N.lib.spf_mplan_route_update(mp, N.ptr(tot, C.c_uint64), C.byref(nbytes),
+                                                 C.byref(ums)), N.global_error())
+        phase = (C.c_double * 3)()
+        N.raise_for(N.lib.spf_mplan_route_update_timing(mp, phase), N.global_error())
+        lists = [([], [], [], []) for _ in range(self._db_mes)]
+        out = [({}, {}) for _ in range(self._db_mes)]
+        D, M = N.SPF_DELTA_DELETE, N.SPF_DELTA_DELETE - 1
+        for r in range(self._n_members):  # one copy per array and member, split here
+            n = np.zeros(5, np.uint64)
+            N.raise_for(N.lib.spf_mplan_route_update_read(mp, r, N.ptr(n, C.c_uint64), *([None] * 9)),
+                        N.global_error())
+            k, ei, ri, el, rl = (int(v) for v in n)
+            if not k or not ei + el:
+                continue
+            slots = np.zeros(k, np.uint32)
+            N.raise_for(N.lib.spf_mplan_route_delta_buffers(mp, r, None, None, None, None, N.ptr(slots), k,
+                                                            None), N.global_error())
+            dp = [np.zeros(k + 1, np.uint64) for _ in range(2)]
+            ds = [np.zeros(max(1, e), np.uint32) for e in (ei, el)]
+            up = [np.zeros(e + 1, np.uint64) for e in (ei, el)]
+            ur = [np.zeros(max(1, c), np.uint64) for c in (ri, rl)]
+            uo = np.zeros(max(1, el), np.uint32)
+            N.raise_for(N.lib.spf_mplan_route_update_read(
+                mp, r, None, N.ptr(dp[0], C.c_uint64), N.ptr(ds[0]), N.ptr(up[0], C.c_uint64),
+                N.ptr(ur[0], C.c_uint64), N.ptr(dp[1], C.c_uint64), N.ptr(ds[1]), N.ptr(uo),
+                N.ptr(up[1], C.c_uint64), N.ptr(ur[1], C.c_uint64)), N.global_error())
+            for w in range(2):
+                has = np.nonzero(dp[w][1:] > dp[w][:-1])[0]  # only the me that have entries
+                for q in has.tolist():
+                    t = int(slots[q])
+                    a, b = int(dp[w][q]), int(dp[w][q + 1])
+                    ent, at = ds[w][a:b].tolist(), up[w][a: b + 1].tolist()
+                    for j, v in enumerate(ent):
+                        if v & D:
+                            lists[t][2 * w + 1].append(v & M)
+                            continue
+                        lists[t][2 * w].append(v)
+                        rec = ur[w][at[j]: at[j + 1]].copy()
+                        out[t][w][v] = rec if w == 0 else (int(uo[a + j]), rec)
+        self._ru = (lists, out)
+        info = {"totals": [int(v) for v in tot], "pool_bytes": int(nbytes.value),
+                "kernel_ms": ums.value, "phase_ms": list(phase)}
+        return lists, [int(v) for v in dtot], ms.value, out, info
+
+    def allSourcesDecisionRouteUpdate(self, t: int, isV4: bool = False):
+        """Node t's part of the last allSourcesRouteUpdate as the pieces of a
+        DecisionRouteUpdate: ({updated set: set of NextHopThrift} -- one per
+        record over the link as seen from t, no MPLS action --, the deleted
+        sets, the RibMplsEntry of every updated node label -- POP_AND_LOOKUP /
+        PHP / SWAP as allSourcesMplsRoutes decides them --, the deleted
+        labels).  Adjacency-label routes are the host's (allSourcesMplsRoutes)."""
+        from .spf_solver import MplsAction, NextHopThrift, RibMplsEntry, createNextHop
+
+        lists, payload = self._ru
+        up, dele, lup, ldel = lists[int(t)]
+        uip, ulb = payload[int(t)]
+        names, _, col, _, lid, _ = self.flatten()
+        me_id = self._db_me_ids[int(t)]
+        me = names[me_id]
+        area = self.getArea()
+
+        def hops(rec, action):
+            nhs = set()
+            for r in rec.tolist():
+                e, metric = r & 0xFFFFFFFF, r >> 32
+                link = self._link(int(lid[e]))
+                addr = link.getNhV4FromNode(me) if isV4 else link.getNhV6FromNode(me)
+                nhs.add(createNextHop(addr, link.getIfaceFromNode(me), metric, action(e), link.getArea(),
+                                      link.getOtherNodeName(me)))
+            return nhs
+
+        unicast = {p: hops(uip[p], lambda e: None) for p in up}
+        php = MplsAction("PHP")
+        mpls = []
+        for label in lup:
+            o, rec = ulb[label]
+            if o == me_id:
+                mpls.append(RibMplsEntry(label, {NextHopThrift(
+                    bytes(16), None, 0, MplsAction("POP_AND_LOOKUP"), area, None)}))
+                continue
+            swap = MplsAction("SWAP", label, None)
+            mpls.append(RibMplsEntry(label, hops(rec, lambda e: php if int(col[e]) == o else swap)))
+        return unicast, list(dele), mpls, list(ldel)
 
     def close(self) -> None:
         for s in list(getattr(self, "_snaps", ())):
