@@ -558,10 +558,52 @@ spf_status spf_mplan_routes(spf_mplan* mp, uint32_t me_req, const uint32_t* set_
  * header's count has 16 bits and a route keeps up to one next hop per slot.
  * (spf_mplan_label_routes has 64-bit offsets and no such limit.)
  * *n_records (optional) = records over every me; *kernel_ms (optional) = the
- * slowest member's kernel.  The databases stay resident until the next call. */
+ * slowest member's kernel.  The databases stay resident until the next call.
+ *
+ * SPF_ROUTE_COMPACT (alone or with SPF_ROUTE_LFA): the same headers' fields
+ * and the same records in an exactly sized pool.  Per member the routes of its
+ * me slots lie in one contiguous pool of exactly `records` u64, in slot order
+ * and within a me in set order: route (slot k, p) holds pool[base[k] + offset
+ * .. + count), its header = offset | count << 32 | 1 << 48 (stride 1), offset
+ * relative to me's region, which is exactly its records; a route without next
+ * hops has count 0 and the offset where it would start, so base[k] + offset
+ * over (k, p) is the exclusive scan of the counts.  Built by a count walk, a
+ * scan and a fill walk (as spf_mplan_label_routes); *kernel_ms = the three
+ * together.  The 65536-slot and the metric refusals hold as above; the region
+ * limit becomes: SPF_E_UNSUPPORTED when one me has 2^32 records or more.
+ * After a call that failed the plan holds no database. */
+#define SPF_ROUTE_COMPACT 0x2u
 spf_status spf_mplan_route_records(spf_mplan* mp, const uint32_t* me_req, uint32_t n_me,
                                    const uint32_t* set_ptr, const uint32_t* set_nodes, uint32_t n_sets,
                                    uint32_t flags, uint64_t* n_records, double* kernel_ms);
+/* The last spf_mplan_route_records' pools: *layout = 0 tiled, 1 compact;
+ * *pool_bytes = the device bytes of the record pools over the members that
+ * hold a me (tiled: 8 x the regions' slots; compact: 8 x max(records, 1) each
+ * -- a pool left by an earlier compact call is kept while it is large enough,
+ * and counts as allocated); *record_bytes = 8 x records.  Every output may be
+ * NULL.  SPF_E_STATE when the plan holds no database (no call yet, or a
+ * snapshot took it).  spf_mplan_route_records_timing: ms[3] = the count, scan
+ * and fill of the last SPF_ROUTE_COMPACT call that asked for kernel_ms (the
+ * slowest member each). */
+spf_status spf_mplan_route_record_pool(spf_mplan* mp, uint32_t* layout, uint64_t* pool_bytes,
+                                       uint64_t* record_bytes);
+spf_status spf_mplan_route_records_timing(const spf_mplan* mp, double* ms);
+/* A member's share of the last spf_mplan_route_records, for device-side
+ * consumers, in either layout: its header array ([n_slots * n_sets], slot
+ * major), base[n_slots] (where each slot's region starts in the pool) and the
+ * record pool as device arrays (NULL when it holds no me, or a snapshot took
+ * them), its record count, and slots[k] = the index t (into that call's
+ * me_req) of its k-th me slot (cap entries; SPF_E_NOMEM when fewer than
+ * *n_slots).  Route (k, p)'s j-th next hop is pool[base[k] + offset + j *
+ * stride] with offset, count and stride from hdr[k * n_sets + p].  Every
+ * output may be NULL. */
+spf_status spf_mplan_route_record_buffers(spf_mplan* mp, uint32_t member, const uint64_t** d_hdr,
+                                          const uint64_t** d_base, const uint64_t** d_pool,
+                                          uint64_t* n_records, uint32_t* slots, uint32_t cap,
+                                          uint32_t* n_slots);
+/* Records a block of the SPF_ROUTE_COMPACT fill assembles on chip before it
+ * stores them; a block whose routes hold more stores them one by one. */
+uint32_t spf_route_compact_stage(void);
 /* me t's database from the last spf_mplan_route_records, compacted on the
  * host: hdr = [n_sets] headers offset | count << 32 (stride 1: route p's next
  * hops contiguous, routes in set order; may be NULL), rec = its records (cap
@@ -628,7 +670,8 @@ spf_status spf_mplan_label_route_buffers(spf_mplan* mp, uint32_t member, const u
  * databases:
  *
  * spf_mplan_route_snapshot: the old generation, kept.  The device pools of the
- * last spf_mplan_route_records (headers, tiled record regions) and, when there
+ * last spf_mplan_route_records (headers, record regions of either layout: a
+ * delta compares tiled with compact generations freely) and, when there
  * was one, of the last spf_mplan_label_routes (owner / ptr / rec) are MOVED
  * into the snapshot, nothing is copied: the plan holds no database afterwards
  * (spf_mplan_route_db / _label_route_db / _label_route_buffers' pools:

@@ -32,6 +32,7 @@ SPF_FLAG_DIST64 = 0x2
 SPF_UNREACHABLE64 = 0xFFFFFFFFFFFFFFFF
 SPF_KSP2_NONE = 0xFFFFFFFF
 SPF_ROUTE_LFA = 0x1
+SPF_ROUTE_COMPACT = 0x2
 SPF_DELTA_DELETE = 0x80000000
 SPF_PARTITION_AUTO = 0
 SPF_PARTITION_CONTIGUOUS = 1
@@ -265,6 +266,12 @@ PROTOTYPES = {
                                           C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "spf_mplan_route_db": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                      C.c_uint64, C.POINTER(C.c_uint64)]),
+    "spf_mplan_route_record_pool": (C.c_int, [_vp, _u32p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "spf_mplan_route_records_timing": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "spf_mplan_route_record_buffers": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp), C.POINTER(_vp),
+                                                 C.POINTER(_vp), C.POINTER(C.c_uint64), _u32p,
+                                                 C.c_uint32, _u32p]),
+    "spf_route_compact_stage": (C.c_uint32, []),
     "spf_label_groups": (C.c_int, [_i32p, C.c_uint32, _i32p, _u32p, _u32p, _u32p]),
     "spf_mplan_label_routes": (C.c_int, [_vp, _u32p, C.c_uint32, _i32p, C.c_uint32, _u32p,
                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),

@@ -419,15 +419,34 @@ void resident_forget(const spf_ctx* c);
 // its headers (n_sets words), where its region of the record pool starts
 // (n_chunks x 256 x deg(me) records), its record count (zeroed before the
 // launch, added to) and the error flags.
+// The exactly sized layout (SPF_ROUTE_COMPACT; kRsCount / kRsFill) takes two
+// launches, pass = 1 then 2, with launch_label_scan over hdr[n_me * n_sets]
+// (+ 1 for the total) and launch_route_block_starts in between: pass 1 leaves
+// each route's count in hdr, pass 2 reads the scanned hdr and bstart, writes
+// the records into pool and the headers over hdr; base and count are unused.
 struct RouteDbOut {
   unsigned long long* hdr = nullptr;
   unsigned long long* pool = nullptr;
   const unsigned long long* base = nullptr;
   uint32_t* count = nullptr;
   uint32_t* flags = nullptr;
+  uint32_t pass = 0;                           // 0: tiled (kRsDb); 1: count; 2: fill
+  const unsigned long long* bstart = nullptr;  // (fill) per block its first record, the total last
+  uint32_t stage = 0;                          // (fill) records a block may assemble in LDS
+  uint32_t nt = 0;                             // (fill) streaming stores for the spans stored directly
 };
-// sets per kRsDb tile (the [deg][sets] tiles of a route database region)
+// sets per kRsDb tile (the [deg][sets] tiles of a route database region) =
+// routes per block of the count and fill passes
 uint32_t route_db_tile_sets();
+// records a fill block assembles in LDS before it stores them (longer spans
+// are stored directly, with plain stores or, SPF_ROUTE_COMPACT_NT=1, streaming
+// ones; SPF_ROUTE_STAGE=records: A/B, 0 = never)
+uint32_t route_compact_stage();
+// bstart[slot * n_chunks + chunk] = scanned[slot * n_sets + chunk *
+// route_db_tile_sets()], bstart[n_me * n_chunks] = scanned[n_me * n_sets];
+// n_chunks = ceil(n_sets / route_db_tile_sets())
+spf_status launch_route_block_starts(spf_ctx* c, const unsigned long long* d_scanned, uint32_t n_me,
+                                     uint32_t n_sets, unsigned long long* d_bstart, hipStream_t s);
 // Route selection over resident rows for many `me` (routes.hip): digests per
 // me (d_digest, n_me slots, added to), their route databases (db), or
 // spf_routes' records of ONE me.

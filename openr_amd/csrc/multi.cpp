@@ -233,6 +233,10 @@ struct spf_mplan {
     std::vector<uint32_t> db_me, h_dbcnt;
     std::vector<unsigned long long> h_dbbase;
     uint64_t db_tiles = 0;  // sets rounded up to whole 256-set tiles
+    // the exactly sized layout (SPF_ROUTE_COMPACT): the scan's tile sums, every
+    // block's first record; db_compact: dbpool / dbbase hold that layout
+    DevBuf<unsigned long long> dbsums, dbstart;
+    bool db_compact = false;
     // node-label MPLS routes (spf_mplan_label_routes): per (me slot, label
     // group) the owner and the u64 offset of its records (CSR form), the
     // exactly sized record pool, the scan's tile sums
@@ -282,6 +286,10 @@ struct spf_mplan {
   // the last spf_mplan_route_records: request t -> (member, slot), sets
   std::vector<std::pair<uint32_t, uint32_t>> db_loc;
   uint32_t db_sets = 0;
+  // ... its layout (SPF_ROUTE_COMPACT or tiled), and of a compact call the
+  // count / scan / fill ms (slowest member each)
+  bool db_compact = false;
+  double db_ms[3] = {0, 0, 0};
   std::vector<unsigned long long> h_rowp, h_nhp;  // the address tables (host; uploads read them)
   std::vector<unsigned long long> h_nrowp;  // u8 rows, when every member's are exact (else empty)
   std::unique_ptr<Part[]> parts;  // [n_parts]
@@ -1031,6 +1039,138 @@ spf_status spf_mplan_route_digests(spf_mplan* mp, const uint32_t* me_req, uint32
   return SPF_OK;
 }
 
+// spf_mplan_route_records with SPF_ROUTE_COMPACT, after its checks and
+// route_prepare: mine[r] = member r's me (node ids, slot order).  Per member a
+// count walk, the scan of the counts and every block's start, then -- the
+// pool allocated from the scan's total in between, on the host -- the fill
+// walk (routes.hip kRsCount / kRsFill).  Nothing here is sized by tiles x deg.
+static spf_status route_records_compact(spf_mplan* mp, const std::vector<std::vector<uint32_t>>& mine,
+                                        uint32_t n_sets, bool lfa, uint64_t* n_records,
+                                        double* kernel_ms) {
+  spf_mctx* m = mp->m;
+  const uint32_t ts = route_db_tile_sets();
+  const uint32_t n_chunks = (n_sets + ts - 1) / ts;
+  // per member with work: [0] before the count, [1] after it, [2] after the
+  // scan and the block starts, [3] before the fill, [4] after it
+  std::vector<hipEvent_t> ev(5 * mp->n_parts, nullptr);
+  std::vector<std::vector<unsigned long long>> bs(mp->n_parts);
+  std::vector<uint32_t> fl(mp->n_parts, 0);
+  IssuedGuard guard{m, {}, &ev};  // declared after bs / fl: drains before they are freed
+  // (a call that fails from here on leaves no database to read: the headers
+  // hold counts or offsets until the fill has run)
+  struct Drop {
+    spf_mplan* mp;
+    bool keep = false;
+    ~Drop() {
+      if (!keep) mp->db_loc.clear();
+    }
+  } drop{mp};
+  for (uint32_t r = 0; r < mp->n_parts; ++r) {
+    spf_mplan::Part& p = mp->parts[r];
+    if (mine[r].empty()) continue;
+    spf_ctx* c = m->members[r];
+    M_HIP(m, hipSetDevice(c->device));
+    guard.members.push_back(r);
+    const hipStream_t s = m->exec[r];
+    const uint32_t n = (uint32_t)mine[r].size();
+    const uint64_t cells = (uint64_t)n * n_sets, blocks = (uint64_t)n * n_chunks;
+    M_HIP(m, hipStreamSynchronize(s));  // no queued upload still reads the host tables
+    if (!p.db_compact) p.dbpool.reset();  // (the other layout's pool is not this one's size)
+    p.db_compact = true;
+    p.db_tiles = 0;
+    p.db_me = mine[r];
+    M_HIP(m, p.rme.upload(p.db_me.data(), n, s));
+    M_HIP(m, p.dbhdr.alloc(cells + 1));
+    M_HIP(m, p.dbsums.alloc(std::max<uint64_t>(label_scan_tiles(cells), 1)));
+    M_HIP(m, p.dbstart.alloc(blocks + 1));
+    M_HIP(m, p.dbflags.alloc(1));
+    M_HIP(m, hipMemsetAsync(p.dbflags.p, 0, 4, s));
+    if (kernel_ms) {
+      for (uint32_t k = 0; k < 5; ++k) M_HIP(m, hipEventCreate(&ev[5 * r + k]));
+      M_HIP(m, hipEventRecord(ev[5 * r], s));
+    }
+    RouteDbOut db;
+    db.hdr = p.dbhdr.p;
+    db.flags = p.dbflags.p;
+    db.pass = 1;
+    spf_status st = launch_route_sets(c, p.rowp.p, p.nhp.p, p.rme.p, n, p.rsp.p, p.rsn.p, n_sets, lfa, nullptr,
+                                      nullptr, nullptr, nullptr, nullptr, nullptr, s, &db,
+                                      mp->h_nrowp.empty() ? nullptr : p.nrowp.p);
+    if (st != SPF_OK) return member_fail(m, r, st);
+    if (kernel_ms) M_HIP(m, hipEventRecord(ev[5 * r + 1], s));
+    st = launch_label_scan(c, p.dbhdr.p, cells, p.dbsums.p, s);
+    if (st == SPF_OK) st = launch_route_block_starts(c, p.dbhdr.p, n, n_sets, p.dbstart.p, s);
+    if (st != SPF_OK) return member_fail(m, r, st);
+    if (kernel_ms) M_HIP(m, hipEventRecord(ev[5 * r + 2], s));
+    bs[r].resize(blocks + 1);
+    M_HIP(m, hipMemcpyAsync(bs[r].data(), p.dbstart.p, 8ull * (blocks + 1), hipMemcpyDeviceToHost, s));
+    M_HIP(m, hipMemcpyAsync(&fl[r], p.dbflags.p, 4, hipMemcpyDeviceToHost, s));
+  }
+  uint64_t total = 0;
+  for (uint32_t r = 0; r < mp->n_parts; ++r) {
+    spf_mplan::Part& p = mp->parts[r];
+    if (mine[r].empty()) continue;
+    spf_ctx* c = m->members[r];
+    M_HIP(m, hipSetDevice(c->device));
+    const hipStream_t s = m->exec[r];
+    M_HIP(m, hipStreamSynchronize(s));  // the scan's total and the starts
+    if (fl[r] & 2u) return mfail(m, SPF_E_UNSUPPORTED, "a next-hop metric exceeds 2^32 - 1");
+    const uint32_t n = (uint32_t)mine[r].size();
+    p.h_dbbase.assign(n, 0);
+    p.h_dbcnt.assign(n, 0);
+    for (uint32_t k = 0; k < n; ++k) {
+      const unsigned long long b = bs[r][(size_t)k * n_chunks], e = bs[r][(size_t)(k + 1) * n_chunks];
+      if (e - b >= (1ull << 32))
+        return mfail(m, SPF_E_UNSUPPORTED, "route database of node %u: %llu records (2^32 max)", mine[r][k],
+                     e - b);
+      p.h_dbbase[k] = b;
+      p.h_dbcnt[k] = (uint32_t)(e - b);
+    }
+    const unsigned long long tot = bs[r].back();
+    total += tot;
+    // the record pool: exactly the total (kept when the previous compact one is large enough)
+    M_HIP(m, p.dbpool.alloc(std::max<unsigned long long>(tot, 1)));
+    M_HIP(m, p.dbbase.upload(p.h_dbbase.data(), n, s));
+    if (kernel_ms) M_HIP(m, hipEventRecord(ev[5 * r + 3], s));
+    RouteDbOut db;
+    db.hdr = p.dbhdr.p;
+    db.pool = p.dbpool.p;
+    db.flags = p.dbflags.p;
+    db.pass = 2;
+    db.bstart = p.dbstart.p;
+    db.stage = route_compact_stage();
+    if (const char* nte = std::getenv("SPF_ROUTE_COMPACT_NT")) db.nt = nte[0] == '1' ? 1u : 0u;  // (A/B)
+    const spf_status st = launch_route_sets(c, p.rowp.p, p.nhp.p, p.rme.p, n, p.rsp.p, p.rsn.p, n_sets, lfa,
+                                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s, &db,
+                                            mp->h_nrowp.empty() ? nullptr : p.nrowp.p);
+    if (st != SPF_OK) return member_fail(m, r, st);
+    if (kernel_ms) M_HIP(m, hipEventRecord(ev[5 * r + 4], s));
+  }
+  double ms[3] = {0, 0, 0}, worst = 0;
+  for (uint32_t r = 0; r < mp->n_parts; ++r) {
+    if (mine[r].empty()) continue;
+    M_HIP(m, hipSetDevice(m->members[r]->device));
+    M_HIP(m, hipStreamSynchronize(m->exec[r]));
+    if (kernel_ms) {
+      const uint32_t from[3] = {0, 1, 3};
+      double sum = 0;
+      for (uint32_t k = 0; k < 3; ++k) {
+        float t = 0;
+        M_HIP(m, hipEventElapsedTime(&t, ev[5 * r + from[k]], ev[5 * r + from[k] + 1]));
+        ms[k] = std::max(ms[k], (double)t);
+        sum += t;
+      }
+      worst = std::max(worst, sum);
+    }
+  }
+  drop.keep = true;
+  mp->db_moved = false;
+  if (kernel_ms) std::copy(ms, ms + 3, mp->db_ms);
+  if (n_records) *n_records = total;
+  if (kernel_ms) *kernel_ms = worst;
+  return SPF_OK;
+}
+
 spf_status spf_mplan_route_records(spf_mplan* mp, const uint32_t* me_req, uint32_t n_me,
                                    const uint32_t* set_ptr, const uint32_t* set_nodes, uint32_t n_sets,
                                    uint32_t flags, uint64_t* n_records, double* kernel_ms) {
@@ -1066,6 +1206,8 @@ spf_status spf_mplan_route_records(spf_mplan* mp, const uint32_t* me_req, uint32
     mine[r].push_back(mp->srcs[me_req[t]]);
     mp->db_nodes[t] = mp->srcs[me_req[t]];
   }
+  mp->db_compact = (flags & SPF_ROUTE_COMPACT) != 0;
+  if (mp->db_compact) return route_records_compact(mp, mine, n_sets, lfa, n_records, kernel_ms);
   // me's region: one [deg(me)][ts] tile per chunk of ts sets (route_quads_kernel<kRsDb>)
   const uint64_t ts = route_db_tile_sets();
   const uint64_t tiles = ((uint64_t)n_sets + ts - 1) / ts * ts;
@@ -1080,8 +1222,10 @@ spf_status spf_mplan_route_records(spf_mplan* mp, const uint32_t* me_req, uint32
     guard.members.push_back(r);
     const hipStream_t s = m->exec[r];
     const uint32_t n = (uint32_t)mine[r].size();
-    if (p.db_me != mine[r] || p.db_tiles != tiles) {
+    if (p.db_me != mine[r] || p.db_tiles != tiles || p.db_compact) {
       M_HIP(m, hipStreamSynchronize(s));  // no queued upload still reads the host tables
+      if (p.db_compact) p.dbpool.reset();  // (the other layout's pool is not this one's size)
+      p.db_compact = false;
       p.db_me = mine[r];
       p.db_tiles = tiles;
       p.h_dbbase.assign(n, 0);
@@ -1166,7 +1310,9 @@ spf_status spf_mplan_route_db(spf_mplan* mp, uint32_t t, uint64_t* hdr, uint64_t
   const uint32_t S = mp->db_sets;
   std::vector<uint64_t> h(S);
   const uint32_t me = p.db_me[k];
-  const uint64_t region = p.db_tiles * (mp->m->members[r]->row_ptr[me + 1] - mp->m->members[r]->row_ptr[me]);
+  // (the compact layout's region is me's records themselves, stride 1)
+  const uint64_t region =
+      p.db_compact ? cnt : p.db_tiles * (mp->m->members[r]->row_ptr[me + 1] - mp->m->members[r]->row_ptr[me]);
   std::vector<uint64_t> tile(std::max<uint64_t>(region, 1));
   M_HIP(m, hipSetDevice(m->members[r]->device));
   const hipStream_t s = m->exec[r];
@@ -1181,6 +1327,62 @@ spf_status spf_mplan_route_db(spf_mplan* mp, uint32_t t, uint64_t* hdr, uint64_t
       for (uint64_t j = 0; j < c; ++j) rec[at + j] = tile[off + j * stride];
     if (hdr) hdr[q] = at | (c << 32);
     at += c;
+  }
+  return SPF_OK;
+}
+
+spf_status spf_mplan_route_record_pool(spf_mplan* mp, uint32_t* layout, uint64_t* pool_bytes,
+                                       uint64_t* record_bytes) {
+  if (!mp) return mfail(nullptr, SPF_E_INVALID, "spf_mplan_route_record_pool: NULL argument");
+  if (mp->db_loc.empty() || mp->db_moved)
+    return mfail(mp->m, SPF_E_STATE,
+                 "spf_mplan_route_record_pool: the plan holds no route records (call spf_mplan_route_records)");
+  std::vector<uint8_t> used(mp->n_parts, 0);
+  for (const auto& loc : mp->db_loc) used[loc.first] = 1;
+  uint64_t bytes = 0, rec = 0;
+  for (uint32_t r = 0; r < mp->n_parts; ++r) {
+    if (!used[r]) continue;
+    bytes += 8ull * mp->parts[r].dbpool.n;
+    for (const uint32_t c : mp->parts[r].h_dbcnt) rec += c;
+  }
+  if (layout) *layout = mp->db_compact ? 1u : 0u;
+  if (pool_bytes) *pool_bytes = bytes;
+  if (record_bytes) *record_bytes = 8 * rec;
+  return SPF_OK;
+}
+
+uint32_t spf_route_compact_stage(void) { return route_compact_stage(); }
+
+spf_status spf_mplan_route_records_timing(const spf_mplan* mp, double* ms) {
+  if (!mp || !ms) return mfail(mp ? mp->m : nullptr, SPF_E_INVALID, "spf_mplan_route_records_timing: NULL argument");
+  std::copy(mp->db_ms, mp->db_ms + 3, ms);
+  return SPF_OK;
+}
+
+spf_status spf_mplan_route_record_buffers(spf_mplan* mp, uint32_t member, const uint64_t** d_hdr,
+                                          const uint64_t** d_base, const uint64_t** d_pool,
+                                          uint64_t* n_records, uint32_t* slots, uint32_t cap,
+                                          uint32_t* n_slots) {
+  if (!mp || member >= mp->n_parts)
+    return mfail(mp ? mp->m : nullptr, SPF_E_INVALID, "spf_mplan_route_record_buffers: bad argument");
+  const spf_mplan::Part& p = mp->parts[member];
+  // (a member without a me of the last call holds nothing of it)
+  uint32_t k = 0;
+  if (!mp->db_moved)
+    for (const auto& loc : mp->db_loc) k += loc.first == member;
+  const bool has = k != 0;
+  uint64_t rec = 0;
+  if (has)
+    for (const uint32_t c : p.h_dbcnt) rec += c;
+  if (n_slots) *n_slots = k;
+  if (d_hdr) *d_hdr = has ? reinterpret_cast<const uint64_t*>(p.dbhdr.p) : nullptr;
+  if (d_base) *d_base = has ? reinterpret_cast<const uint64_t*>(p.dbbase.p) : nullptr;
+  if (d_pool) *d_pool = has ? reinterpret_cast<const uint64_t*>(p.dbpool.p) : nullptr;
+  if (n_records) *n_records = rec;
+  if (slots) {
+    if (cap < k) return mfail(mp->m, SPF_E_NOMEM, "%u me slots, room for %u", k, cap);
+    for (uint32_t t = 0; t < mp->db_loc.size() && has; ++t)
+      if (mp->db_loc[t].first == member) slots[mp->db_loc[t].second] = t;
   }
   return SPF_OK;
 }

@@ -128,10 +128,41 @@ __device__ __forceinline__ uint64_t rmix64(uint64_t z) {
 //              layout needs no count before the walk (no scan, no atomics, no
 //              second walk); a tile's unused slots are never written.  A metric
 //              past 2^32 - 1 sets flags bit 1.
-constexpr int kRsOne = 0, kRsDigest = 1, kRsDb = 2;
+//   kRsCount / kRsFill  the same databases in an exactly sized pool
+//              (SPF_ROUTE_COMPACT), by two walks with an exclusive scan in
+//              between (launch_label_scan), as label_routes.hip.  Count: the
+//              walk, only hdr[slot * n_sets + p] = the route's count written
+//              (no records, no atomics; a metric past 2^32 - 1 sets flags bit
+//              1).  The scan turns hdr into each route's first record in the
+//              member's pool, slot-then-set order; bstart[slot * n_chunks +
+//              chunk] = the first record of that block's routes (the total
+//              behind the last), so bstart[slot * n_chunks] is me's region
+//              start, base[slot].  Fill: the walk again, route (slot, p)'s
+//              records at pool[hdr .. hdr + count) in link order, then hdr =
+//              (its start - base[slot]) | count << 32 | 1 << 48.  A block's
+//              routes are consecutive sets of one me: their records are one
+//              contiguous span of the pool.  A span of at most db.stage
+//              records is assembled in LDS and flushed with every lane of a
+//              wave on consecutive words (whole lines, streaming stores); a
+//              longer one is written record by record as the walk finds them,
+//              with plain stores that leave a line's sixteen records to L2
+//              (db.nt: streaming ones, four times slower on fabric_full).
+constexpr int kRsOne = 0, kRsDigest = 1, kRsDb = 2, kRsCount = 3, kRsFill = 4;
 constexpr uint32_t kRsThreads = 256;
 constexpr uint32_t kRsGroup = 4;  // consecutive me slots per XCD turn
 constexpr uint32_t kRsLinks = 256;  // me's links staged in LDS per pass
+// kRsFill's span staging, in records (dynamic LDS): 64 KB next to the 10 KB of
+// link staging, two blocks per CU (fabric_full, fill ms at 4,096 / 8,192
+// records: 13.1 / 10.4); the cap is what one block may take of a CU's 160 KB
+constexpr uint32_t kRsStageDefault = 8192, kRsStageMax = 18432;
+extern __shared__ unsigned long long s_stage[];
+
+// a staged span out: lane i of the block on word i, i + threads, ...
+__device__ __forceinline__ void flush_span(unsigned long long* __restrict__ dst, uint32_t n) {
+  __syncthreads();  // every route's records are in s_stage
+  for (uint32_t i = threadIdx.x; i < n; i += kRsThreads) __builtin_nontemporal_store(s_stage[i], dst + i);
+}
+
 template <int MODE>
 __global__ __launch_bounds__(kRsThreads) void route_sets_kernel(
     const unsigned long long* __restrict__ rowp, const unsigned long long* __restrict__ nhp,
@@ -172,6 +203,17 @@ __global__ __launch_bounds__(kRsThreads) void route_sets_kernel(
   // (kRsDb) this block's tile of me's region: [deg][kRsThreads] records
   const uint64_t tile = MODE == kRsDb ? (uint64_t)chunk * kRsThreads * (e1 - e0) : 0ull;
   unsigned long long* const out = MODE == kRsDb ? db.pool + db.base[slot] + tile + threadIdx.x : nullptr;
+  // (kRsFill) this block's span of the pool, and this route's place in it
+  unsigned long long span0 = 0;
+  uint32_t span = 0, rel = 0;
+  bool staged = false;  // block-uniform
+  if constexpr (MODE == kRsFill) {
+    const size_t bi = (size_t)slot * n_chunks + chunk;
+    span0 = db.bstart[bi];
+    span = (uint32_t)(db.bstart[bi + 1] - span0);  // (a me's records fit 32 bits: checked on the host)
+    staged = span <= db.stage;
+    if (live) rel = (uint32_t)(db.hdr[(size_t)slot * n_sets + p] - span0);
+  }
   // me's up links, kRsLinks at a time, staged in LDS by the whole block: the
   // neighbour's bitmap index, its row's address, d_me(x), d_x(me), the link's
   // metric and hash -- formerly a dependent scalar chain per link and thread
@@ -238,6 +280,16 @@ __global__ __launch_bounds__(kRsThreads) void route_sets_kernel(
         wide |= (over >> 32) != 0;
         __builtin_nontemporal_store((unsigned long long)(c0 + t) | (over << 32),
                                     out + (size_t)cnt * kRsThreads);
+      } else if constexpr (MODE == kRsCount) {
+        wide |= (over >> 32) != 0;
+      } else if constexpr (MODE == kRsFill) {
+        const unsigned long long r = (unsigned long long)(c0 + t) | (over << 32);
+        if (staged)
+          s_stage[rel + cnt] = r;
+        else if (db.nt)
+          __builtin_nontemporal_store(r, db.pool + span0 + rel + cnt);
+        else
+          db.pool[span0 + rel + cnt] = r;
       } else {
         const uint32_t deg = e1 - e0;
         out_edge[(size_t)p * deg + cnt] = c0 + t;
@@ -262,6 +314,14 @@ __global__ __launch_bounds__(kRsThreads) void route_sets_kernel(
     if (live)
       db.hdr[(size_t)slot * n_sets + p] = (tile + threadIdx.x) | ((unsigned long long)cnt << 32) |
                                           ((unsigned long long)kRsThreads << 48);
+  } else if constexpr (MODE == kRsCount) {
+    if (wide) atomicOr(db.flags, 2u);
+    if (live) db.hdr[(size_t)slot * n_sets + p] = cnt;
+  } else if constexpr (MODE == kRsFill) {
+    const unsigned long long base = db.bstart[(size_t)slot * n_chunks];
+    if (live)
+      db.hdr[(size_t)slot * n_sets + p] = (span0 - base + rel) | ((unsigned long long)cnt << 32) | (1ull << 48);
+    if (staged) flush_span(db.pool + span0, span);
   } else {
     if (live) {
       out_min[p] = shortest;
@@ -282,7 +342,7 @@ constexpr uint32_t kRqPerBlock = kRqSets * kRsThreads;
 constexpr bool kRqNt = true;  // streaming 32-byte stores (full lines when a wave's routes agree)
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 template <int MODE, typename Dist>
-__global__ __launch_bounds__(kRsThreads) __attribute__((amdgpu_waves_per_eu(MODE == kRsDb && sizeof(Dist) == 4 ? 8 : 1)))
+__global__ __launch_bounds__(kRsThreads) __attribute__((amdgpu_waves_per_eu((MODE == kRsDb || MODE == kRsCount) && sizeof(Dist) == 4 ? 8 : 1)))
 void route_quads_kernel(
     const unsigned long long* __restrict__ rowp, const unsigned long long* __restrict__ nhp,
     uint32_t wpm, const uint32_t* __restrict__ row_ptr, const uint32_t* __restrict__ col,
@@ -346,6 +406,19 @@ void route_quads_kernel(
   const uint64_t tile = MODE == kRsDb ? (uint64_t)chunk * kRqPerBlock * (e1 - e0) : 0ull;
   unsigned long long* const out =
       MODE == kRsDb ? db.pool + db.base[slot] + tile + kRqSets * threadIdx.x : nullptr;
+  // (kRsFill) this block's span of the pool, and the four routes' places in it
+  unsigned long long span0 = 0;
+  uint32_t span = 0, rel[kRqSets] = {0, 0, 0, 0};
+  bool staged = false;  // block-uniform
+  if constexpr (MODE == kRsFill) {
+    const size_t bi = (size_t)slot * n_chunks + chunk;
+    span0 = db.bstart[bi];
+    span = (uint32_t)(db.bstart[bi + 1] - span0);  // (a me's records fit 32 bits: checked on the host)
+    staged = span <= db.stage;
+#pragma unroll
+    for (uint32_t j = 0; j < kRqSets; ++j)
+      if (p0 + j < n_sets) rel[j] = (uint32_t)(db.hdr[(size_t)slot * n_sets + p0 + j] - span0);
+  }
   __shared__ uint32_t s_j[kRsLinks], s_dmx[kRsLinks], s_back[kRsLinks], s_w[kRsLinks];
   __shared__ unsigned long long s_row[kRsLinks], s_lh[kRsLinks], s_row8[kRsLinks];
   bool wide = false;
@@ -431,6 +504,27 @@ void route_quads_kernel(
             rec[j] += rmix64(s_lh[t] + (uint32_t)over[j]);
             ++cnt[j];
           }
+      } else if constexpr (MODE == kRsCount) {
+#pragma unroll
+        for (uint32_t j = 0; j < kRqSets; ++j)
+          if (keep[j]) {
+            wide |= ((uint64_t)over[j] >> 32) != 0;
+            ++cnt[j];
+          }
+      } else if constexpr (MODE == kRsFill) {
+        const unsigned long long eb = c0 + t;
+#pragma unroll
+        for (uint32_t j = 0; j < kRqSets; ++j)
+          if (keep[j]) {
+            const unsigned long long r = eb | ((uint64_t)over[j] << 32);
+            if (staged)
+              s_stage[rel[j] + cnt[j]] = r;
+            else if (db.nt)
+              __builtin_nontemporal_store(r, db.pool + span0 + rel[j] + cnt[j]);
+            else
+              db.pool[span0 + rel[j] + cnt[j]] = r;
+            ++cnt[j];
+          }
       } else {
         const unsigned long long eb = c0 + t;
         if (keep[0] && keep[1] && keep[2] && keep[3] && cnt[0] == cnt[1] && cnt[1] == cnt[2] &&
@@ -476,6 +570,19 @@ void route_quads_kernel(
       h += ((uint64_t)hi2 << 32) | lo2;
     }
     if ((threadIdx.x & 63) == 0 && h) atomicAdd(&digest[slot], (unsigned long long)h);
+  } else if constexpr (MODE == kRsCount) {
+    if (wide) atomicOr(db.flags, 2u);
+#pragma unroll
+    for (uint32_t j = 0; j < kRqSets; ++j)
+      if (p0 + j < n_sets) db.hdr[(size_t)slot * n_sets + p0 + j] = cnt[j];
+  } else if constexpr (MODE == kRsFill) {
+    const unsigned long long base = db.bstart[(size_t)slot * n_chunks];
+#pragma unroll
+    for (uint32_t j = 0; j < kRqSets; ++j)
+      if (p0 + j < n_sets)
+        db.hdr[(size_t)slot * n_sets + p0 + j] =
+            (span0 - base + rel[j]) | ((unsigned long long)cnt[j] << 32) | (1ull << 48);
+    if (staged) flush_span(db.pool + span0, span);
   } else {
     if (wide) atomicOr(db.flags, 2u);
     uint32_t wsum = 0;
@@ -492,11 +599,41 @@ void route_quads_kernel(
   }
 }
 
+// the scanned counts at every block's first route (the total last)
+__global__ __launch_bounds__(kRsThreads) void route_block_starts_kernel(
+    const unsigned long long* __restrict__ scanned, uint32_t n_me, uint32_t n_sets, uint32_t n_chunks,
+    uint32_t per_block, unsigned long long* __restrict__ bstart) {
+  const uint64_t i = (uint64_t)blockIdx.x * kRsThreads + threadIdx.x, n = (uint64_t)n_me * n_chunks;
+  if (i < n)
+    bstart[i] = scanned[i / n_chunks * n_sets + i % n_chunks * per_block];
+  else if (i == n)
+    bstart[i] = scanned[(uint64_t)n_me * n_sets];
+}
+
 }  // namespace
 
 namespace spfi {
 
 uint32_t route_db_tile_sets() { return std::getenv("SPF_ROUTE_SETS1") ? kRsThreads : kRqPerBlock; }
+
+uint32_t route_compact_stage() {
+  const char* e = std::getenv("SPF_ROUTE_STAGE");
+  if (!e) return kRsStageDefault;
+  const long v = std::atol(e);
+  return v < 0 ? 0u : (uint32_t)std::min<long>(v, kRsStageMax);
+}
+
+spf_status launch_route_block_starts(spf_ctx* c, const unsigned long long* d_scanned, uint32_t n_me,
+                                     uint32_t n_sets, unsigned long long* d_bstart, hipStream_t s) {
+  const uint32_t per_block = route_db_tile_sets();
+  const uint32_t n_chunks = (n_sets + per_block - 1) / per_block;
+  const uint64_t n = (uint64_t)n_me * n_chunks + 1, blocks = (n + kRsThreads - 1) / kRsThreads;
+  if (blocks >= (1ull << 31)) return fail(c, SPF_E_INVALID, "route sets: grid too large");
+  hipLaunchKernelGGL(route_block_starts_kernel, dim3((uint32_t)blocks), dim3(kRsThreads), 0, s, d_scanned,
+                     n_me, n_sets, n_chunks, per_block, d_bstart);
+  HIP_TRY(c, hipGetLastError());
+  return SPF_OK;
+}
 
 spf_status launch_route_sets(spf_ctx* c, const unsigned long long* d_rowp,
                              const unsigned long long* d_nhp, const uint32_t* d_me, uint32_t n_me,
@@ -518,7 +655,26 @@ spf_status launch_route_sets(spf_ctx* c, const unsigned long long* d_rowp,
     const bool n32 = !c->needs64 && 2 * B + mm < (uint64_t)kInf && !std::getenv("SPF_ROUTE_U64");
     const dim3 grid((uint32_t)blocks), block(kRsThreads);
     const uint32_t wpm = c->pitch / 32, lf = lfa ? 1u : 0u;
-    if (db && n32)
+    if (db && db->pass) {  // the exactly sized layout: count, or fill (its span staging in dynamic LDS)
+#define ROUTE_QUADS(MODE, DIST, LDS)                                                                      \
+  hipLaunchKernelGGL((route_quads_kernel<MODE, DIST>), grid, block, LDS, s, d_rowp, d_nhp, wpm,          \
+                     c->d_row_ptr.p, c->d_col.p, c->d_wt.p, c->d_link.p, c->d_edge_nb.p, d_me, d_set_ptr, \
+                     d_set_nodes, n_sets, lf, nullptr, nullptr, n_me, n_chunks, *db, d_nrowp)
+      const size_t lds = 8ull * db->stage;
+      if (db->pass == 2)  // (past the default limit of a launch's dynamic LDS)
+        HIP_TRY(c, hipFuncSetAttribute(n32 ? reinterpret_cast<const void*>(&route_quads_kernel<kRsFill, uint32_t>)
+                                           : reinterpret_cast<const void*>(&route_quads_kernel<kRsFill, uint64_t>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      if (db->pass == 1 && n32)
+        ROUTE_QUADS(kRsCount, uint32_t, 0);
+      else if (db->pass == 1)
+        ROUTE_QUADS(kRsCount, uint64_t, 0);
+      else if (n32)
+        ROUTE_QUADS(kRsFill, uint32_t, lds);
+      else
+        ROUTE_QUADS(kRsFill, uint64_t, lds);
+#undef ROUTE_QUADS
+    } else if (db && n32)
       hipLaunchKernelGGL((route_quads_kernel<kRsDb, uint32_t>), grid, block, 0, s, d_rowp, d_nhp, wpm,
                          c->d_row_ptr.p, c->d_col.p, c->d_wt.p, c->d_link.p, c->d_edge_nb.p, d_me,
                          d_set_ptr, d_set_nodes, n_sets, lf, nullptr, nullptr, n_me, n_chunks, *db, d_nrowp);
@@ -545,7 +701,19 @@ spf_status launch_route_sets(spf_ctx* c, const unsigned long long* d_rowp,
   const uint64_t blocks = 8ull * per_xcd * n_chunks;
   if (blocks >= (1ull << 31)) return fail(c, SPF_E_INVALID, "route sets: grid too large");
   const dim3 grid((uint32_t)blocks);
-  if (db)
+  if (db && db->pass == 1)
+    hipLaunchKernelGGL(route_sets_kernel<kRsCount>, grid, dim3(kRsThreads), 0, s, d_rowp, d_nhp,
+                       c->pitch / 32, c->d_row_ptr.p, c->d_col.p, c->d_wt.p, c->d_link.p, c->d_edge_nb.p,
+                       d_me, d_set_ptr, d_set_nodes, n_sets, lfa ? 1u : 0u, nullptr,
+                       nullptr, nullptr, nullptr, nullptr, nullptr, n_me, n_chunks, *db);
+  else if (db && db->pass == 2) {
+    HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&route_sets_kernel<kRsFill>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(8ull * db->stage)));
+    hipLaunchKernelGGL(route_sets_kernel<kRsFill>, grid, dim3(kRsThreads), 8ull * db->stage, s, d_rowp,
+                       d_nhp, c->pitch / 32, c->d_row_ptr.p, c->d_col.p, c->d_wt.p, c->d_link.p,
+                       c->d_edge_nb.p, d_me, d_set_ptr, d_set_nodes, n_sets, lfa ? 1u : 0u, nullptr,
+                       nullptr, nullptr, nullptr, nullptr, nullptr, n_me, n_chunks, *db);
+  } else if (db)
     hipLaunchKernelGGL(route_sets_kernel<kRsDb>, grid, dim3(kRsThreads), 0, s, d_rowp, d_nhp,
                        c->pitch / 32, c->d_row_ptr.p, c->d_col.p, c->d_wt.p, c->d_link.p, c->d_edge_nb.p,
                        d_me, d_set_ptr, d_set_nodes, n_sets, lfa ? 1u : 0u, nullptr,

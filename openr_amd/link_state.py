@@ -524,11 +524,13 @@ class LinkState(N.NativeHandle):
         N.raise_for(st, N.global_error())
         return out[: len(mes)], ms.value
 
-    def allSourcesRouteRecords(self, set_ptr, set_nodes, lfa: bool, mes=None):
+    def allSourcesRouteRecords(self, set_ptr, set_nodes, lfa: bool, mes=None, compact: bool = False):
         """Every node's (or the csr ids in `mes`) route database materialised
         on its owning GPU from the resident all-sources pass
         (spf_mplan_route_records): returns (records over every node, the
-        slowest member's kernel ms); read one node's with allSourcesRouteDb."""
+        slowest member's kernel ms); read one node's with allSourcesRouteDb.
+        compact: the exactly sized pool (SPF_ROUTE_COMPACT) instead of the
+        tiled one; allSourcesRouteRecordPool() tells what either holds."""
         import numpy as np
 
         mp = N.lib.ls_all_sources_plan(self._h)
@@ -540,13 +542,26 @@ class LinkState(N.NativeHandle):
         sn = np.ascontiguousarray(set_nodes if len(set_nodes) else [0], np.uint32)
         tot, ms = C.c_uint64(), C.c_double()
         st = N.lib.spf_mplan_route_records(C.c_void_p(mp), N.ptr(mes), len(mes), N.ptr(sp), N.ptr(sn),
-                                           len(sp) - 1, N.SPF_ROUTE_LFA if lfa else 0, C.byref(tot),
+                                           len(sp) - 1, (N.SPF_ROUTE_LFA if lfa else 0) |
+                                           (N.SPF_ROUTE_COMPACT if compact else 0), C.byref(tot),
                                            C.byref(ms))
         N.raise_for(st, N.global_error())
         self._db_sets = len(sp) - 1
         self._db_mes = len(mes)
         self._db_me_ids = [int(v) for v in mes]
         return int(tot.value), ms.value
+
+    def allSourcesRouteRecordPool(self):
+        """The last allSourcesRouteRecords' pools (spf_mplan_route_record_pool):
+        (layout -- 0 tiled, 1 compact --, the record pools' device bytes, 8 x
+        records)."""
+        mp = N.lib.ls_all_sources_plan(self._h)
+        if not mp:
+            raise RuntimeError("allSourcesRouteRecordPool: no resident all-sources pass")
+        layout, pool, rec = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        N.raise_for(N.lib.spf_mplan_route_record_pool(C.c_void_p(mp), C.byref(layout), C.byref(pool),
+                                                      C.byref(rec)), N.global_error())
+        return int(layout.value), int(pool.value), int(rec.value)
 
     def allSourcesRouteDb(self, t: int):
         """Node t's (index into the last allSourcesRouteRecords' node list)
