@@ -350,6 +350,73 @@ spf_status spf_ksp2_solve(spf_ctx* ctx, const uint32_t* srcs, uint32_t n_src,
                           spf_ksp2_pair* pairs_out, uint32_t* pool_out, uint64_t pool_cap,
                           uint64_t* pool_used);
 
+/* ---- every source's KSP2_ED_ECMP routes (SR-MPLS label stacks) ------------ */
+/* SpfSolver::selectBestPathsKsp2 (Decision.cpp:895-1018) for one area, for
+ * every me = srcs[i] of the plan and every destination set p = set_nodes[
+ * set_ptr[p] .. set_ptr[p + 1]) (a prefix's best advertisers), read from the
+ * device-resident pairs and pool of an spf_ksp2_execute of the same plan that
+ * did not overflow.  No path data crosses to the host.
+ *   candidates  the k = 1 paths of every member in the set's order (list order
+ *               within a member; a member equal to me contributes nothing,
+ *               :923-925), then in the same member order every k = 2 path that
+ *               contains none of the route's k = 1 paths as a contiguous run
+ *               of link ids (LinkState::pathAInPathB, :934-957);
+ *   per path    me -> v1 -> ... -> vk: cost = the sum of the metric each link
+ *               advertises from the node the walk leaves it by (:973); first
+ *               hop = the CSR edge of me's row with the path's first link id;
+ *               label stack in labelVec order = [prepend(vk)?, L(vk), L(vk-1),
+ *               ..., L(v2)] -- the first hop's own label dropped (PHP, :979),
+ *               L(v) = node_label[v] as given (0 = advertises none: the
+ *               reference pushes the thrift default unchecked), prepend = the
+ *               member's set_prepend entry unless it is -1.  An empty stack
+ *               means no MPLS action (:990);
+ *   dedup       the reference collects std::unordered_set<NextHopThrift>: two
+ *               candidates with the same first CSR edge, cost and label
+ *               sequence are one next hop, the first in candidate order kept.
+ *               A 64-bit key pre-filters; equality is decided by walking both
+ *               paths again.
+ * addBestPaths (:1020-1080: the min-nexthop threshold, the static next hops of
+ * a self-advertised prefix), thrift formatting and the union over several
+ * areas stay with the host.
+ * Layout (CSR throughout, exactly sized: count, exclusive scan, fill as
+ * ordinary launches on the plan's context stream, no atomics):
+ *   rptr[n_src * n_sets + 1] u64  route (i, p)'s next hops are
+ *                                 rec[rptr[i * n_sets + p] .. rptr[.. + 1])
+ *   rec[n_hops]              u64  CSR edge | cost << 32 (with negative metrics
+ *                                 the cost's low 32 bits, two's complement)
+ *   lptr[n_hops + 1]         u64  next hop h's stack is lab[lptr[h] .. lptr[h + 1])
+ *   lab[n_label_words]       i32
+ * *pool_bytes = 8 n_hops + 8 (n_src n_sets + 1) + 8 (n_hops + 1) + 4 n_label_words;
+ * *kernel_ms = the three passes together (spf_ksp2_routes_timing: apart); the
+ * outputs are optional.  The pools are kept by the plan while they are large
+ * enough; the same inputs give byte-identical arrays.  Waits.
+ * SPF_E_INVALID: a NULL plan / d_pairs / d_pool / set_ptr / node_label, a set
+ * node >= n_nodes, a non-monotone set_ptr.  SPF_E_UNSUPPORTED: max |metric| x
+ * (n_nodes - 1) >= 2^32 (a cost might not fit the record).  SPF_E_STATE: the
+ * graph changed since the plan was created.  All checked before anything is
+ * launched; after a failed call the plan holds no routes. */
+spf_status spf_ksp2_routes(spf_ksp2_plan* plan, const spf_ksp2_pair* d_pairs, const uint32_t* d_pool,
+                           const uint32_t* set_ptr, const uint32_t* set_nodes, uint32_t n_sets,
+                           const int32_t* set_prepend /* parallel to set_nodes, -1 = none; may be NULL */,
+                           const int32_t* node_label /* [n_nodes] */, uint64_t* n_hops,
+                           uint64_t* n_label_words, uint64_t* pool_bytes, double* kernel_ms);
+/* ms[3] = count, scan, fill of the last spf_ksp2_routes (SPF_E_STATE: none). */
+spf_status spf_ksp2_routes_timing(const spf_ksp2_plan* plan, double* ms);
+/* srcs[i]'s share of the last spf_ksp2_routes, rebased to 0: rptr = [n_sets +
+ * 1], rec = its *n_rec next hops (rec_cap entries; SPF_E_NOMEM when fewer),
+ * lptr = [*n_rec + 1] (needs rec_cap >= *n_rec as well), lab = its *n_lab
+ * label words (lab_cap entries; SPF_E_NOMEM when fewer).  Any output may be
+ * NULL.  SPF_E_STATE when the plan holds no routes.  Waits. */
+spf_status spf_ksp2_route_db(spf_ksp2_plan* plan, uint32_t i, uint64_t* rptr, uint64_t* rec,
+                             uint64_t rec_cap, uint64_t* n_rec, uint64_t* lptr, int32_t* lab,
+                             uint64_t lab_cap, uint64_t* n_lab);
+/* The device arrays of the last spf_ksp2_routes, for device-side consumers
+ * (valid until the next call on the plan); every output may be NULL.
+ * SPF_E_STATE when the plan holds no routes. */
+spf_status spf_ksp2_route_buffers(spf_ksp2_plan* plan, const uint64_t** d_rptr, const uint64_t** d_rec,
+                                  const uint64_t** d_lptr, const int32_t** d_lab, uint64_t* n_hops,
+                                  uint64_t* n_label_words);
+
 /* ---- what-if batches: one source, every single-link failure -------------- */
 /* For each failed link l of the list: the reference's
  * runSpf(src, true, {l}) (LinkState.cpp:808-882 with linksToIgnore = {l}),

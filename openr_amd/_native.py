@@ -229,7 +229,14 @@ PROTOTYPES = {
     "spf_ksp2_enable_timing": (C.c_int, [_vp, C.c_uint32]),
     "spf_ksp2_timing": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), _u32p]),
     "spf_ksp2_solve": (C.c_int, [_vp, _u32p, C.c_uint32, _u32p, _u32p, C.c_uint64, _u64p]),
-    "spf_whatif_plan_create": (C.c_int, [_vp, C.c_uint32, _u32p, C.c_uint32, C.POINTER(_vp)]),
+    "spf_ksp2_routes": (C.c_int, [_vp, _vp, _vp, _u32p, _u32p, C.c_uint32, _i32p, _i32p, _u64p, _u64p,
+                                  _u64p, C.POINTER(C.c_double)]),
+    "spf_ksp2_routes_timing": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "spf_ksp2_route_db": (C.c_int, [_vp, C.c_uint32, _u64p, _u64p, C.c_uint64, _u64p, _u64p, _i32p,
+                                    C.c_uint64, _u64p]),
+    "spf_ksp2_route_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
+                                         C.POINTER(_vp), _u64p, _u64p]),
+    "spf_whatif_plan_create":(C.c_int, [_vp, C.c_uint32, _u32p, C.c_uint32, C.POINTER(_vp)]),
     "spf_whatif_plan_destroy": (None, [_vp]),
     "spf_whatif_plan_failures": (C.c_uint32, [_vp]),
     "spf_whatif_plan_links": (C.c_int, [_vp, _u32p]),

@@ -1,6 +1,6 @@
 // ============================================================================
 //  engine_internal.h -- state shared by the engine's translation units
-//  (spf_engine.hip: SPF/ECMP plans; ksp2.hip: batched KSP2).  Not part of the
+//  (spf_engine.hip: SPF/ECMP plans; ksp2.hip: batched KSP2; ...).  Not part of the
 //  C-ABI: include/openr_spf.h is the boundary.
 // ============================================================================
 #pragma once
@@ -10,6 +10,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -329,6 +330,62 @@ struct spf_plan {
   std::vector<hipEvent_t> ev;
   uint32_t timing_cap = 0, timing_n = 0;
   ~spf_plan() {
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+  }
+};
+
+// A KSP2 source batch (ksp2.hip) and, once spf_ksp2_routes ran on it, every
+// source's KSP2_ED_ECMP routes (ksp2_routes.hip).
+namespace spfi {
+constexpr uint32_t kKsp2Chunk = 64;  // sources per KSP2 workgroup (default)
+constexpr uint32_t kKsp2Grab = 256;  // pool words a KSP2 wave reserves at a time
+
+// spf_ksp2_routes' state: inputs staged on the device, the exactly sized
+// pools (kept while they are large enough) and the last call's totals.
+struct Ksp2Routes {
+  bool valid = false;  // a call succeeded and nothing failed since
+  uint32_t n_sets = 0;
+  uint64_t hops = 0, words = 0;
+  double ms[3] = {0, 0, 0};  // count, scan, fill of the last call
+  uint64_t links_epoch = ~0ull;  // graph epoch d_links was built for
+  uint32_t max_link = 0;
+  DevBuf<uint32_t> d_links;  // per link id 8 words: both directed CSR edges (Ksp2LinkEnds)
+  DevBuf<uint32_t> d_set_ptr, d_set_nodes;
+  DevBuf<int32_t> d_prepend, d_label;
+  DevBuf<unsigned long long> d_rptr, d_lbase, d_sums, d_rec, d_lptr;
+  DevBuf<int32_t> d_lab;
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  ~Ksp2Routes() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+}  // namespace spfi
+
+struct spf_ksp2_plan {
+  spf_ctx* ctx = nullptr;
+  uint32_t n_src = 0, lw = 0;
+  uint32_t delta = 0;  // bucket width of the k = 2 SPF (KspArgs::delta)
+  uint32_t chunk = spfi::kKsp2Chunk;  // sources per workgroup
+  uint32_t grab = spfi::kKsp2Grab;    // pool words per wave reservation
+  uint64_t epoch = 0;  // graph state the plan was derived from
+  std::vector<uint32_t> srcs;
+  spfi::DevBuf<uint32_t> d_srcs, d_D, d_H, d_all, d_wt_rev;
+  spfi::DevBuf<uint8_t> d_no_drain;
+  spfi::DevBuf<unsigned long long> d_prof;  // SPF_KSP2_PROF diagnostics
+  size_t lds = 0;
+  uint32_t lds_waves = 0;  // > 0: the staged-graph kernel with this many waves
+  bool compact = false;     // ... with u16 labels, and the u32 redo pass behind it
+  uint32_t lw_links = 0, redo_waves = 0;
+  size_t redo_lds = 0;
+  spfi::DevBuf<unsigned long long> d_redo;  // [n_src * N] pairs handed to the redo pass
+  std::vector<hipEvent_t> ev;
+  uint32_t timing_cap = 0, timing_n = 0;
+  // outside the batched kernel's envelope (metrics <= 0, u64 labels, more
+  // than 65535 nodes or a working set past the LDS): the exact kernel
+  std::unique_ptr<spfi::ExactKsp2> exact;
+  spfi::Ksp2Routes rt;  // spf_ksp2_routes (ksp2_routes.hip)
+  ~spf_ksp2_plan() {
     for (hipEvent_t e : ev) (void)hipEventDestroy(e);
   }
 };

@@ -43,8 +43,8 @@ namespace {
 constexpr int kKspThreads = 256;             // 4 waves, one pair each
 constexpr int kKspWaves = kKspThreads / 64;
 constexpr int kKspLdsMaxThreads = 1024;      // staged-graph kernel: up to 16 waves
-constexpr uint32_t kKspChunk = 64;          // sources per workgroup (default; SPF_KSP2_CHUNK)
-constexpr uint32_t kPoolGrab = 256;         // words a wave reserves at a time (~ its pairs' paths)
+constexpr uint32_t kKspChunk = spfi::kKsp2Chunk;  // sources per workgroup (default; SPF_KSP2_CHUNK)
+constexpr uint32_t kPoolGrab = spfi::kKsp2Grab;   // words a wave reserves at a time (~ its pairs' paths)
 constexpr size_t kMaxLdsKsp = 160 * 1024;
 constexpr uint32_t kCompactCap = 512;       // u16-label waves: DFS stack / SPF queue entries
 constexpr uint32_t kRedoBlocks = 256;       // workgroups of the u32 redo pass
@@ -889,33 +889,6 @@ __global__ __launch_bounds__(256) void ksp2_digest_kernel(const spf_ksp2_pair* _
   atomicAdd(&out[i], (unsigned long long)dg_mix64(h + dg_mix64((uint64_t)d + 1)));
 }
 }  // namespace
-
-struct spf_ksp2_plan {
-  spf_ctx* ctx = nullptr;
-  uint32_t n_src = 0, lw = 0;
-  uint32_t delta = 0;  // bucket width of the k = 2 SPF (KspArgs::delta)
-  uint32_t chunk = kKspChunk;  // sources per workgroup
-  uint32_t grab = kPoolGrab;   // pool words per wave reservation
-  uint64_t epoch = 0;  // graph state the plan was derived from
-  std::vector<uint32_t> srcs;
-  DevBuf<uint32_t> d_srcs, d_D, d_H, d_all, d_wt_rev;
-  DevBuf<uint8_t> d_no_drain;
-  DevBuf<unsigned long long> d_prof;  // SPF_KSP2_PROF diagnostics
-  size_t lds = 0;
-  uint32_t lds_waves = 0;  // > 0: the staged-graph kernel with this many waves
-  bool compact = false;     // ... with u16 labels, and the u32 redo pass behind it
-  uint32_t lw_links = 0, redo_waves = 0;
-  size_t redo_lds = 0;
-  DevBuf<unsigned long long> d_redo;  // [n_src * N] pairs handed to the redo pass
-  std::vector<hipEvent_t> ev;
-  uint32_t timing_cap = 0, timing_n = 0;
-  // outside the batched kernel's envelope (metrics <= 0, u64 labels, more
-  // than 65535 nodes or a working set past the LDS): the exact kernel
-  std::unique_ptr<spfi::ExactKsp2> exact;
-  ~spf_ksp2_plan() {
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-  }
-};
 
 extern "C" {
 

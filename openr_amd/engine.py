@@ -233,8 +233,113 @@ class Ksp2Plan(NativeHandle):
         self._eng._err(N.lib.spf_ksp2_timing(self._h, C.byref(a), C.byref(b), C.byref(n)))
         return a.value, b.value, n.value
 
+    # ---- KSP2_ED_ECMP routes of every source (spf_ksp2_routes) ---------------------
+    def routes(self, d_pairs: int, d_pool: int, set_ptr, set_nodes, node_label,
+               set_prepend=None) -> Tuple[int, int, int, float]:
+        """selectBestPathsKsp2's next hops of every source of the plan towards
+        every set ``set_nodes[set_ptr[p]:set_ptr[p + 1]]``, built on the GPU
+        from an execute's device pairs and pool (no overflow) into exactly
+        sized device pools.  node_label: i32 per node (0 = none); set_prepend:
+        i32 parallel to set_nodes (-1 = none).  Returns (next hops, label
+        words, pool bytes, kernel ms of count + scan + fill)."""
+        sp = np.ascontiguousarray(set_ptr, np.uint32)
+        sn = np.ascontiguousarray(set_nodes, np.uint32)
+        lab = np.ascontiguousarray(node_label, np.int32)
+        pre = None if set_prepend is None else np.ascontiguousarray(set_prepend, np.int32)
+        if len(sp) < 1 or len(sn) < int(sp.max()):
+            raise ValueError("set_ptr / set_nodes length mismatch")
+        if pre is not None and len(pre) != len(sn):
+            raise ValueError("set_prepend must be parallel to set_nodes")
+        if len(lab) < self._eng.n_nodes:
+            raise ValueError("node_label needs one entry per node")
+        pad = np.zeros(1, np.uint32)
+        hops, words, nbytes, ms = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_double()
+        self._rt_sets = None
+        self._eng._err(N.lib.spf_ksp2_routes(
+            self._h, C.c_void_p(d_pairs), C.c_void_p(d_pool), N.ptr(sp), N.ptr(sn if len(sn) else pad),
+            len(sp) - 1, None if pre is None else N.ptr(pre if len(pre) else pad.view(np.int32), C.c_int32),
+            N.ptr(lab, C.c_int32), C.byref(hops), C.byref(words), C.byref(nbytes), C.byref(ms)))
+        self._rt_sets = len(sp) - 1
+        return hops.value, words.value, nbytes.value, ms.value
 
-DIGEST_DTYPE = np.dtype([("n_dist_changed", "<u4"), ("n_nh_changed", "<u4"),
+    def routes_timing(self) -> Tuple[float, float, float]:
+        """(count, scan, fill) ms of the last routes() (spf_ksp2_routes_timing)."""
+        ms = (C.c_double * 3)()
+        self._eng._err(N.lib.spf_ksp2_routes_timing(self._h, ms))
+        return ms[0], ms[1], ms[2]
+
+    def route_db(self, i: int):
+        """Source slot i's share of the last routes(), rebased to 0: (rptr u64
+        [n_sets + 1], rec u64 = CSR edge | cost << 32, lptr u64 [len(rec) + 1],
+        lab i32): route p's next hops are rec[rptr[p]:rptr[p + 1]], next hop
+        h's label stack is lab[lptr[h]:lptr[h + 1]] (spf_ksp2_route_db)."""
+        n_rec, n_lab = C.c_uint64(), C.c_uint64()
+        sets = getattr(self, "_rt_sets", None) or 0
+        rptr = np.zeros(sets + 1, np.uint64)
+        self._eng._err(N.lib.spf_ksp2_route_db(self._h, int(i), N.ptr(rptr, C.c_uint64), None, 0,
+                                               C.byref(n_rec), None, None, 0, C.byref(n_lab)))
+        rec = np.zeros(max(1, n_rec.value), np.uint64)
+        lptr = np.zeros(n_rec.value + 1, np.uint64)
+        lab = np.zeros(max(1, n_lab.value), np.int32)
+        self._eng._err(N.lib.spf_ksp2_route_db(self._h, int(i), None, N.ptr(rec, C.c_uint64),
+                                               n_rec.value, None, N.ptr(lptr, C.c_uint64),
+                                               N.ptr(lab, C.c_int32), n_lab.value, None))
+        return rptr, rec[: n_rec.value], lptr, lab[: n_lab.value]
+
+    def route_buffers(self) -> Tuple[int, int, int, int, int, int]:
+        """Device addresses (rptr, rec, lptr, lab) of the last routes() and its
+        (next hops, label words), for device-side consumers
+        (spf_ksp2_route_buffers)."""
+        p = [C.c_void_p() for _ in range(4)]
+        hops, words = C.c_uint64(), C.c_uint64()
+        self._eng._err(N.lib.spf_ksp2_route_buffers(self._h, *[C.byref(x) for x in p],
+                                                    C.byref(hops), C.byref(words)))
+        return tuple(int(x.value or 0) for x in p) + (hops.value, words.value)
+
+
+class Ksp2Routes:
+    """Every source's KSP2_ED_ECMP next hops (SpfEngine.ksp2_routes): the plan
+    that holds the device pools, the path buffers they were built from and the
+    totals.  ``close()`` releases them."""
+
+    def __init__(self, plan: Ksp2Plan, bufs, totals: Tuple[int, int, int, float]) -> None:
+        self.plan = plan
+        self.srcs = plan.srcs
+        self._bufs = bufs
+        self.hops, self.label_words, self.pool_bytes, self.kernel_ms = totals
+        self._dbs: dict = {}
+
+    def db(self, i: int):
+        hit = self._dbs.get(int(i))
+        if hit is None:
+            hit = self._dbs[int(i)] = self.plan.route_db(int(i))
+        return hit
+
+    def nexthops(self, i: int, p: int) -> List[Tuple[int, int, Tuple[int, ...]]]:
+        """Route (srcs[i], set p): [(CSR edge, cost, label stack in labelVec
+        order)] in candidate order, first occurrences kept."""
+        rptr, rec, lptr, lab = self.db(i)
+        out = []
+        for h in range(int(rptr[p]), int(rptr[p + 1])):
+            r = int(rec[h])
+            out.append((r & 0xFFFFFFFF, r >> 32,
+                        tuple(int(x) for x in lab[int(lptr[h]): int(lptr[h + 1])])))
+        return out
+
+    def close(self) -> None:
+        self.plan.close()
+        for b in self._bufs:
+            b.free()
+        self._bufs = ()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+
+DIGEST_DTYPE =np.dtype([("n_dist_changed", "<u4"), ("n_nh_changed", "<u4"),
                          ("hash", "<u8")])  # spf_whatif_digest
 
 
@@ -282,8 +387,11 @@ class SpfEngine(NativeHandle):
     _LEVEL = 1
     _destroy = "spf_ctx_destroy"
 
-    def __init__(self, device: int = 0, handle: Optional[C.c_void_p] = None) -> None:
+    def __init__(self, device: int = 0, handle: Optional[C.c_void_p] = None,
+                 n_nodes: int = 0) -> None:
         self._owned = handle is None
+        self.device = device
+        self._n_nodes = n_nodes  # (a wrapped handle's graph was loaded by its owner)
         self._plans: "weakref.WeakSet[NativeHandle]" = weakref.WeakSet()
         if handle is None:
             h = C.c_void_p()
@@ -361,7 +469,7 @@ class SpfEngine(NativeHandle):
 
     @property
     def n_nodes(self) -> int:
-        return len(self._graph[0]) - 1 if self._graph is not None else 0
+        return len(self._graph[0]) - 1 if self._graph is not None else self._n_nodes
 
     def neighbors(self, src: int) -> np.ndarray:
         cnt = C.c_uint32()
@@ -452,6 +560,42 @@ class SpfEngine(NativeHandle):
         self._err(st)
         pool = pool[: used.value]
         return Ksp2Result(srcs, n, pairs, pool)
+
+    def ksp2_routes(self, srcs: Sequence[int], set_ptr, set_nodes, node_label,
+                    set_prepend=None) -> Ksp2Routes:
+        """Every source's KSP2_ED_ECMP next hops towards every destination
+        set, all on the GPU: plan, execute (the path pool grown on overflow, as
+        ksp2() does), then Ksp2Plan.routes.  The paths never leave the device."""
+        from .hiprt import DeviceArray, set_device, synchronize
+
+        set_device(self.device)
+        plan = self.ksp2_plan(srcs)
+        bufs: list = []
+        try:
+            n_pairs = len(plan.srcs) * self.n_nodes
+            d_pairs = DeviceArray(4 * n_pairs, np.uint32)
+            d_cnt = DeviceArray(4, np.uint64)
+            bufs += [d_pairs, d_cnt]
+            words = n_pairs * 12 + (1 << 20)
+            for _ in range(3):
+                d_pool = DeviceArray(words, np.uint32)
+                plan.execute(d_pairs.ptr, d_pool.ptr, words, d_cnt.ptr)
+                synchronize()
+                cnt = d_cnt.numpy()
+                if not int(cnt[2]) & 1:
+                    break
+                d_pool.free()
+                words = int(cnt[0]) + int(cnt[0]) // 4  # the counter says how much it wanted
+            else:
+                raise N.SpfError(N.SPF_E_NOMEM, "KSP2 path pool overflow")
+            bufs.append(d_pool)
+            totals = plan.routes(d_pairs.ptr, d_pool.ptr, set_ptr, set_nodes, node_label, set_prepend)
+        except BaseException:
+            plan.close()
+            for b in bufs:
+                b.free()
+            raise
+        return Ksp2Routes(plan, bufs, totals)
 
     def whatif_plan(self, src: int, links: Optional[Sequence[int]] = None) -> WhatIfPlan:
         return self._track(WhatIfPlan(self, src, links))

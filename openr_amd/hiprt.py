@@ -45,6 +45,17 @@ def device_reset() -> None:
     _check(_lib.hipDeviceReset(), "hipDeviceReset")
 
 
+def read_device(ptr: int, n: int, dtype) -> np.ndarray:
+    """`n` elements of `dtype` at device address `ptr`, copied to the host
+    (hipMemcpy: waits for the null stream only -- synchronize() first when
+    another stream wrote them)."""
+    out = np.empty(int(n), np.dtype(dtype))
+    if n:
+        _check(_lib.hipMemcpy(out.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), out.nbytes, _D2H),
+               "hipMemcpy D2H")
+    return out
+
+
 class DeviceArray:
     """A device allocation of `n` elements of `dtype` (no torch)."""
 

@@ -257,6 +257,8 @@ class LinkState(N.NativeHandle):
         self._adopt(h)
         self._area = area
         self._n_members = len(devices) if devices else 1
+        self._device = int(devices[0]) if devices else int(device)
+        self._k2r = None  # allSourcesKsp2Routes' result
         self._names: List[Optional[str]] = []
         self._gen = 0
         self._spf_cache: Dict[Tuple[str, bool], SpfResult] = {}
@@ -802,9 +804,77 @@ class LinkState(N.NativeHandle):
             mpls.append(RibMplsEntry(label, hops(rec, lambda e: php if int(col[e]) == o else swap)))
         return unicast, list(dele), mpls, list(ldel)
 
+    def allSourcesKsp2Routes(self, set_ptr, set_nodes, prepend=None, mes=None):
+        """Every node's (or the csr ids in `mes`) KSP2_ED_ECMP next hops
+        towards every destination set ``set_nodes[set_ptr[p]:set_ptr[p + 1]]``
+        (csr ids: a prefix's best advertisers of this area) --
+        selectBestPathsKsp2, Decision.cpp:895-1018 -- on the GPU: one batched
+        KSP2 pass, then spf_ksp2_routes over its device-resident paths.  The
+        node labels come from getAdjacencyDatabaseLabels(); `prepend` is
+        parallel to set_nodes (the entries' prependLabel, None or -1: none).
+        addBestPaths (min-nexthop, static next hops of a self-advertised
+        prefix) stays with the caller.  Returns (next hops, label words, pool
+        bytes, kernel ms); allSourcesKsp2NextHops reads the routes."""
+        import numpy as np
+
+        from .engine import SpfEngine
+
+        names, _, _, _, lid, _ = self.flatten()  # (loads the graph into the engine)
+        h = self.engine_handle()
+        if not h.value:
+            raise RuntimeError("allSourcesKsp2Routes: LinkState created host-only (device < 0)")
+        n = len(names)
+        adv = self.getAdjacencyDatabaseLabels()
+        node_label = np.array([adv.get(s, 0) for s in names] or [0], np.int32)
+        pre = None if prepend is None else np.array(
+            [-1 if v is None else int(v) for v in prepend], np.int32)
+        mes = np.arange(n, dtype=np.uint32) if mes is None else np.ascontiguousarray(mes, np.uint32)
+        self._close_ksp2_routes()
+        eng = SpfEngine(device=self._device, handle=h, n_nodes=n)
+        r = eng.ksp2_routes(mes, set_ptr, set_nodes, node_label, pre)
+        self._k2r = (r, [int(v) for v in mes], names, lid, self._gen)
+        return r.hops, r.label_words, r.pool_bytes, r.kernel_ms
+
+    def allSourcesKsp2RouteDb(self, t: int):
+        """Node mes[t]'s share of the last allSourcesKsp2Routes (rptr u64
+        [sets + 1], rec u64 = CSR edge | cost << 32, lptr u64 [len(rec) + 1],
+        lab i32): set p's next hops are rec[rptr[p]:rptr[p + 1]], next hop h's
+        label stack is lab[lptr[h]:lptr[h + 1]]."""
+        if self._k2r is None or self._k2r[4] != self._gen:
+            raise RuntimeError("allSourcesKsp2RouteDb: no routes (call allSourcesKsp2Routes)")
+        return self._k2r[0].db(int(t))
+
+    def allSourcesKsp2NextHops(self, t: int, p: int, isV4: bool = False):
+        """The set of NextHopThrift of route (mes[t], set p) of the last
+        allSourcesKsp2Routes: one per record over its first link as seen from
+        the node, PUSH of the label stack unless it is empty -- what
+        ``SpfSolver._ksp2NextHops`` returns for the same node, advertisers and
+        prefix entries."""
+        from .spf_solver import MplsAction, createNextHop
+
+        if self._k2r is None or self._k2r[4] != self._gen:
+            raise RuntimeError("allSourcesKsp2NextHops: no routes (call allSourcesKsp2Routes)")
+        r, mes, names, lid, _ = self._k2r
+        me = names[mes[int(t)]]
+        nhs = set()
+        for e, cost, labels in r.nexthops(int(t), int(p)):
+            link = self._link(int(lid[e]))
+            addr = link.getNhV4FromNode(me) if isV4 else link.getNhV6FromNode(me)
+            action = MplsAction("PUSH", None, tuple(labels)) if labels else None
+            nhs.add(createNextHop(addr, link.getIfaceFromNode(me), cost, action, link.getArea(),
+                                  link.getOtherNodeName(me)))
+        return nhs
+
+    def _close_ksp2_routes(self) -> None:
+        k2r = getattr(self, "_k2r", None)
+        if k2r is not None:
+            k2r[0].close()
+        self._k2r = None
+
     def close(self) -> None:
         for s in list(getattr(self, "_snaps", ())):
             s.close()
+        self._close_ksp2_routes()
         super().close()
 
     def allSourcesMplsRoutes(self, t: int):
