@@ -145,6 +145,21 @@ int spf_graph_needs_dist64(const spf_ctx* ctx);
 spf_status spf_src_neighbors(const spf_ctx* ctx, uint32_t src, uint32_t* out,
                              uint32_t cap, uint32_t* count);
 
+/* False-twin classes (host only): nodes whose distinct-neighbour lists
+ * (nb_id[nb_ptr[v] .. nb_ptr[v+1]), ascending ids, as spf_src_neighbors gives
+ * them) are equal share a class; classes are numbered by their first member.
+ * cls = [n_nodes]; *n_classes = their number.  The unit-metric BFS sweeps the
+ * quotient graph of these classes when that removes at least half of its
+ * columns (a fabric pod's rack switches and a plane's spines are one class
+ * each).  No reference counterpart. */
+spf_status spf_twin_classes(uint32_t n_nodes, const uint32_t* nb_ptr, const uint32_t* nb_id,
+                            uint32_t* cls, uint32_t* n_classes);
+/* The loaded graph's quotient: its classes, its directed quotient edges, and
+ * *in_use = 1 when msbfs_kernel plans sweep it (0: the plain sweep -- too few
+ * twins, tables too large for LDS, another BFS kernel, or SPF_QUOTIENT=0 in
+ * the environment).  Any output may be NULL.  Engine introspection. */
+spf_status spf_graph_quotient(spf_ctx* ctx, uint32_t* n_classes, uint64_t* n_edges, uint32_t* in_use);
+
 /* ---- plans: a fixed batch of sources, executable many times ------------- */
 /* Next-hop layout of source i of the plan: one destination bitmap per
  * distinct up neighbour (k_i bitmaps, neighbours in ascending id), each of

@@ -195,6 +195,8 @@ PROTOTYPES = {
     "spf_row_pitch": (C.c_uint32, [_vp]),
     "spf_graph_has_nonpositive_metric": (C.c_int, [_vp]),
     "spf_src_neighbors": (C.c_int, [_vp, C.c_uint32, _u32p, C.c_uint32, _u32p]),
+    "spf_twin_classes": (C.c_int, [C.c_uint32, _u32p, _u32p, _u32p, _u32p]),
+    "spf_graph_quotient": (C.c_int, [_vp, _u32p, _u64p, _u32p]),
     "spf_plan_create": (C.c_int, [_vp, _u32p, C.c_uint32, C.c_uint32, C.POINTER(_vp)]),
     "spf_plan_destroy": (None, [_vp]),
     "spf_plan_nh_words": (C.c_uint64, [_vp]),

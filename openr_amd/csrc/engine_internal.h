@@ -173,6 +173,15 @@ struct spf_ctx {
   } tm_tab;
   spfi::DevBuf<uint32_t> d_sell_ptr, d_sell_col;
   spfi::DevBuf<uint32_t> d_ms_smap;  // msbfs_kernel: slice of (wave, slot), balanced by width
+  // msbfs_kernel's twin-class quotient (spfi::quotient_prepare: built at the
+  // first BFS launch after a load or a row patch that changed a neighbour set)
+  struct Quotient {
+    bool stale = true;
+    uint32_t n_cls = 0, n_vrow = 0;  // classes; quotient rows in chunks of kQChunk columns
+    uint64_t n_edge = 0;             // directed quotient edges
+    std::vector<uint16_t> cls, tab;  // class of node; [n_vrow'] rows + [kQChunk][n_vrow'] columns
+  } qt;
+  spfi::DevBuf<uint16_t> d_qcls, d_qtab;
   std::vector<uint32_t> sell4_ptr, sell4;  // packed u16x4 columns (uint2 entries), planes BFS
   spfi::DevBuf<uint32_t> d_sell4_ptr, d_sell4;
   spfi::DevBuf<uint32_t> d_row_ptr, d_col, d_wt, d_rev, d_nb_ptr, d_nb_id, d_nb_w;

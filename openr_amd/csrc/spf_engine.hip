@@ -279,7 +279,24 @@ inline uint32_t ms_own(uint32_t N) {
 //   Links are up in both directions or neither, so CSR out-neighbours are
 //   the in-neighbours the pull reads.  (Pushing later levels, whose
 //   frontiers live in the owners' registers, spilled msbfs_kernel<10>.)
-template <int OWN, bool LCOL, bool DB = false>
+//   Q: the sweep runs on the quotient graph of false-twin classes (nodes with
+//   the same neighbour set; a fabric pod's rack switches, a plane's spines).
+//   Twins receive the same OR at every level, and a node adjacent to one
+//   member of a class is adjacent to all of them (links are up in both
+//   directions or neither), so the frontier is kept per class, CF[class] =
+//   OR of its members' new masks (a drained member's masked to its own
+//   source bit first), and a level is
+//     1. per quotient row, QA[class] = OR of CF over its neighbour classes
+//        (rows cut into chunks of kQChunk columns, one chunk per thread, the
+//        chunks of a wide row joined by an LDS atomic OR);
+//     2. per owned node, new = QA[class of node] & ~visited, the row stores
+//        as in the plain sweep, and new ORed into the next CF[class].
+//   Classes, rows and columns are u16 tables staged in LDS once; a level
+//   issues no global load.  Level 1 is the same sweep from the sources' bits
+//   in their class slots.  CF and QA are double-buffered: two barriers a level.
+constexpr uint32_t kQChunk = 8;
+constexpr int kQMaxOwn = 12;  // (the 16-slot instance spills its owned nodes' state: N <= 12288)
+template <int OWN, bool LCOL, bool DB = false, bool Q = false>
 __global__ __launch_bounds__(kMsThreads) void msbfs_kernel(
     const uint32_t* __restrict__ sell_ptr, const uint32_t* __restrict__ sell_col,
     uint32_t n_col, const uint32_t* __restrict__ row_ptr, const uint32_t* __restrict__ col,
@@ -287,17 +304,30 @@ __global__ __launch_bounds__(kMsThreads) void msbfs_kernel(
     uint32_t n_rows, uint32_t bs, uint32_t N, uint32_t pitch, uint32_t npitch,
     uint32_t* __restrict__ D, uint8_t* __restrict__ Dn, uint32_t* __restrict__ maxd,
     uint32_t d_from, const uint32_t* __restrict__ smap,
-    unsigned long long* __restrict__ stamps /* diagnostics, usually null */) {
+    unsigned long long* __restrict__ stamps /* diagnostics, usually null */,
+    const uint16_t* __restrict__ q_cls, const uint16_t* __restrict__ q_tab, uint32_t q_nc,
+    uint32_t q_nv /* Q: class of node, row/column tables, classes, row chunks */) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint64_t* F = reinterpret_cast<uint64_t*>(smem);             // [N + 1]
   uint64_t* F2 = F + (DB ? N + 1 : 0);                         // [N + 1] (DB) second frontier
-  uint32_t* o_node = reinterpret_cast<uint32_t*>(F2 + N + 1);  // [64] drained batch sources
+  // Q: class frontiers CF[2][q_nc + 1] and row results QA[2][q_nc + 1] (slot
+  // q_nc of each stays 0: the padding column, the class of nodes past N),
+  // the chunk -> row table and the chunk-major columns, the small arrays, and
+  // self[N]: 1 + batch index of the nodes that are sources
+  const uint32_t q_nvp = (q_nv + 7u) & ~7u;
+  uint64_t* const CF = reinterpret_cast<uint64_t*>(smem);
+  uint64_t* const QA = CF + 2 * (q_nc + 1);
+  uint16_t* const vrow = reinterpret_cast<uint16_t*>(QA + 2 * (q_nc + 1));  // [q_nvp]
+  uint16_t* const vcol = vrow + q_nvp;                                       // [kQChunk][q_nvp]
+  uint32_t* o_node = Q ? reinterpret_cast<uint32_t*>(vcol + kQChunk * q_nvp)
+                       : reinterpret_cast<uint32_t*>(F2 + N + 1);  // [64] drained batch sources
   uint32_t* o_cnt = o_node + kMsBatch;                         // [1]
   uint32_t* flag = o_cnt + 1;                                  // [3] progress flags
   uint32_t* src_l = flag + 3;                                  // [64] the batch's sources
   uint32_t* e_base = src_l + kMsBatch;                         // [64] their first CSR edge
   uint32_t* e_pre = e_base + kMsBatch;                         // [65] degree prefix sums
   uint16_t* lcol = reinterpret_cast<uint16_t*>(e_pre + kMsBatch + 1);  // [n_col] (LCOL)
+  uint8_t* const self = reinterpret_cast<uint8_t*>(e_pre + kMsBatch + 1);  // [N] (Q)
 
   const uint32_t tid = threadIdx.x, lane = tid & 63;
   const uint32_t row0 = blockIdx.x * bs;  // bs <= 64 sources per workgroup
@@ -318,7 +348,15 @@ __global__ __launch_bounds__(kMsThreads) void msbfs_kernel(
   } while (0)
   MS_STAMP();
 
+  if constexpr (Q) {
+    for (uint32_t t = tid; t < 4 * (q_nc + 1); t += kMsThreads) CF[t] = 0;  // CF and QA
+    const uint4* tab4 = reinterpret_cast<const uint4*>(q_tab);
+    for (uint32_t t = tid; t < (1 + kQChunk) * q_nvp / 8; t += kMsThreads)
+      reinterpret_cast<uint4*>(vrow)[t] = tab4[t];
+    for (uint32_t t = tid; t < (N + 3) / 4; t += kMsThreads) reinterpret_cast<uint32_t*>(self)[t] = 0;
+  } else {
   for (uint32_t v = tid; v <= N; v += kMsThreads) F[v] = 0;
+  }
   if (LCOL)
     for (uint32_t t = tid; t < n_col; t += kMsThreads) lcol[t] = (uint16_t)sell_col[t];
   if (DB)
@@ -331,7 +369,17 @@ __global__ __launch_bounds__(kMsThreads) void msbfs_kernel(
   // ---- the batch's sources (wave 0): level 0, drained sources, their CSR
   // rows as one flat edge list (exclusive scan of the degrees), and their own
   // bits marked in F for the owners to pick up ----
-  if (tid < 64) {
+  if constexpr (Q) {
+    if (tid < nb) {
+      const uint32_t src = rows_src[row0 + tid];  // sources of a batch are distinct
+      if (ovl[src]) o_node[atomicAdd(o_cnt, 1u)] = src | (tid << 24);
+      if (D && d_from == 0) D[(size_t)(row0 + tid) * pitch + src] = 0;  // level 0
+      if (Dn) Dn[(size_t)(row0 + tid) * npitch + src] = 0;
+      self[src] = (uint8_t)(tid + 1);
+      // level 0's frontier: a source expands even when drained
+      atomicOr(reinterpret_cast<unsigned long long*>(&CF[q_cls[src]]), 1ull << tid);
+    }
+  } else if (tid < 64) {
     uint32_t deg = 0;
     if (tid < nb) {
       const uint32_t src = rows_src[row0 + tid];  // sources of a batch are distinct
@@ -365,13 +413,22 @@ __global__ __launch_bounds__(kMsThreads) void msbfs_kernel(
   uint32_t sv[OWN];  // first node of owned slice i (wave-uniform)
   uint64_t vis[OWN], nv[OWN];
   uint32_t drained = 0;  // bit i: owned node i is drained
+  uint32_t cl[Q ? OWN : 1];  // (Q) class of owned node i
 #pragma unroll
   for (int i = 0; i < OWN; ++i) {
     sv[i] = __builtin_amdgcn_readfirstlane(smap[wv * OWN + i]) * kSliceW;
     const uint32_t v = sv[i] + lane;
+    if constexpr (Q) {
+      const uint32_t me = v < N ? self[v] : 0u;
+      vis[i] = me ? 1ull << (me - 1) : 0ull;
+      cl[i] = v < N ? q_cls[v] : q_nc;
+    } else {
     vis[i] = v < N ? F[v] : 0ull;  // the node's own source bit, if it is a source
+    }
     if (v < N && ovl[v]) drained |= 1u << i;
   }
+  bool level1 = false;
+  if constexpr (!Q) {
   __syncthreads();  // the self marks are read
   if (tid < nb) F[src_l[tid]] = 0;
   __syncthreads();
@@ -408,7 +465,8 @@ __global__ __launch_bounds__(kMsThreads) void msbfs_kernel(
   }
   if (any1) flag[0] = 1;  // level 1 is not empty (flag[1] stays 0 for level 1's sweep)
   __syncthreads();
-  const bool level1 = flag[0] != 0;  // read before level 1 resets flag[0]
+  level1 = flag[0] != 0;  // read before level 1 resets flag[0]
+  }
 
   MS_STAMP();
   // ---- record a level: D[s][v] = L for every new (s, v) of owned slice i
@@ -422,7 +480,10 @@ __global__ __launch_bounds__(kMsThreads) void msbfs_kernel(
     const uint64_t wm = wave_or64(x);
     uint32_t mlo = __builtin_amdgcn_readfirstlane((uint32_t)wm);
     uint32_t mhi = __builtin_amdgcn_readfirstlane((uint32_t)(wm >> 32));
-    const uint32_t v = sv[i] + lane;
+    uint32_t v = sv[i] + lane;
+    // (Q: formed per call -- ten slots' row addresses hoisted out of the level
+    // loop spilled VGPRs)
+    if constexpr (Q) asm volatile("" : "+v"(v));
     // Two ways to cover the (source, node) pairs of the slice: one
     // coalesced store per source (row-major; best when a source discovers
     // many nodes of the slice at once -- dense fabrics), or each lane
@@ -536,7 +597,52 @@ __global__ __launch_bounds__(kMsThreads) void msbfs_kernel(
     return nx;
   };
   uint32_t last = 0;  // deepest level of the batch
-  if constexpr (DB) {
+  if constexpr (Q) {
+    // flag[L mod 3] as in the double-buffered loop below.  Buffer L & 1 of CF
+    // holds level L's frontier and of QA its rows' results; the other two are
+    // cleared during the row phase (their last readers passed a barrier).
+    for (uint32_t L = 0;; ++L) {
+      const uint64_t* CFc = CF + (L & 1u) * (q_nc + 1);
+      uint64_t* CFn = CF + ((L + 1) & 1u) * (q_nc + 1);
+      uint64_t* QAc = QA + (L & 1u) * (q_nc + 1);
+      uint64_t* QAn = QA + ((L + 1) & 1u) * (q_nc + 1);
+      for (uint32_t r = tid; r < q_nv; r += kMsThreads) {
+        uint32_t k[kQChunk];
+#pragma unroll
+        for (uint32_t j = 0; j < kQChunk; ++j) k[j] = vcol[j * q_nvp + r];
+        uint64_t acc = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < kQChunk; ++j) acc |= CFc[k[j]];
+        if (acc) atomicOr(reinterpret_cast<unsigned long long*>(&QAc[vrow[r]]), acc);
+      }
+      for (uint32_t t = tid; t <= q_nc; t += kMsThreads) {
+        CFn[t] = 0;
+        QAn[t] = 0;
+      }
+      MS_STAMP();
+      __syncthreads();
+      MS_STAMP();
+      uint64_t any = 0;
+#pragma unroll
+      for (int i = 0; i < OWN; ++i) {
+        const uint64_t nx = QAc[cl[i]] & ~vis[i];  // (nodes past N: slot q_nc, 0)
+        vis[i] |= nx;
+        const uint64_t f = ((drained >> i) & 1u) ? own_bits(sv[i] + lane, nx) : nx;
+        if (f) atomicOr(reinterpret_cast<unsigned long long*>(&CFn[cl[i]]), f);
+        any |= nx;
+        record(i, nx, L + 1);
+      }
+      if (any) flag[L % 3] = 1;
+      if (tid == 0) flag[(L + 1) % 3] = 0;
+      MS_STAMP();
+      __syncthreads();
+      MS_STAMP();
+      if (!flag[L % 3]) {
+        last = L;
+        break;
+      }
+    }
+  } else if constexpr (DB) {
     // Double-buffered frontier (graphs whose two F arrays fit in LDS): a
     // slice is pulled from level L's frontier, its level L + 1 bits go
     // straight into the other buffer and its stores are issued at once --
@@ -1633,6 +1739,13 @@ size_t sssp_lds_bytes(uint32_t N, uint32_t pitch, uint32_t big, bool q16) {
   return (b + 15) & ~size_t(15);
 }
 
+// msbfs_kernel's twin-class quotient (defined with its launch below)
+uint32_t twin_classes(uint32_t N, const uint32_t* nb_ptr, const uint32_t* nb_id, uint32_t* cls);
+spf_status quotient_prepare(spf_ctx* c);
+bool use_quotient(const spf_ctx* c);
+bool use_planes(const spf_ctx* c);
+uint32_t ms_batch(const spf_ctx* c, uint32_t rows);
+
 }  // namespace
 
 extern "C" {
@@ -1739,6 +1852,7 @@ spf_status spf_graph_load(spf_ctx* c, const spf_graph* g) {
   c->loaded = false;
   c->N = N;
   c->E = E;
+  c->qt.stale = true;
   // dist rows / bitmap rows: whole 1024-node chunks, so every next-hop
   // bitmap (pitch / 8 bytes) starts on a 128-byte line and no line of the
   // output is written partially by two waves (SPF_PITCH_ALIGN: A/B only)
@@ -2173,10 +2287,12 @@ spf_status spf_graph_patch_rows(spf_ctx* c, const uint32_t* nodes, uint32_t n, c
     c->nb_id.swap(id);
     c->nb_w.swap(w);
     ++c->layout;
+    c->qt.stale = true;  // a neighbour set changed: its twin class may split or merge
   } else {
     for (uint32_t i = 0; i < n; ++i) {
       const uint32_t b = c->nb_ptr[nodes[i]];
       for (size_t k = 0; k < fresh[i].size(); ++k) {
+        if (c->nb_id[b + k] != fresh[i][k].first) c->qt.stale = true;
         c->nb_id[b + k] = fresh[i][k].first;
         c->nb_w[b + k] = fresh[i][k].second;
       }
@@ -2290,6 +2406,27 @@ spf_status spf_graph_patch_rows(spf_ctx* c, const uint32_t* nodes, uint32_t n, c
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   stage_done(c);
   ++c->epoch;
+  return SPF_OK;
+}
+
+spf_status spf_twin_classes(uint32_t n_nodes, const uint32_t* nb_ptr, const uint32_t* nb_id,
+                            uint32_t* cls, uint32_t* n_classes) {
+  if (!nb_ptr || !cls || !n_classes || (n_nodes && nb_ptr[n_nodes] && !nb_id))
+    return fail(nullptr, SPF_E_INVALID, "spf_twin_classes: NULL argument");
+  for (uint32_t v = 0; v < n_nodes; ++v)
+    if (nb_ptr[v] > nb_ptr[v + 1]) return fail(nullptr, SPF_E_INVALID, "nb_ptr not monotone at %u", v);
+  *n_classes = twin_classes(n_nodes, nb_ptr, nb_id, cls);
+  return SPF_OK;
+}
+
+spf_status spf_graph_quotient(spf_ctx* c, uint32_t* n_classes, uint64_t* n_edges, uint32_t* in_use) {
+  if (!c) return fail(c, SPF_E_INVALID, "spf_graph_quotient: NULL context");
+  if (!c->loaded) return fail(c, SPF_E_STATE, "no graph loaded");
+  const spf_status st = quotient_prepare(c);
+  if (st != SPF_OK) return st;
+  if (n_classes) *n_classes = c->qt.n_cls;
+  if (n_edges) *n_edges = c->qt.n_edge;
+  if (in_use) *in_use = (c->N <= kMsMaxNodes && !use_planes(c) && use_quotient(c)) ? 1u : 0u;
   return SPF_OK;
 }
 
@@ -2951,8 +3088,10 @@ spf_status spf_plan_traffic_phases(const spf_plan* p, uint64_t* bytes) {
     const uint64_t bs = std::min<uint64_t>(batch, (rows + rounds * c->n_cu - 1) / (rounds * c->n_cu));
     const uint64_t groups = (rows + bs - 1) / bs;
     const uint64_t n_slices = c->sell_ptr.size() - 1;
+    // (quotient sweep: the class and row/column tables instead of the columns)
     const uint64_t csr = planes ? 8ull * c->sell4_ptr.back() + 4ull * (n_slices + 1)
-                                : 4ull * c->sell_ptr.back() + 4ull * (n_slices + 1);
+                         : use_quotient(c) ? 2ull * (c->qt.cls.size() + c->qt.tab.size())
+                                           : 4ull * c->sell_ptr.back() + 4ull * (n_slices + 1);
     // expand plans: the u32 rows are written by the slicing pass instead
     bfs = groups * (csr + N) + (p->expand ? 0ull : rows * c->pitch * 4ull) +
           (p->narrow ? rows * c->npitch : 0ull);
@@ -3063,6 +3202,127 @@ bool ms_double_buffer(const spf_ctx* c) {
   return msbfs_lds_bytes(c->N) + 2ull * n_col > kMaxLds && msbfs_lds_bytes(c->N, true) <= kMaxLds;
 }
 
+// False-twin classes: nodes whose distinct-neighbour lists (ascending ids)
+// are equal share a class; classes are numbered by their first member.  Lists
+// are hashed, then compared within a hash bucket.
+uint32_t twin_classes(uint32_t N, const uint32_t* nb_ptr, const uint32_t* nb_id, uint32_t* cls) {
+  std::vector<uint64_t> h(N);
+  for (uint32_t v = 0; v < N; ++v) {
+    uint64_t x = 0x9E3779B97F4A7C15ull ^ (nb_ptr[v + 1] - nb_ptr[v]);
+    for (uint32_t e = nb_ptr[v]; e < nb_ptr[v + 1]; ++e) {
+      x ^= nb_id[e] + 0x9E3779B97F4A7C15ull + (x << 6) + (x >> 2);
+      x *= 0xFF51AFD7ED558CCDull;
+    }
+    h[v] = x;
+  }
+  std::vector<uint32_t> order(N), rep(N);
+  std::iota(order.begin(), order.end(), 0u);
+  std::sort(order.begin(), order.end(),
+            [&](uint32_t a, uint32_t b) { return h[a] != h[b] ? h[a] < h[b] : a < b; });
+  auto same = [&](uint32_t a, uint32_t b) {
+    const uint32_t k = nb_ptr[a + 1] - nb_ptr[a];
+    return k == nb_ptr[b + 1] - nb_ptr[b] &&
+           std::equal(nb_id + nb_ptr[a], nb_id + nb_ptr[a] + k, nb_id + nb_ptr[b]);
+  };
+  std::vector<uint32_t> reps;  // first members of the classes in one hash bucket
+  for (size_t i = 0; i < N;) {
+    size_t j = i;
+    reps.clear();
+    for (; j < N && h[order[j]] == h[order[i]]; ++j) {
+      const uint32_t v = order[j];
+      rep[v] = v;
+      for (uint32_t r : reps)
+        if (same(r, v)) {
+          rep[v] = r;
+          break;
+        }
+      if (rep[v] == v) reps.push_back(v);
+    }
+    i = j;
+  }
+  uint32_t n_cls = 0;
+  for (uint32_t v = 0; v < N; ++v) cls[v] = rep[v] == v ? n_cls++ : cls[rep[v]];  // rep[v] <= v
+  return n_cls;
+}
+
+// LDS of msbfs_kernel's quotient variant: CF and QA (two buffers each), the
+// row/column tables, the small arrays, the source marks
+size_t msbfs_q_lds_bytes(uint32_t N, uint32_t n_cls, uint32_t n_vrow) {
+  const size_t nvp = (n_vrow + 7u) & ~7u;
+  return 32ull * (n_cls + 1) + 2ull * (1 + kQChunk) * nvp + 4ull * (4 * kMsBatch + 5) + ((N + 3u) & ~3u);
+}
+
+// The quotient tables of the loaded graph, rebuilt when stale.  A node's
+// neighbours are whole classes (links are up in both directions or neither),
+// so the quotient row of a class is the set of classes of its first member's
+// neighbours; rows are cut into chunks of kQChunk columns padded with n_cls.
+spf_status quotient_prepare(spf_ctx* c) {
+  spf_ctx::Quotient& q = c->qt;
+  if (!q.stale) return SPF_OK;
+  const uint32_t N = c->N;
+  q.n_cls = q.n_vrow = 0;
+  q.n_edge = 0;
+  q.stale = false;
+  if (N > kMsMaxNodes) return SPF_OK;  // (msbfs_kernel does not run on such graphs)
+  std::vector<uint32_t> cls(N);
+  q.n_cls = twin_classes(N, c->nb_ptr.data(), c->nb_id.data(), cls.data());
+  q.cls.assign(cls.begin(), cls.end());
+  std::vector<uint32_t> row_of, cols, qn;  // per chunk: its row; kQChunk columns
+  std::vector<uint8_t> seen(N, 0);         // (first members only)
+  for (uint32_t v = 0; v < N; ++v) {
+    if (seen[cls[v]]) continue;
+    seen[cls[v]] = 1;
+    qn.clear();
+    for (uint32_t e = c->nb_ptr[v]; e < c->nb_ptr[v + 1]; ++e) qn.push_back(cls[c->nb_id[e]]);
+    std::sort(qn.begin(), qn.end());
+    qn.erase(std::unique(qn.begin(), qn.end()), qn.end());
+    q.n_edge += qn.size();
+    for (size_t b = 0; b < qn.size(); b += kQChunk) {
+      row_of.push_back(cls[v]);
+      for (size_t j = 0; j < kQChunk; ++j) cols.push_back(b + j < qn.size() ? qn[b + j] : q.n_cls);
+    }
+  }
+  q.n_vrow = (uint32_t)row_of.size();
+  const size_t nvp = (q.n_vrow + 7u) & ~7u;
+  q.tab.assign((1 + kQChunk) * nvp, (uint16_t)q.n_cls);
+  for (uint32_t r = 0; r < q.n_vrow; ++r) {
+    q.tab[r] = (uint16_t)row_of[r];
+    for (uint32_t j = 0; j < kQChunk; ++j) q.tab[nvp + j * nvp + r] = (uint16_t)cols[(size_t)r * kQChunk + j];
+  }
+  for (size_t r = q.n_vrow; r < nvp; ++r) q.tab[r] = 0;  // (chunks past n_vrow are not read)
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipDeviceSynchronize());  // no launch still reads the old tables
+  HIP_TRY(c, c->d_qcls.upload(q.cls.data(), q.cls.size(), c->stream));
+  HIP_TRY(c, c->d_qtab.upload(q.tab.data(), q.tab.size(), c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return SPF_OK;
+}
+
+// The quotient sweep is taken when it reads at most half the columns of the
+// plain one (a grid or a ring has no twins: every node its own class) and its
+// tables fit in LDS.  SPF_QUOTIENT=0 keeps the plain sweep (A/B, parity tests).
+bool quotient_allowed(const spf_ctx* c) {
+  if (c->N > kMsMaxNodes || ms_own(c->N) > (uint32_t)kQMaxOwn) return false;
+  const char* e = std::getenv("SPF_QUOTIENT");
+  return !(e && e[0] == '0');
+}
+bool use_quotient(const spf_ctx* c) {
+  const spf_ctx::Quotient& q = c->qt;
+  if (!quotient_allowed(c) || q.stale || q.n_cls == 0 || 2 * q.n_edge > c->nb_id.size()) return false;
+  return msbfs_q_lds_bytes(c->N, q.n_cls, q.n_vrow) <= kMaxLds;
+}
+
+// msbfs_kernel's sources per workgroup.  SPF_MSBFS_BATCH=1..64 fixes it
+// (tests: full batches on graphs too small to fill the chip with them).
+uint32_t ms_batch(const spf_ctx* c, uint32_t rows) {
+  if (const char* e = std::getenv("SPF_MSBFS_BATCH")) {
+    const int b = atoi(e);
+    if (b >= 1 && b <= (int)kMsBatch) return (uint32_t)b;
+  }
+  const uint32_t rounds = (rows + kMsBatch * c->n_cu - 1) / (kMsBatch * c->n_cu);
+  return std::min<uint32_t>(kMsBatch, (rows + rounds * c->n_cu - 1) / (rounds * c->n_cu));
+}
+
 template <int OWN>
 void msbfs_launch(spf_ctx* c, const uint32_t* rows_src, uint32_t rows, uint32_t* D, uint8_t* Dn,
                   uint32_t* maxd, uint32_t d_from, hipStream_t s) {
@@ -3072,23 +3332,34 @@ void msbfs_launch(spf_ctx* c, const uint32_t* rows_src, uint32_t rows, uint32_t*
   // one workgroup per CU per round: a batch costs one edge sweep per level
   // whatever its size, but its stores scale with it, so spread the sources
   // over every CU rather than fill 64-source batches on fewer CUs
-  const uint32_t rounds = (rows + kMsBatch * c->n_cu - 1) / (kMsBatch * c->n_cu);
-  const uint32_t bs = std::min<uint32_t>(kMsBatch, (rows + rounds * c->n_cu - 1) / (rounds * c->n_cu));
+  const uint32_t bs = ms_batch(c, rows);
+  const uint16_t* const no_q = nullptr;
+  if constexpr (OWN <= kQMaxOwn) {
+    if (use_quotient(c)) {
+      hipLaunchKernelGGL((msbfs_kernel<OWN, false, false, true>), dim3((rows + bs - 1) / bs),
+                       dim3(kMsThreads), msbfs_q_lds_bytes(c->N, c->qt.n_cls, c->qt.n_vrow), s,
+                       c->d_sell_ptr.p, c->d_sell_col.p, n_col, c->d_row_ptr.p, c->d_col.p, c->d_ovl.p,
+                       rows_src, rows, bs, c->N, c->pitch, c->npitch, D, Dn, maxd, d_from,
+                       c->d_ms_smap.p, c->d_stamps.p, c->d_qcls.p, c->d_qtab.p, c->qt.n_cls,
+                       c->qt.n_vrow);
+      return;
+    }
+  }
   if (lcol)
     hipLaunchKernelGGL((msbfs_kernel<OWN, true>), dim3((rows + bs - 1) / bs), dim3(kMsThreads),
                        lds_col, s, c->d_sell_ptr.p, c->d_sell_col.p, n_col, c->d_row_ptr.p, c->d_col.p,
                        c->d_ovl.p, rows_src, rows, bs, c->N, c->pitch, c->npitch, D, Dn,
-                       maxd, d_from, c->d_ms_smap.p, c->d_stamps.p);
+                       maxd, d_from, c->d_ms_smap.p, c->d_stamps.p, no_q, no_q, 0u, 0u);
   else if (ms_double_buffer(c))
     hipLaunchKernelGGL((msbfs_kernel<OWN, false, true>), dim3((rows + bs - 1) / bs), dim3(kMsThreads),
                        msbfs_lds_bytes(c->N, true), s, c->d_sell_ptr.p, c->d_sell_col.p, n_col,
                        c->d_row_ptr.p, c->d_col.p, c->d_ovl.p, rows_src, rows, bs, c->N, c->pitch,
-                       c->npitch, D, Dn, maxd, d_from, c->d_ms_smap.p, c->d_stamps.p);
+                       c->npitch, D, Dn, maxd, d_from, c->d_ms_smap.p, c->d_stamps.p, no_q, no_q, 0u, 0u);
   else
     hipLaunchKernelGGL((msbfs_kernel<OWN, false>), dim3((rows + bs - 1) / bs), dim3(kMsThreads),
                        lds, s, c->d_sell_ptr.p, c->d_sell_col.p, n_col, c->d_row_ptr.p, c->d_col.p,
                        c->d_ovl.p, rows_src, rows, bs, c->N, c->pitch, c->npitch, D, Dn,
-                       maxd, d_from, c->d_ms_smap.p, c->d_stamps.p);
+                       maxd, d_from, c->d_ms_smap.p, c->d_stamps.p, no_q, no_q, 0u, 0u);
 }
 
 size_t planes_lds_bytes(uint32_t own) { return 8ull * own * kMsThreads + 4ull * (kPlBatch + 4); }
@@ -3148,6 +3419,10 @@ spf_status launch_msbfs(spf_ctx* c, const uint32_t* rows_src, uint32_t rows, uin
     else planes_launch<10>(c, rows_src, rows, D, Dn, order, s);
     HIP_TRY(c, hipGetLastError());
     return SPF_OK;
+  }
+  if (quotient_allowed(c)) {  // (else the tables stay stale: nothing is built for a path not taken)
+    const spf_status st = quotient_prepare(c);
+    if (st != SPF_OK) return st;
   }
   if (own == 1) msbfs_launch<1>(c, rows_src, rows, D, Dn, maxd, d_from, s);
   else if (own == 2) msbfs_launch<2>(c, rows_src, rows, D, Dn, maxd, d_from, s);
@@ -3215,10 +3490,13 @@ spf_status set_lds_limits(spf_ctx* c) {
   const void* fns[] = {SSK(uint16_t, true), SSK(uint16_t, false), SSK(uint32_t, true), SSK(uint32_t, false),
 #define MSB(o) (const void*)msbfs_kernel<o, false>, (const void*)msbfs_kernel<o, true>, \
                (const void*)msbfs_kernel<o, false, true>
+#define MSQ(o) (const void*)msbfs_kernel<o, false, false, true>
                        MSB(1), MSB(2), MSB(4), MSB(8), MSB(10), MSB(12), MSB(16),
+                       MSQ(1), MSQ(2), MSQ(4), MSQ(8), MSQ(10), MSQ(12),
 #define PLB(o) (const void*)msbfs_planes_kernel<o, false>, (const void*)msbfs_planes_kernel<o, true>
                        PLB(1), PLB(2), PLB(4), PLB(8), PLB(10)};
 #undef PLB
+#undef MSQ
 #undef MSB
 #undef SSK
   for (const void* f : fns)
