@@ -1,7 +1,10 @@
 // ============================================================================
-//  engine_internal.h -- state shared by the engine's translation units
-//  (spf_engine.hip: SPF/ECMP plans; ksp2.hip: batched KSP2; ...).  Not part of the
-//  C-ABI: include/openr_spf.h is the boundary.
+//  engine_internal.h -- state shared by the engine's translation units: the
+//  context (the graph's host state of graph_host.h plus its device copy and
+//  the kernels' scratch), the plans, and the launch functions each unit offers
+//  the others (graph.cpp: the spf_graph_* calls; spf_engine.hip: SPF/ECMP
+//  plans; ksp2.hip: batched KSP2; ...).  Not part of the C-ABI:
+//  include/openr_spf.h is the boundary.
 // ============================================================================
 #pragma once
 #include <hip/hip_runtime.h>
@@ -14,11 +17,11 @@
 #include <string>
 #include <vector>
 
+#include "graph_host.h"
 #include "openr_spf.h"
 
 namespace spfi {
 
-constexpr uint32_t kInf = SPF_UNREACHABLE;
 // diagnostics buffer (SPF_STAMPS): 16 waves x 64 phase stamps of one block,
 // the block selector, then a start / end s_memrealtime pair per block
 constexpr uint32_t kStampBlocks = 1024;
@@ -122,7 +125,9 @@ struct ExactKsp2 {
 
 }  // namespace spfi
 
-struct spf_ctx {
+// The graph itself (CSR, derived tables, versions) is the GraphHost base; here
+// are its device copy and everything the kernels keep per context.
+struct spf_ctx : spfi::GraphHost {
   int device = 0;
   uint32_t n_cu = 256;  // compute units (BFS batch sizing)
   hipStream_t stream = nullptr;
@@ -134,34 +139,8 @@ struct spf_ctx {
   bool team_off = false;  // a team barrier timed out: plans keep msbfs_kernel
   std::string err;
   uint64_t solves = 0;
-  uint64_t shape = 0;  // bumped by spf_graph_load (CSR structure)
-  uint64_t epoch = 0;  // bumped by every graph change (load or in-place patch)
-  // bumped when a patch changes some node's distinct-neighbour count (a
-  // plan's next-hop layout); plans of the old layout fail with SPF_E_STATE
-  uint64_t layout = 0;
-  // the two CSR slots of every link id (kInf: none), kept by spf_graph_patch_rows
-  std::vector<uint32_t> link_slot;
-  // graph
-  bool loaded = false;
-  uint32_t N = 0, E = 0, pitch = 0;
-  bool nonpos = false;
-  bool needs64 = false;  // a negative metric or max metric x N >= 2^32 - 1: u64 labels
-  uint32_t max_metric = 0;
-  // live directed edges with metric <= 0, < 0, and weight == max_metric: a
-  // row patch updates the metric facts from these without a graph scan
-  uint64_t n_nonpos = 0, n_neg = 0, n_at_max = 0;
-  std::vector<uint32_t> row_ptr, col, wt, rev, link;
-  std::vector<int32_t> met;  // metrics as advertised (exact kernel)
   spfi::DevBuf<int32_t> d_met;
   spfi::ExactScratch exact1;  // spf_solve_exact (synchronous one-shot solves) only
-  std::vector<uint8_t> ovl;
-  std::vector<uint32_t> nb_ptr, nb_id, nb_w;  // distinct up neighbours
-  uint32_t big_nodes = 0;                    // nodes with degree > kBigDeg
-  uint32_t max_link = 0;
-  bool unit = false;                         // every up edge has metric 1
-  uint32_t npitch = 0;                       // narrow (u8) row pitch
-  std::vector<uint32_t> sell_ptr, sell_col;  // sliced-ELL columns (64-node slices)
-  uint64_t sell_ver = 0;  // bumped whenever sell_ptr / sell_col change (load, row patch)
   // msbfs_team_prepare's graph-derived tables for one team size (slices to
   // members, finalize slots, column streams, frontier slices each member
   // reads): valid while sell_ver holds, shared by every plan of the context
@@ -172,21 +151,11 @@ struct spf_ctx {
     std::vector<uint32_t> fin, mptr, meta, need;
   } tm_tab;
   spfi::DevBuf<uint32_t> d_sell_ptr, d_sell_col;
-  spfi::DevBuf<uint32_t> d_ms_smap;  // msbfs_kernel: slice of (wave, slot), balanced by width
-  // msbfs_kernel's twin-class quotient (spfi::quotient_prepare: built at the
-  // first BFS launch after a load or a row patch that changed a neighbour set)
-  struct Quotient {
-    bool stale = true;
-    uint32_t n_cls = 0, n_vrow = 0;  // classes; quotient rows in chunks of kQChunk columns
-    uint64_t n_edge = 0;             // directed quotient edges
-    std::vector<uint16_t> cls, tab;  // class of node; [n_vrow'] rows + [kQChunk][n_vrow'] columns
-  } qt;
-  spfi::DevBuf<uint16_t> d_qcls, d_qtab;
-  std::vector<uint32_t> sell4_ptr, sell4;  // packed u16x4 columns (uint2 entries), planes BFS
+  spfi::DevBuf<uint32_t> d_ms_smap;
+  spfi::DevBuf<uint16_t> d_qcls, d_qtab;  // qt.cls, qt.tab (spfi::quotient_prepare)
   spfi::DevBuf<uint32_t> d_sell4_ptr, d_sell4;
   spfi::DevBuf<uint32_t> d_row_ptr, d_col, d_wt, d_rev, d_nb_ptr, d_nb_id, d_nb_w;
-  std::vector<uint32_t> edge_nb;     // host copy of d_edge_nb (patched in place)
-  spfi::DevBuf<uint32_t> d_edge_nb;  // per CSR edge: its head's index among the tail's distinct neighbours
+  spfi::DevBuf<uint32_t> d_edge_nb;
   spfi::DevBuf<uint8_t> d_ovl;
   // scratch for spf_preds
   spfi::DevBuf<uint32_t> d_pred_cnt, d_pred_edge, d_link, d_ign, d_one_src, d_row;
@@ -472,6 +441,12 @@ spf_status launch_big(spf_ctx* c, spf_plan* p, uint32_t* d_dist, uint32_t* d_nh,
                       hipStream_t s);
 // Raise the dynamic-LDS limit of the engine's LDS-resident kernels.
 spf_status set_lds_limits(spf_ctx* c);
+// msbfs_kernel's twin-class quotient: its tables rebuilt and uploaded when
+// stale (graph.cpp); whether the BFS sweeps it, and whether the register-plane
+// BFS runs instead (spf_engine.hip, with the kernels)
+spf_status quotient_prepare(spf_ctx* c);
+bool use_quotient(const spf_ctx* c);
+bool use_planes(const spf_ctx* c);
 // Order a launch whose workgroups wait on each other (grid barriers, team
 // BFS) on stream s after the previous such launch of this process on the
 // same device, whatever context or stream that was on: two of them running

@@ -556,6 +556,9 @@ spf_status spf_mctx_graph_patch_rows(spf_mctx* m, const uint32_t* nodes, uint32_
                                      const uint32_t* col, const int32_t* metric, const uint32_t* link) {
   if (!m) return mfail(m, SPF_E_INVALID, "spf_mctx_graph_patch_rows: NULL context");
   if (const spf_status st = drain_exec(m); st != SPF_OK) return st;
+  // every member holds the same graph (spf_mplan_create relies on it) and a
+  // member refuses a patch before it changes anything: what member 0 refuses
+  // has changed no member
   for (uint32_t i = 0; i < m->members.size(); ++i) {
     const spf_status st = spf_graph_patch_rows(m->members[i], nodes, n, col, metric, link);
     if (st != SPF_OK) return member_fail(m, i, st);

@@ -70,7 +70,6 @@ using namespace spfi;
 namespace {
 
 constexpr int kEcmpThreads = 256;
-constexpr uint32_t kBigDeg = 24;  // > kBigDeg: expanded by a whole wave
 constexpr size_t kMaxLds = 160 * 1024;
 
 
@@ -246,22 +245,9 @@ __global__ __launch_bounds__(THREADS) void sssp_kernel(
 //     that have new nodes in the wave; one store covers 64 consecutive nodes
 //     of one source row.  The u8 narrow copy for the next-hop pass saturates at
 //     254.
-constexpr int kMsThreads = 1024;
 constexpr uint32_t kMsBatch = 64;
-constexpr int kMsMaxOwn = 16;
-constexpr uint32_t kMsMaxNodes = kMsThreads * kMsMaxOwn;  // 16384 (F: 128 KiB of LDS)
 constexpr int kMsUnroll = 8;
 constexpr uint32_t kMsLaneStoreRatio = 4;  // per-lane stores when 4 * max per-node count < #sources
-constexpr uint32_t kSliceW = 64;  // nodes per sliced-ELL slice (= wave width)
-constexpr uint32_t kNoSlice = 0x03FFFFFFu;  // unused slot: its nodes (kNoSlice * 64 + lane) lie past N
-
-// owned slots per thread of msbfs_kernel (the template instances: 1, 2, 4, 8,
-// 10, 12, 16) for an N-node graph
-inline uint32_t ms_own(uint32_t N) {
-  const uint32_t own = (N + kMsThreads - 1) / kMsThreads;
-  return own <= 1 ? 1 : own <= 2 ? 2 : own <= 4 ? 4 : own <= 8 ? 8 : own <= 10 ? 10 : own <= 12 ? 12 : 16;
-}
-
 // Narrow (u8) distance rows: npitch bytes (a multiple of 1024), node v at
 // byte v -- a level's stores are 64 consecutive bytes per (source, slice),
 // lane-ordered like the u32 ones (any permutation of the lanes' addresses
@@ -294,7 +280,6 @@ inline uint32_t ms_own(uint32_t N) {
 //   Classes, rows and columns are u16 tables staged in LDS once; a level
 //   issues no global load.  Level 1 is the same sweep from the sources' bits
 //   in their class slots.  CF and QA are double-buffered: two barriers a level.
-constexpr uint32_t kQChunk = 8;
 constexpr int kQMaxOwn = 12;  // (the 16-slot instance spills its owned nodes' state: N <= 12288)
 template <int OWN, bool LCOL, bool DB = false, bool Q = false>
 __global__ __launch_bounds__(kMsThreads) void msbfs_kernel(
@@ -1739,11 +1724,6 @@ size_t sssp_lds_bytes(uint32_t N, uint32_t pitch, uint32_t big, bool q16) {
   return (b + 15) & ~size_t(15);
 }
 
-// msbfs_kernel's twin-class quotient (defined with its launch below)
-uint32_t twin_classes(uint32_t N, const uint32_t* nb_ptr, const uint32_t* nb_id, uint32_t* cls);
-spf_status quotient_prepare(spf_ctx* c);
-bool use_quotient(const spf_ctx* c);
-bool use_planes(const spf_ctx* c);
 uint32_t ms_batch(const spf_ctx* c, uint32_t rows);
 
 }  // namespace
@@ -1809,630 +1789,6 @@ void spf_ctx_destroy(spf_ctx* c) {
   delete c;
 }
 
-// Live-edge metric facts (nonpos, needs64, max_metric, unit) from a scan of
-// the graph, with the counts a row patch keeps them current by
-static void metric_flags(spf_ctx* c) {
-  c->nonpos = c->n_nonpos > 0;
-  // i32 -> u64 wraps (LinkState.h:22); the longest possible path beyond 32
-  // bits takes the exact kernel's u64 labels (SPF_FLAG_DIST64).  The bound is
-  // on max metric x N, not x (N - 1): the u32 kernels form d(u) + w(u, v) for
-  // every edge of a settled u, d(u) <= max metric x (N - 1), before they
-  // compare it, and that sum must neither wrap nor reach kInf (a 50-node
-  // chain at 87,652,393 per link has d = 2^32 - 39 at its far end, and the
-  // relaxation back from there wrapped to a "shorter" distance)
-  c->needs64 = c->n_neg > 0 || (uint64_t)c->max_metric * (uint64_t)c->N >= (uint64_t)kInf;
-  c->unit = !c->nonpos && c->max_metric <= 1;
-}
-static void metric_facts(spf_ctx* c) {
-  c->n_nonpos = c->n_neg = c->n_at_max = 0;
-  c->max_metric = 0;
-  for (uint32_t u = 0; u < c->N; ++u)
-    for (uint32_t e = c->row_ptr[u]; e < c->row_ptr[u + 1]; ++e) {
-      if (c->col[e] == u) continue;  // dead slot
-      c->n_nonpos += c->met[e] <= 0;
-      c->n_neg += c->met[e] < 0;
-      if (c->wt[e] > c->max_metric) {
-        c->max_metric = c->wt[e];
-        c->n_at_max = 1;
-      } else if (c->wt[e] == c->max_metric) {
-        ++c->n_at_max;
-      }
-    }
-  metric_flags(c);
-}
-
-spf_status spf_graph_load(spf_ctx* c, const spf_graph* g) {
-  if (!c || !g) return fail(c, SPF_E_INVALID, "spf_graph_load: NULL argument");
-  const uint32_t N = g->n_nodes, E = g->n_edges;
-  if (N == 0) return fail(c, SPF_E_INVALID, "graph has no nodes");
-  if (!g->row_ptr || (E && (!g->col || !g->metric || !g->link_id)) || !g->overloaded)
-    return fail(c, SPF_E_INVALID, "graph arrays missing");
-  if (g->row_ptr[0] != 0 || g->row_ptr[N] != E)
-    return fail(c, SPF_E_INVALID, "row_ptr must start at 0 and end at n_edges");
-  c->loaded = false;
-  c->N = N;
-  c->E = E;
-  c->qt.stale = true;
-  // dist rows / bitmap rows: whole 1024-node chunks, so every next-hop
-  // bitmap (pitch / 8 bytes) starts on a 128-byte line and no line of the
-  // output is written partially by two waves (SPF_PITCH_ALIGN: A/B only)
-  {
-    const char* e = std::getenv("SPF_PITCH_ALIGN");
-    const uint32_t a = e ? (uint32_t)atoi(e) : 1024u;  // a power of two >= 64
-    c->pitch = (N + a - 1) & ~(a - 1);
-  }
-  c->npitch = (N + 1023) & ~1023u;  // narrow rows: whole 1024-node chunks
-  c->row_ptr.assign(g->row_ptr, g->row_ptr + N + 1);
-  c->col.assign(g->col, g->col + E);
-  c->link.assign(g->link_id, g->link_id + E);
-  c->ovl.assign(g->overloaded, g->overloaded + N);
-  c->wt.resize(E);
-  c->met.assign(g->metric, g->metric + E);
-  c->nonpos = false;
-  c->needs64 = false;
-  c->max_metric = 0;
-  for (uint32_t u = 0; u < N; ++u) {
-    if (c->row_ptr[u] > c->row_ptr[u + 1])
-      return fail(c, SPF_E_INVALID, "row_ptr not monotone at %u", u);
-  }
-  for (uint32_t u = 0; u < N; ++u)
-    for (uint32_t e = c->row_ptr[u]; e < c->row_ptr[u + 1]; ++e) {
-      if (c->col[e] >= N) return fail(c, SPF_E_INVALID, "edge %u head %u out of range", e, c->col[e]);
-      const int32_t m = g->metric[e];
-      c->wt[e] = m > 0 ? (uint32_t)m : 0u;
-      if (c->col[e] == u) {  // a dead slot (see openr_spf.h): no edge
-        if (m != 1) return fail(c, SPF_E_INVALID, "dead slot %u (a self-loop) must carry metric 1", e);
-        continue;
-      }
-      if (m <= 0) c->nonpos = true;
-      if (m < 0) c->needs64 = true;  // i32 -> u64 wraps (LinkState.h:22)
-      c->max_metric = std::max(c->max_metric, c->wt[e]);
-    }
-  metric_facts(c);  // (the same facts, with the counts row patches update)
-  // reverse edge of every directed edge (same link id, swapped ends)
-  c->rev.assign(E, kInf);
-  {
-    std::vector<uint32_t> first(0);
-    uint32_t max_link = 0;
-    for (uint32_t e = 0; e < E; ++e) max_link = std::max(max_link, c->link[e]);
-    std::vector<uint32_t> seen((size_t)max_link + 1, kInf);
-    for (uint32_t u = 0; u < N; ++u)
-      for (uint32_t e = c->row_ptr[u]; e < c->row_ptr[u + 1]; ++e) {
-        uint32_t& s = seen[c->link[e]];
-        if (s == kInf) {
-          s = e;
-        } else {
-          c->rev[e] = s;
-          c->rev[s] = e;
-        }
-      }
-    for (uint32_t e = 0; e < E; ++e)
-      if (c->rev[e] == kInf)
-        return fail(c, SPF_E_INVALID, "edge %u (link %u) has no reverse edge", e, c->link[e]);
-    c->link_slot.assign(2 * ((size_t)max_link + 1), kInf);
-    for (uint32_t e = 0; e < E; ++e) {
-      uint32_t* ls = &c->link_slot[2 * (size_t)c->link[e]];
-      ls[ls[0] == kInf ? 0 : 1] = e;
-    }
-  }
-  // distinct up neighbours per node, ascending id, min metric
-  c->nb_ptr.assign(N + 1, 0);
-  c->nb_id.clear();
-  c->nb_w.clear();
-  c->big_nodes = 0;
-  std::vector<std::pair<uint32_t, uint32_t>> tmp;
-  for (uint32_t u = 0; u < N; ++u) {
-    tmp.clear();
-    for (uint32_t e = c->row_ptr[u]; e < c->row_ptr[u + 1]; ++e)
-      if (c->col[e] != u) tmp.emplace_back(c->col[e], c->wt[e]);
-    if (c->row_ptr[u + 1] - c->row_ptr[u] > kBigDeg) ++c->big_nodes;
-    std::sort(tmp.begin(), tmp.end());
-    for (size_t i = 0; i < tmp.size(); ++i) {
-      if (i && tmp[i].first == tmp[i - 1].first) continue;  // first = min metric
-      c->nb_id.push_back(tmp[i].first);
-      c->nb_w.push_back(tmp[i].second);
-    }
-    c->nb_ptr[u + 1] = (uint32_t)c->nb_id.size();
-  }
-  HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, c->d_row_ptr.upload(c->row_ptr.data(), N + 1, c->stream));
-  HIP_TRY(c, c->d_col.upload(c->col.data(), E, c->stream));
-  HIP_TRY(c, c->d_wt.upload(c->wt.data(), E, c->stream));
-  HIP_TRY(c, c->d_met.upload(c->met.data(), E, c->stream));
-  HIP_TRY(c, c->d_rev.upload(c->rev.data(), E, c->stream));
-  HIP_TRY(c, c->d_link.upload(c->link.data(), E, c->stream));
-  c->max_link = 0;
-  for (uint32_t e = 0; e < E; ++e) c->max_link = std::max(c->max_link, c->link[e]);
-  HIP_TRY(c, c->d_ovl.upload(c->ovl.data(), N, c->stream));
-  HIP_TRY(c, c->d_nb_ptr.upload(c->nb_ptr.data(), N + 1, c->stream));
-  HIP_TRY(c, c->d_nb_id.upload(c->nb_id.data(), c->nb_id.size(), c->stream));
-  HIP_TRY(c, c->d_nb_w.upload(c->nb_w.data(), c->nb_w.size(), c->stream));
-  {  // per edge: the head's index among the tail's distinct neighbours (the
-     // route selection's next-hop bitmap of that neighbour)
-    std::vector<uint32_t>& enb = c->edge_nb;
-    enb.assign(std::max<uint32_t>(E, 1), kInf);
-    for (uint32_t u = 0; u < N; ++u) {
-      const auto b = c->nb_id.begin() + c->nb_ptr[u], e = c->nb_id.begin() + c->nb_ptr[u + 1];
-      for (uint32_t q = c->row_ptr[u]; q < c->row_ptr[u + 1]; ++q)
-        enb[q] = c->col[q] == u ? kInf : (uint32_t)(std::lower_bound(b, e, c->col[q]) - b);
-    }
-    HIP_TRY(c, c->d_edge_nb.upload(enb.data(), enb.size(), c->stream));
-  }
-  // sliced ELL (SELL-64): slice = 64 consecutive nodes, width = max degree in
-  // the slice, entry (slice, j, lane) = j-th neighbour of node slice*64+lane,
-  // padded with N (F[N] == 0 in the BFS kernel)
-  {
-    const uint32_t n_slices = (N + kSliceW - 1) / kSliceW;
-    c->sell_ptr.assign(n_slices + 1, 0);
-    for (uint32_t sl = 0; sl < n_slices; ++sl) {
-      uint32_t w = 0;
-      for (uint32_t v = sl * kSliceW; v < std::min(N, (sl + 1) * kSliceW); ++v)
-        w = std::max(w, c->row_ptr[v + 1] - c->row_ptr[v]);
-      c->sell_ptr[sl + 1] = c->sell_ptr[sl] + w * kSliceW;
-    }
-    // + one trailing all-padding group (msbfs_team.hip pads its column streams with it)
-    // + padding columns (node N): the trailing all-padding group the team
-    // kernel's stream pads with, and the BFS kernels' unconditional loads up
-    // to three groups of 8 columns past a slice's last column
-    c->sell_col.assign(c->sell_ptr[n_slices] + 32 * kSliceW, N);
-    ++c->sell_ver;
-    for (uint32_t v = 0; v < N; ++v) {
-      const uint32_t sl = v / kSliceW, ln = v % kSliceW;
-      for (uint32_t j = 0; j < c->row_ptr[v + 1] - c->row_ptr[v]; ++j) {
-        const uint32_t x = c->col[c->row_ptr[v] + j];
-        c->sell_col[c->sell_ptr[sl] + j * kSliceW + ln] = x == v ? N : x;  // dead slot: padding
-      }
-    }
-    HIP_TRY(c, c->d_sell_ptr.upload(c->sell_ptr.data(), c->sell_ptr.size(), c->stream));
-    HIP_TRY(c, c->d_sell_col.upload(c->sell_col.data(), c->sell_col.size(), c->stream));
-    // msbfs_kernel's slices per wave: a level's pull sweep costs each wave the
-    // column groups of its slices and the workgroup waits for the slowest, so
-    // slices are dealt widest first to the wave with the fewest groups that
-    // still has a free slot (OWN slots per wave; unused slots = kNoSlice)
-    if (N <= kMsMaxNodes) {
-      const uint32_t own = ms_own(N), waves = kMsThreads / 64;
-      std::vector<uint32_t> order(n_slices), load(waves, 0), used(waves, 0);
-      std::iota(order.begin(), order.end(), 0u);
-      auto width = [&](uint32_t sl) { return (c->sell_ptr[sl + 1] - c->sell_ptr[sl]) / kSliceW; };
-      std::stable_sort(order.begin(), order.end(),
-                       [&](uint32_t a, uint32_t b) { return width(a) > width(b); });
-      std::vector<uint32_t> smap((size_t)waves * own, kNoSlice);
-      for (uint32_t sl : order) {
-        uint32_t best = waves;
-        for (uint32_t w = 0; w < waves; ++w)
-          if (used[w] < own && (best == waves || load[w] < load[best])) best = w;
-        smap[(size_t)best * own + used[best]++] = sl;
-        load[best] += std::max(1u, width(sl));
-      }
-      if (std::getenv("SPF_SMAP_STRIDED"))  // A/B: slot i of wave w = slice 16 i + w
-        for (uint32_t w = 0; w < waves; ++w)
-          for (uint32_t i = 0; i < own; ++i) {
-            const uint32_t sl = i * waves + w;
-            smap[(size_t)w * own + i] = sl < n_slices ? sl : kNoSlice;
-          }
-      HIP_TRY(c, c->d_ms_smap.upload(smap.data(), smap.size(), c->stream));
-    }
-    // the same columns packed four u16 ids per lane (groups of 4 per slice,
-    // at least one), for msbfs_planes_kernel (N <= 10240)
-    c->sell4_ptr.assign(n_slices + 1, 0);
-    c->sell4.clear();
-    if (4ull * N < 65536) {
-      for (uint32_t sl = 0; sl < n_slices; ++sl) {
-        const uint32_t w = (c->sell_ptr[sl + 1] - c->sell_ptr[sl]) / kSliceW;
-        const uint32_t groups = std::max(1u, (w + 3) / 4);
-        c->sell4_ptr[sl + 1] = c->sell4_ptr[sl] + groups * kSliceW;
-      }
-      c->sell4.assign(2ull * c->sell4_ptr[n_slices], 0);
-      for (uint32_t sl = 0; sl < n_slices; ++sl) {
-        const uint32_t w = (c->sell_ptr[sl + 1] - c->sell_ptr[sl]) / kSliceW;
-        const uint32_t groups = (c->sell4_ptr[sl + 1] - c->sell4_ptr[sl]) / kSliceW;
-        for (uint32_t g = 0; g < groups; ++g)
-          for (uint32_t ln = 0; ln < kSliceW; ++ln) {
-            uint32_t id[4];
-            for (uint32_t k = 0; k < 4; ++k) {
-              const uint32_t j = 4 * g + k;
-              id[k] = j < w ? c->sell_col[c->sell_ptr[sl] + j * kSliceW + ln] : N;
-            }
-            const size_t e = 2ull * (c->sell4_ptr[sl] + g * kSliceW + ln);
-            // byte offsets into the BFS frontier array (4 B per node)
-            c->sell4[e] = 4 * id[0] | (4 * id[1] << 16);
-            c->sell4[e + 1] = 4 * id[2] | (4 * id[3] << 16);
-          }
-      }
-      HIP_TRY(c, c->d_sell4_ptr.upload(c->sell4_ptr.data(), c->sell4_ptr.size(), c->stream));
-      HIP_TRY(c, c->d_sell4.upload(c->sell4.data(), c->sell4.size(), c->stream));
-    }
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->loaded = true;
-  ++c->shape;
-  ++c->epoch;
-  ++c->layout;
-  return SPF_OK;
-}
-
-// In-place graph patches.  The reference reacts to
-// every adjacency-database publication by re-running updateAdjacencyDatabase
-// (LinkState.cpp:564-719) and dropping its SPF memo; the common cases -- a node
-// toggling its overload bit (the per-iteration perturbation of
-// BM_DecisionFabric, RoutingBenchmarkUtils.cpp:453-479) or a link metric
-// change -- leave the CSR structure intact, so only the affected bytes are
-// rewritten here instead of a full spf_graph_load.
-spf_status spf_graph_set_overload(spf_ctx* c, const uint32_t* nodes, const uint8_t* overloaded,
-                                  uint32_t n) {
-  if (!c || (n && (!nodes || !overloaded)))
-    return fail(c, SPF_E_INVALID, "spf_graph_set_overload: NULL argument");
-  if (!c->loaded) return fail(c, SPF_E_STATE, "no graph loaded");
-  for (uint32_t i = 0; i < n; ++i)
-    if (nodes[i] >= c->N) return fail(c, SPF_E_INVALID, "node %u out of range", nodes[i]);
-  bool changed = false;
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint8_t v = overloaded[i] ? 1 : 0;
-    if (c->ovl[nodes[i]] != v) {
-      c->ovl[nodes[i]] = v;
-      changed = true;
-    }
-  }
-  if (!changed) return SPF_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, stage_upload(c, c->d_ovl, c->ovl.data(), c->N));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  stage_done(c);
-  ++c->epoch;
-  return SPF_OK;
-}
-
-spf_status spf_graph_set_metric(spf_ctx* c, const uint32_t* edges, const int32_t* metric,
-                                uint32_t n) {
-  if (!c || (n && (!edges || !metric)))
-    return fail(c, SPF_E_INVALID, "spf_graph_set_metric: NULL argument");
-  if (!c->loaded) return fail(c, SPF_E_STATE, "no graph loaded");
-  for (uint32_t i = 0; i < n; ++i)
-    if (edges[i] >= c->E) return fail(c, SPF_E_INVALID, "edge %u out of range", edges[i]);
-  std::vector<uint32_t> wt = c->wt;
-  std::vector<int32_t> met = c->met;
-  bool changed = false;
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint32_t w = metric[i] > 0 ? (uint32_t)metric[i] : 0u;
-    changed |= met[edges[i]] != metric[i];
-    wt[edges[i]] = w;
-    met[edges[i]] = metric[i];
-  }
-  if (!changed) return SPF_OK;
-  c->wt.swap(wt);
-  c->met.swap(met);
-  metric_facts(c);
-  // min metric per distinct neighbour of every tail touched
-  std::vector<uint32_t> tails;
-  for (uint32_t i = 0; i < n; ++i)
-    tails.push_back((uint32_t)(std::upper_bound(c->row_ptr.begin(), c->row_ptr.end(), edges[i]) -
-                               c->row_ptr.begin()) - 1);
-  std::sort(tails.begin(), tails.end());
-  tails.erase(std::unique(tails.begin(), tails.end()), tails.end());
-  for (uint32_t u : tails) {
-    const uint32_t b = c->nb_ptr[u], e = c->nb_ptr[u + 1];
-    for (uint32_t j = b; j < e; ++j) c->nb_w[j] = kInf;
-    for (uint32_t k = c->row_ptr[u]; k < c->row_ptr[u + 1]; ++k) {
-      if (c->col[k] == u) continue;  // dead slot
-      const uint32_t j = (uint32_t)(std::lower_bound(c->nb_id.begin() + b, c->nb_id.begin() + e,
-                                                     c->col[k]) - c->nb_id.begin());
-      c->nb_w[j] = std::min(c->nb_w[j], c->wt[k]);
-    }
-  }
-  HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, stage_upload(c, c->d_wt, c->wt.data(), c->E));
-  HIP_TRY(c, stage_upload(c, c->d_met, c->met.data(), c->E));
-  HIP_TRY(c, stage_upload(c, c->d_nb_w, c->nb_w.data(), c->nb_w.size()));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  stage_done(c);
-  ++c->epoch;
-  return SPF_OK;
-}
-
-// Rows rewritten in place (a link going down or up,
-// or an adjacency withdrawn and advertised again, without a reload).  Each
-// listed node keeps its row length; a dead slot is a self-loop (col = the
-// node, metric 1): no kernel relaxes, pushes or pulls anything over one, the
-// distinct-neighbour lists and the route tables skip them.  The derived
-// tables of the touched rows are patched: reverse edges (by link id), the
-// distinct-neighbour lists (rebuilt when a count changes: plans whose
-// sources' next-hop layout changed fail with SPF_E_STATE), the route tables'
-// per-edge neighbour index and the sliced-ELL columns.  Plans re-derive at
-// their next execute, as after a metric patch.
-spf_status spf_graph_patch_rows(spf_ctx* c, const uint32_t* nodes, uint32_t n, const uint32_t* col,
-                                const int32_t* metric, const uint32_t* link) {
-  if (!c || (n && (!nodes || !col || !metric || !link)))
-    return fail(c, SPF_E_INVALID, "spf_graph_patch_rows: NULL argument");
-  if (!c->loaded) return fail(c, SPF_E_STATE, "no graph loaded");
-  const uint32_t N = c->N;
-  std::vector<uint8_t> touched(N, 0);
-
-  for (uint32_t i = 0; i < n; ++i) {
-    if (nodes[i] >= N) return fail(c, SPF_E_INVALID, "node %u out of range", nodes[i]);
-    if (touched[nodes[i]]++) return fail(c, SPF_E_INVALID, "node %u listed twice", nodes[i]);
-
-  }
-  if (!n) return SPF_OK;
-  // validate the new rows before changing anything
-  const uint32_t max_link = (uint32_t)(c->link_slot.size() / 2) - 1;
-  {
-    size_t o = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-      const uint32_t u = nodes[i];
-      for (uint32_t e = c->row_ptr[u]; e < c->row_ptr[u + 1]; ++e, ++o) {
-        if (col[o] >= N) return fail(c, SPF_E_INVALID, "row of %u: head %u out of range", u, col[o]);
-        if (link[o] > max_link)
-          return fail(c, SPF_E_INVALID, "row of %u: link %u is not a link of the loaded graph", u, link[o]);
-        if (col[o] == u && metric[o] != 1)
-          return fail(c, SPF_E_INVALID, "row of %u: a dead slot (self-loop) must carry metric 1", u);
-      }
-    }
-  }
-  std::vector<uint32_t> old_nb(n);
-  for (uint32_t i = 0; i < n; ++i) old_nb[i] = c->nb_ptr[nodes[i] + 1] - c->nb_ptr[nodes[i]];
-  // rows (the metric-fact counts lose the old rows' live edges and gain the
-  // new ones')
-  {
-    size_t o = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-      const uint32_t u = nodes[i];
-      for (uint32_t e = c->row_ptr[u]; e < c->row_ptr[u + 1]; ++e)
-        if (c->col[e] != u) {
-          c->n_nonpos -= c->met[e] <= 0;
-          c->n_neg -= c->met[e] < 0;
-          c->n_at_max -= c->wt[e] == c->max_metric;
-        }
-    }
-    for (uint32_t i = 0; i < n; ++i) {
-      const uint32_t u = nodes[i];
-      for (uint32_t e = c->row_ptr[u]; e < c->row_ptr[u + 1]; ++e, ++o) {
-        c->col[e] = col[o];
-        c->met[e] = metric[o];
-        c->wt[e] = metric[o] > 0 ? (uint32_t)metric[o] : 0u;
-        c->link[e] = link[o];
-      }
-    }
-    for (uint32_t i = 0; i < n; ++i) {
-      const uint32_t u = nodes[i];
-      for (uint32_t e = c->row_ptr[u]; e < c->row_ptr[u + 1]; ++e)
-        if (c->col[e] != u) {
-          c->n_nonpos += c->met[e] <= 0;
-          c->n_neg += c->met[e] < 0;
-          if (c->wt[e] > c->max_metric) {
-            c->max_metric = c->wt[e];
-            c->n_at_max = 1;
-          } else if (c->wt[e] == c->max_metric) {
-            ++c->n_at_max;
-          }
-        }
-    }
-  }
-  // link slots and reverse edges: a link's slot in an untouched row keeps its
-  // position; its slots in touched rows are where the new rows put them
-  auto tail = [&](uint32_t e) {
-    return (uint32_t)(std::upper_bound(c->row_ptr.begin(), c->row_ptr.end(), e) - c->row_ptr.begin()) - 1;
-  };
-  std::unordered_map<uint32_t, std::vector<uint32_t>> moved;  // link -> its slots in touched rows
-  std::vector<uint32_t> rev_dirty;  // reverse-edge entries whose value changed
-  auto set_rev = [&](uint32_t e, uint32_t r) {
-    if (c->rev[e] != r) {
-      c->rev[e] = r;
-      rev_dirty.push_back(e);
-    }
-  };
-  for (uint32_t i = 0; i < n; ++i)
-    for (uint32_t e = c->row_ptr[nodes[i]]; e < c->row_ptr[nodes[i] + 1]; ++e) moved[c->link[e]].push_back(e);
-  for (auto& [l, es] : moved) {
-    uint32_t* ls = &c->link_slot[2 * (size_t)l];
-    std::vector<uint32_t> slots = es;
-    for (int k = 0; k < 2; ++k)  // its slot in an untouched row, if any, stays
-      if (ls[k] != kInf && !touched[tail(ls[k])] && c->link[ls[k]] == l) slots.push_back(ls[k]);
-    if (slots.size() != 2)
-      return fail(c, SPF_E_INVALID, "link %u has %zu slots after the patch (2 needed)", l, slots.size());
-    ls[0] = slots[0];
-    ls[1] = slots[1];
-    set_rev(slots[0], slots[1]);
-    set_rev(slots[1], slots[0]);
-    const uint32_t a = tail(slots[0]), b = tail(slots[1]);
-    const bool dead0 = c->col[slots[0]] == a, dead1 = c->col[slots[1]] == b;
-    if (dead0 != dead1 || (!dead0 && (c->col[slots[0]] != b || c->col[slots[1]] != a)))
-      return fail(c, SPF_E_INVALID, "link %u: its two slots are not one link in both directions", l);
-  }
-  // graph-wide metric facts over live edges: from the counts, unless every
-  // edge at the old maximum left (then the maximum fell: one scan)
-  if (c->n_at_max == 0) metric_facts(c);
-  else metric_flags(c);
-  // distinct up neighbours of the touched nodes; the lists are rebuilt (every
-  // untouched node's range copied) when a count changes
-  std::vector<std::vector<std::pair<uint32_t, uint32_t>>> fresh(n);
-  bool counts = false;
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint32_t u = nodes[i];
-    auto& t = fresh[i];
-    for (uint32_t e = c->row_ptr[u]; e < c->row_ptr[u + 1]; ++e)
-      if (c->col[e] != u) t.emplace_back(c->col[e], c->wt[e]);
-    std::sort(t.begin(), t.end());
-    t.erase(std::unique(t.begin(), t.end(), [](const auto& a, const auto& b) { return a.first == b.first; }),
-            t.end());
-    counts |= t.size() != old_nb[i];
-  }
-  if (counts) {
-    // the untouched nodes' lists move as whole blocks between touched nodes
-    std::vector<uint32_t> order(n);
-    std::iota(order.begin(), order.end(), 0u);
-    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return nodes[a] < nodes[b]; });
-    std::vector<uint32_t> ptr(N + 1, 0), id, w;
-    id.reserve(c->nb_id.size() + 16);
-    w.reserve(c->nb_id.size() + 16);
-    uint32_t next = 0;  // first node not yet placed
-    auto block = [&](uint32_t to) {  // untouched nodes next .. to - 1
-      const uint32_t b = c->nb_ptr[next], e = c->nb_ptr[to];
-      const int64_t shift = (int64_t)id.size() - (int64_t)b;
-      id.insert(id.end(), c->nb_id.begin() + b, c->nb_id.begin() + e);
-      w.insert(w.end(), c->nb_w.begin() + b, c->nb_w.begin() + e);
-      for (uint32_t u = next; u < to; ++u) ptr[u + 1] = (uint32_t)((int64_t)c->nb_ptr[u + 1] + shift);
-    };
-    for (uint32_t oi : order) {
-      const uint32_t u = nodes[oi];
-      block(u);
-      for (const auto& x : fresh[oi]) {
-        id.push_back(x.first);
-        w.push_back(x.second);
-      }
-      ptr[u + 1] = (uint32_t)id.size();
-      next = u + 1;
-    }
-    block(N);
-    c->nb_ptr.swap(ptr);
-    c->nb_id.swap(id);
-    c->nb_w.swap(w);
-    ++c->layout;
-    c->qt.stale = true;  // a neighbour set changed: its twin class may split or merge
-  } else {
-    for (uint32_t i = 0; i < n; ++i) {
-      const uint32_t b = c->nb_ptr[nodes[i]];
-      for (size_t k = 0; k < fresh[i].size(); ++k) {
-        if (c->nb_id[b + k] != fresh[i][k].first) c->qt.stale = true;
-        c->nb_id[b + k] = fresh[i][k].first;
-        c->nb_w[b + k] = fresh[i][k].second;
-      }
-    }
-  }
-  HIP_TRY(c, hipSetDevice(c->device));
-  // the route tables' per-edge neighbour index (touched tails only)
-  std::vector<uint32_t>& enb = c->edge_nb;
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint32_t u = nodes[i];
-    const auto b = c->nb_id.begin() + c->nb_ptr[u], e = c->nb_id.begin() + c->nb_ptr[u + 1];
-    for (uint32_t q = c->row_ptr[u]; q < c->row_ptr[u + 1]; ++q)
-      enb[q] = c->col[q] == u ? kInf : (uint32_t)(std::lower_bound(b, e, c->col[q]) - b);
-  }
-  // sliced-ELL columns of the touched nodes (and their packed u16 copies)
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint32_t v = nodes[i], sl = v / kSliceW, ln = v % kSliceW;
-    const uint32_t deg = c->row_ptr[v + 1] - c->row_ptr[v];
-    for (uint32_t j = 0; j < deg; ++j) {
-      const uint32_t x = c->col[c->row_ptr[v] + j];
-      c->sell_col[c->sell_ptr[sl] + j * kSliceW + ln] = x == v ? N : x;
-    }
-    if (!c->sell4.empty()) {
-      const uint32_t w = (c->sell_ptr[sl + 1] - c->sell_ptr[sl]) / kSliceW;
-      const uint32_t groups = (c->sell4_ptr[sl + 1] - c->sell4_ptr[sl]) / kSliceW;
-      for (uint32_t g = 0; g < groups; ++g) {
-        uint32_t id[4];
-        for (uint32_t k = 0; k < 4; ++k) {
-          const uint32_t j = 4 * g + k;
-          id[k] = j < w ? c->sell_col[c->sell_ptr[sl] + j * kSliceW + ln] : N;
-        }
-        const size_t e = 2ull * (c->sell4_ptr[sl] + g * kSliceW + ln);
-        c->sell4[e] = 4 * id[0] | (4 * id[1] << 16);
-        c->sell4[e + 1] = 4 * id[2] | (4 * id[3] << 16);
-      }
-    }
-  }
-  ++c->sell_ver;  // (msbfs_team_prepare's cached tables read sell_col)
-  // upload the changed ranges only: the touched rows (merged when adjacent),
-  // the partner slots their reverse edges point at, and the touched slices
-  std::vector<uint32_t> order(nodes, nodes + n);
-  std::sort(order.begin(), order.end());
-  std::vector<std::pair<uint32_t, uint32_t>> runs;  // [begin, end) edge ranges
-  for (uint32_t u : order) {
-    const uint32_t b = c->row_ptr[u], e = c->row_ptr[u + 1];
-    if (b == e) continue;
-    if (!runs.empty() && runs.back().second == b)
-      runs.back().second = e;
-    else
-      runs.emplace_back(b, e);
-  }
-  // (uploads through the pinned stage: queued, not a blocking pageable copy each)
-  for (const auto& r : runs) {
-    const size_t b = r.first, k = r.second - r.first;
-    HIP_TRY(c, stage_upload_at(c, c->d_col, c->col.data(), b, k));
-    HIP_TRY(c, stage_upload_at(c, c->d_wt, c->wt.data(), b, k));
-    HIP_TRY(c, stage_upload_at(c, c->d_met, c->met.data(), b, k));
-    HIP_TRY(c, stage_upload_at(c, c->d_rev, c->rev.data(), b, k));
-    HIP_TRY(c, stage_upload_at(c, c->d_link, c->link.data(), b, k));
-    HIP_TRY(c, stage_upload_at(c, c->d_edge_nb, enb.data(), b, k));
-  }
-  {  // reverse-edge entries outside the touched rows whose value changed
-    std::sort(rev_dirty.begin(), rev_dirty.end());
-    rev_dirty.erase(std::unique(rev_dirty.begin(), rev_dirty.end()), rev_dirty.end());
-    auto in_runs = [&](uint32_t q) {
-      auto it = std::upper_bound(runs.begin(), runs.end(), std::make_pair(q, ~0u));
-      return it != runs.begin() && q < std::prev(it)->second;
-    };
-    for (size_t a = 0; a < rev_dirty.size();) {
-      if (in_runs(rev_dirty[a])) {
-        ++a;
-        continue;
-      }
-      size_t b = a + 1;
-      while (b < rev_dirty.size() && rev_dirty[b] == rev_dirty[b - 1] + 1 && !in_runs(rev_dirty[b])) ++b;
-      HIP_TRY(c, stage_upload_at(c, c->d_rev, c->rev.data(), rev_dirty[a], b - a));
-      a = b;
-    }
-  }
-  if (counts) {  // the lists moved from the first touched node on
-    const uint32_t u0 = order.front();
-    const size_t b = c->nb_ptr[u0];
-    HIP_TRY(c, stage_upload_at(c, c->d_nb_ptr, c->nb_ptr.data(), u0, N + 1 - u0));
-    if (c->d_nb_id.n < c->nb_id.size()) {  // (the lists outgrew the buffers)
-      HIP_TRY(c, stage_upload(c, c->d_nb_id, c->nb_id.data(), c->nb_id.size()));
-      HIP_TRY(c, stage_upload(c, c->d_nb_w, c->nb_w.data(), c->nb_w.size()));
-    } else {
-      HIP_TRY(c, stage_upload_at(c, c->d_nb_id, c->nb_id.data(), b, c->nb_id.size() - b));
-      HIP_TRY(c, stage_upload_at(c, c->d_nb_w, c->nb_w.data(), b, c->nb_w.size() - b));
-    }
-  } else {
-    for (uint32_t u : order) {
-      const size_t b = c->nb_ptr[u], k = c->nb_ptr[u + 1] - b;
-      HIP_TRY(c, stage_upload_at(c, c->d_nb_id, c->nb_id.data(), b, k));
-      HIP_TRY(c, stage_upload_at(c, c->d_nb_w, c->nb_w.data(), b, k));
-    }
-  }
-  {
-    std::vector<uint32_t> slices;
-    for (uint32_t u : order) slices.push_back(u / kSliceW);
-    slices.erase(std::unique(slices.begin(), slices.end()), slices.end());
-    for (uint32_t sl : slices) {
-      const size_t b = c->sell_ptr[sl], k = c->sell_ptr[sl + 1] - b;
-      HIP_TRY(c, stage_upload_at(c, c->d_sell_col, c->sell_col.data(), b, k));
-      if (!c->sell4.empty()) {
-        const size_t b4 = 2ull * c->sell4_ptr[sl], k4 = 2ull * (c->sell4_ptr[sl + 1] - c->sell4_ptr[sl]);
-        HIP_TRY(c, stage_upload_at(c, c->d_sell4, c->sell4.data(), b4, k4));
-      }
-    }
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  stage_done(c);
-  ++c->epoch;
-  return SPF_OK;
-}
-
-spf_status spf_twin_classes(uint32_t n_nodes, const uint32_t* nb_ptr, const uint32_t* nb_id,
-                            uint32_t* cls, uint32_t* n_classes) {
-  if (!nb_ptr || !cls || !n_classes || (n_nodes && nb_ptr[n_nodes] && !nb_id))
-    return fail(nullptr, SPF_E_INVALID, "spf_twin_classes: NULL argument");
-  for (uint32_t v = 0; v < n_nodes; ++v)
-    if (nb_ptr[v] > nb_ptr[v + 1]) return fail(nullptr, SPF_E_INVALID, "nb_ptr not monotone at %u", v);
-  *n_classes = twin_classes(n_nodes, nb_ptr, nb_id, cls);
-  return SPF_OK;
-}
-
-spf_status spf_graph_quotient(spf_ctx* c, uint32_t* n_classes, uint64_t* n_edges, uint32_t* in_use) {
-  if (!c) return fail(c, SPF_E_INVALID, "spf_graph_quotient: NULL context");
-  if (!c->loaded) return fail(c, SPF_E_STATE, "no graph loaded");
-  const spf_status st = quotient_prepare(c);
-  if (st != SPF_OK) return st;
-  if (n_classes) *n_classes = c->qt.n_cls;
-  if (n_edges) *n_edges = c->qt.n_edge;
-  if (in_use) *in_use = (c->N <= kMsMaxNodes && !use_planes(c) && use_quotient(c)) ? 1u : 0u;
-  return SPF_OK;
-}
-
-uint64_t spf_graph_epoch(const spf_ctx* c) { return c ? c->epoch : 0; }
-uint64_t spf_graph_loads(const spf_ctx* c) { return c ? c->shape : 0; }
-
 spf_status spf_src_neighbors(const spf_ctx* c, uint32_t src, uint32_t* out,
                              uint32_t cap, uint32_t* count) {
   if (!c || !c->loaded) return SPF_E_STATE;
@@ -2446,14 +1802,6 @@ spf_status spf_src_neighbors(const spf_ctx* c, uint32_t src, uint32_t* out,
 }  // extern "C"
 
 namespace {
-
-// u8 narrow rows for the next-hop pass: 4x fewer bytes per neighbour row
-// read, paid for by a second store per (source, slice, level) in
-// msbfs_kernel.  Worth it when next-hop work (sum of neighbour counts)
-// outweighs the BFS store work, which grows with the number of levels:
-// dense fabrics (degree ~23, 5 levels) yes; always with the register-plane
-// BFS (one coalesced store per row).  SPF_NARROW=0/1 overrides (experiments).
-bool use_planes(const spf_ctx* c);
 
 // Eccentricity estimate of every node (hop counts, drains ignored): the
 // largest BFS distance from a few landmarks -- the node farthest from node
@@ -2551,6 +1899,12 @@ uint32_t depth_bound(spf_ctx* c) {
   return c->dbound;
 }
 
+// u8 narrow rows for the next-hop pass: 4x fewer bytes per neighbour row
+// read, paid for by a second store per (source, slice, level) in
+// msbfs_kernel.  Worth it when next-hop work (sum of neighbour counts)
+// outweighs the BFS store work, which grows with the number of levels:
+// dense fabrics (degree ~23, 5 levels) yes; always with the register-plane
+// BFS (one coalesced store per row).  SPF_NARROW=0/1 overrides (experiments).
 bool use_narrow(const spf_ctx* c, const spf_plan* p) {
   if (const char* e = std::getenv("SPF_NARROW")) return e[0] != '0';
   // the register-plane BFS writes each row once, coalesced: the u8 copy
@@ -3202,100 +2556,11 @@ bool ms_double_buffer(const spf_ctx* c) {
   return msbfs_lds_bytes(c->N) + 2ull * n_col > kMaxLds && msbfs_lds_bytes(c->N, true) <= kMaxLds;
 }
 
-// False-twin classes: nodes whose distinct-neighbour lists (ascending ids)
-// are equal share a class; classes are numbered by their first member.  Lists
-// are hashed, then compared within a hash bucket.
-uint32_t twin_classes(uint32_t N, const uint32_t* nb_ptr, const uint32_t* nb_id, uint32_t* cls) {
-  std::vector<uint64_t> h(N);
-  for (uint32_t v = 0; v < N; ++v) {
-    uint64_t x = 0x9E3779B97F4A7C15ull ^ (nb_ptr[v + 1] - nb_ptr[v]);
-    for (uint32_t e = nb_ptr[v]; e < nb_ptr[v + 1]; ++e) {
-      x ^= nb_id[e] + 0x9E3779B97F4A7C15ull + (x << 6) + (x >> 2);
-      x *= 0xFF51AFD7ED558CCDull;
-    }
-    h[v] = x;
-  }
-  std::vector<uint32_t> order(N), rep(N);
-  std::iota(order.begin(), order.end(), 0u);
-  std::sort(order.begin(), order.end(),
-            [&](uint32_t a, uint32_t b) { return h[a] != h[b] ? h[a] < h[b] : a < b; });
-  auto same = [&](uint32_t a, uint32_t b) {
-    const uint32_t k = nb_ptr[a + 1] - nb_ptr[a];
-    return k == nb_ptr[b + 1] - nb_ptr[b] &&
-           std::equal(nb_id + nb_ptr[a], nb_id + nb_ptr[a] + k, nb_id + nb_ptr[b]);
-  };
-  std::vector<uint32_t> reps;  // first members of the classes in one hash bucket
-  for (size_t i = 0; i < N;) {
-    size_t j = i;
-    reps.clear();
-    for (; j < N && h[order[j]] == h[order[i]]; ++j) {
-      const uint32_t v = order[j];
-      rep[v] = v;
-      for (uint32_t r : reps)
-        if (same(r, v)) {
-          rep[v] = r;
-          break;
-        }
-      if (rep[v] == v) reps.push_back(v);
-    }
-    i = j;
-  }
-  uint32_t n_cls = 0;
-  for (uint32_t v = 0; v < N; ++v) cls[v] = rep[v] == v ? n_cls++ : cls[rep[v]];  // rep[v] <= v
-  return n_cls;
-}
-
 // LDS of msbfs_kernel's quotient variant: CF and QA (two buffers each), the
 // row/column tables, the small arrays, the source marks
 size_t msbfs_q_lds_bytes(uint32_t N, uint32_t n_cls, uint32_t n_vrow) {
   const size_t nvp = (n_vrow + 7u) & ~7u;
   return 32ull * (n_cls + 1) + 2ull * (1 + kQChunk) * nvp + 4ull * (4 * kMsBatch + 5) + ((N + 3u) & ~3u);
-}
-
-// The quotient tables of the loaded graph, rebuilt when stale.  A node's
-// neighbours are whole classes (links are up in both directions or neither),
-// so the quotient row of a class is the set of classes of its first member's
-// neighbours; rows are cut into chunks of kQChunk columns padded with n_cls.
-spf_status quotient_prepare(spf_ctx* c) {
-  spf_ctx::Quotient& q = c->qt;
-  if (!q.stale) return SPF_OK;
-  const uint32_t N = c->N;
-  q.n_cls = q.n_vrow = 0;
-  q.n_edge = 0;
-  q.stale = false;
-  if (N > kMsMaxNodes) return SPF_OK;  // (msbfs_kernel does not run on such graphs)
-  std::vector<uint32_t> cls(N);
-  q.n_cls = twin_classes(N, c->nb_ptr.data(), c->nb_id.data(), cls.data());
-  q.cls.assign(cls.begin(), cls.end());
-  std::vector<uint32_t> row_of, cols, qn;  // per chunk: its row; kQChunk columns
-  std::vector<uint8_t> seen(N, 0);         // (first members only)
-  for (uint32_t v = 0; v < N; ++v) {
-    if (seen[cls[v]]) continue;
-    seen[cls[v]] = 1;
-    qn.clear();
-    for (uint32_t e = c->nb_ptr[v]; e < c->nb_ptr[v + 1]; ++e) qn.push_back(cls[c->nb_id[e]]);
-    std::sort(qn.begin(), qn.end());
-    qn.erase(std::unique(qn.begin(), qn.end()), qn.end());
-    q.n_edge += qn.size();
-    for (size_t b = 0; b < qn.size(); b += kQChunk) {
-      row_of.push_back(cls[v]);
-      for (size_t j = 0; j < kQChunk; ++j) cols.push_back(b + j < qn.size() ? qn[b + j] : q.n_cls);
-    }
-  }
-  q.n_vrow = (uint32_t)row_of.size();
-  const size_t nvp = (q.n_vrow + 7u) & ~7u;
-  q.tab.assign((1 + kQChunk) * nvp, (uint16_t)q.n_cls);
-  for (uint32_t r = 0; r < q.n_vrow; ++r) {
-    q.tab[r] = (uint16_t)row_of[r];
-    for (uint32_t j = 0; j < kQChunk; ++j) q.tab[nvp + j * nvp + r] = (uint16_t)cols[(size_t)r * kQChunk + j];
-  }
-  for (size_t r = q.n_vrow; r < nvp; ++r) q.tab[r] = 0;  // (chunks past n_vrow are not read)
-  HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, hipDeviceSynchronize());  // no launch still reads the old tables
-  HIP_TRY(c, c->d_qcls.upload(q.cls.data(), q.cls.size(), c->stream));
-  HIP_TRY(c, c->d_qtab.upload(q.tab.data(), q.tab.size(), c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return SPF_OK;
 }
 
 // The quotient sweep is taken when it reads at most half the columns of the
@@ -3306,11 +2571,13 @@ bool quotient_allowed(const spf_ctx* c) {
   const char* e = std::getenv("SPF_QUOTIENT");
   return !(e && e[0] == '0');
 }
-bool use_quotient(const spf_ctx* c) {
+}  // namespace
+bool spfi::use_quotient(const spf_ctx* c) {
   const spf_ctx::Quotient& q = c->qt;
   if (!quotient_allowed(c) || q.stale || q.n_cls == 0 || 2 * q.n_edge > c->nb_id.size()) return false;
   return msbfs_q_lds_bytes(c->N, q.n_cls, q.n_vrow) <= kMaxLds;
 }
+namespace {
 
 // msbfs_kernel's sources per workgroup.  SPF_MSBFS_BATCH=1..64 fixes it
 // (tests: full batches on graphs too small to fill the chip with them).
@@ -3394,11 +2661,13 @@ void planes_launch(spf_ctx* c, const uint32_t* rows_src, uint32_t rows, uint32_t
 // when levels are many (partial-line rewrites dominate msbfs_kernel) and
 // loses when the edge sweep dominates (it runs 32 sources per sweep, not
 // 64).  SPF_MSBFS=planes|masks overrides (experiments).
-bool use_planes(const spf_ctx* c) {
+}  // namespace
+bool spfi::use_planes(const spf_ctx* c) {
   if (c->N > 10 * (uint32_t)kMsThreads || c->sell4.empty()) return false;
   if (const char* e = std::getenv("SPF_MSBFS")) return e[0] == 'p';
   return c->sell_ptr.back() <= 8ull * c->N;  // sliced-ELL width <= 8 on average
 }
+namespace {
 
 spf_status launch_msbfs(spf_ctx* c, const uint32_t* rows_src, uint32_t rows, uint32_t* D,
                         uint8_t* Dn, uint32_t* maxd, hipStream_t s, uint32_t d_from = 0,

@@ -353,3 +353,122 @@ def test_row_patch_keeps_metric_facts():
                                                           "msbfs_team_kernel")
     same_as_fresh(cc, mm)
     eng.close()
+
+
+# ---- a refused row patch changes nothing ------------------------------------
+def ring130():
+    """130-node ring with chords and two parallel links (CSR arrays, links by
+    id): nodes 63 | 64 straddle a sliced-ELL slice boundary, 129 sits in the
+    last, partial slice.  Returns the arrays and the chord 64 - 101's link id."""
+    links = [(i, (i + 1) % 130, 1 + i % 3, 1 + i % 5) for i in range(130)]
+    links += [(64, 101, 4, 6), (5, 70, 9, 9), (129, 30, 2, 2), (63, 20, 3, 1), (63, 64, 5, 2), (129, 0, 1, 1)]
+    rows = [[] for _ in range(130)]
+    for lid, (a, b, m_ab, m_ba) in enumerate(links):
+        rows[a].append((b, m_ab, lid))
+        rows[b].append((a, m_ba, lid))
+    rp = np.zeros(131, np.uint32)
+    rp[1:] = np.cumsum([len(r) for r in rows])
+    flat = [s for r in rows for s in r]
+    col, met, lid = (np.array([s[k] for s in flat], t) for k, t in ((0, np.uint32), (1, np.int32), (2, np.uint32)))
+    return rp, col, met, lid, np.zeros(130, np.uint8), 130
+
+
+def rows_with_link_down(rp, col, met, lid, link, nodes):
+    """The rows of `nodes` back to back with `link`'s slots dead, and the whole
+    graph's col / metric arrays after that patch."""
+    col2, met2 = col.copy(), met.copy()
+    for u in nodes:
+        for q in range(int(rp[u]), int(rp[u + 1])):
+            if lid[q] == link:
+                col2[q], met2[q] = u, 1
+    pick = np.concatenate([np.arange(int(rp[u]), int(rp[u + 1])) for u in nodes])
+    return col2[pick], met2[pick], lid[pick], col2, met2
+
+
+def all_sources(eng, n):
+    res = eng.plan(list(range(n)), hop=False).execute_host()
+    return res.dist.copy(), [res.nh_matrix(i).copy() for i in range(n)]
+
+
+def same_results(a, b):
+    assert np.array_equal(a[0], b[0])
+    for x, y in zip(a[1], b[1]):
+        assert np.array_equal(x, y)
+
+
+def test_refused_row_patch_changes_nothing():
+    """A patch that leaves a link with one slot dead and the other live is
+    refused with nothing changed (epoch, distances, next hops); the valid
+    link-down patch afterwards equals a fresh load of the patched graph."""
+    import ctypes as C
+
+    from openr_amd import _native as N
+    from openr_amd._native import SpfError
+
+    rp, col, met, lid, ovl, chord = ring130()
+    n = 130
+    with SpfEngine(0) as eng, SpfEngine(0) as ref:
+        eng.load(rp, col, met, lid, ovl)
+        plan = eng.plan(list(range(n)), hop=False)
+        res = plan.execute_host()
+        before = (res.dist.copy(), [res.nh_matrix(i).copy() for i in range(n)])
+        epoch = eng.epoch
+
+        def patch(nodes):
+            cc, mm, ll, col2, met2 = rows_with_link_down(rp, col, met, lid, chord, nodes)
+            nn = np.array(nodes, np.uint32)
+            eng._err(N.lib.spf_graph_patch_rows(eng._h, N.ptr(nn), len(nn), N.ptr(cc), N.ptr(mm, C.c_int32),
+                                                N.ptr(ll)))
+            return col2, met2
+
+        with pytest.raises(SpfError, match="not one link in both directions"):
+            patch([64])  # 101's slot stays live
+        assert eng.epoch == epoch
+        res = plan.execute_host()  # the plan re-executed
+        same_results(before, (res.dist, [res.nh_matrix(i) for i in range(n)]))
+        same_results(before, all_sources(eng, n))
+        col2, met2 = patch([64, 101])
+        assert eng.epoch == epoch + 1
+        ref.load(rp, col2, met2, lid, ovl)
+        want = all_sources(ref, n)
+        assert not np.array_equal(want[0], before[0])
+        same_results(want, all_sources(eng, n))
+
+
+def test_refused_row_patch_changes_no_member():
+    """The same through a two-member spf_mctx on one device: after the refusal
+    both members' results are unchanged and equal to each other."""
+    import ctypes as C
+
+    from openr_amd import _native as N
+    from openr_amd._native import SpfError
+    from openr_amd.engine import SpfMultiEngine
+
+    rp, col, met, lid, ovl, chord = ring130()
+    n = 130
+    with SpfMultiEngine([0, 0]) as m, SpfEngine(0) as ref:
+        m.load(rp, col, met, lid, ovl)
+        members = [SpfEngine(handle=C.c_void_p(N.lib.spf_mctx_member(m._h, i)), n_nodes=n) for i in range(2)]
+        before = [all_sources(e, n) for e in members]
+        same_results(before[0], before[1])
+        epochs = [e.epoch for e in members]
+
+        def patch(nodes):
+            cc, mm, ll, col2, met2 = rows_with_link_down(rp, col, met, lid, chord, nodes)
+            nn = np.array(nodes, np.uint32)
+            m._err(N.lib.spf_mctx_graph_patch_rows(m._h, N.ptr(nn), len(nn), N.ptr(cc), N.ptr(mm, C.c_int32),
+                                                   N.ptr(ll)))
+            return col2, met2
+
+        with pytest.raises(SpfError, match="not one link in both directions"):
+            patch([64])
+        assert [e.epoch for e in members] == epochs
+        for e, b in zip(members, before):
+            same_results(b, all_sources(e, n))
+        col2, met2 = patch([64, 101])
+        assert [e.epoch for e in members] == [x + 1 for x in epochs]
+        ref.load(rp, col2, met2, lid, ovl)
+        want = all_sources(ref, n)
+        for e in members:
+            same_results(want, all_sources(e, n))
+            e.close()  # its plans, before the context they were made on goes
