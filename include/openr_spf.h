@@ -328,6 +328,35 @@ void spf_ksp2_plan_destroy(spf_ksp2_plan* plan);
 /* Sources per KSP2 workgroup (a block is one destination x this many
  * sources; the graph is staged once per block): for traffic accounting. */
 uint32_t spf_ksp2_plan_chunk(const spf_ksp2_plan* plan);
+/* What spf_ksp2_plan_create decided for the plan (read-only; no device work):
+ * the kernel its executes launch and that kernel's launch parameters.
+ *   EXACT    exact_ksp2_kernel: metrics <= 0 or u64 labels, more than 65535
+ *            nodes, or per-wave rows past the LDS (SPF_KSP2_EXACT forces it)
+ *   HBM      ksp2_kernel: the graph read from HBM (>= 65536 directed edges, a
+ *            metric >= 65536, a degree >= 32768, a link that is not exactly
+ *            one {e, rev(e)} pair, or a staged graph that leaves no room for
+ *            two waves; SPF_KSP2_HBM forces it)
+ *   LDS_U32  ksp2_lds_kernel<u32>: the graph staged in LDS, u32 labels
+ *   LDS_U16  ksp2_lds_kernel<u16>, then ksp2_redo_kernel for the pairs whose
+ *            labels or paths outgrow the compact waves
+ * On EXACT plans every other field is 0. */
+typedef enum spf_ksp2_kind {
+  SPF_KSP2_KIND_EXACT = 0,
+  SPF_KSP2_KIND_HBM = 1,
+  SPF_KSP2_KIND_LDS_U32 = 2,
+  SPF_KSP2_KIND_LDS_U16 = 3
+} spf_ksp2_kind;
+struct spf_ksp2_plan_info { /* (a tag, no typedef: the call below bears the name) */
+  uint32_t kind;       /* spf_ksp2_kind */
+  uint32_t waves;      /* waves per workgroup of the pair kernel */
+  uint32_t redo_waves; /* waves per workgroup of the redo pass (LDS_U16), else 0 */
+  uint32_t chunk;      /* sources per workgroup (SPF_KSP2_CHUNK) */
+  uint32_t delta;      /* bucket width of the k = 2 SPF (SPF_KSP2_DELTA) */
+  uint32_t grab;       /* pool words a wave reserves at a time (SPF_KSP2_GRAB) */
+  uint64_t lds_bytes;  /* dynamic LDS of the pair kernel */
+};
+/* SPF_E_INVALID when either argument is NULL (*out untouched). */
+spf_status spf_ksp2_plan_info(const spf_ksp2_plan* plan, struct spf_ksp2_plan_info* out);
 /* Enqueue on `stream` (NULL = context stream).  d_pairs = [n_src * n_nodes],
  * d_pool = pool_words u32, d_counters = 4 u64 zeroed by the call:
  *   [0] pool words claimed, reservations' unused tails included (may

@@ -31,6 +31,7 @@ SPF_FLAG_HOP_COUNT = 0x1
 SPF_FLAG_DIST64 = 0x2
 SPF_UNREACHABLE64 = 0xFFFFFFFFFFFFFFFF
 SPF_KSP2_NONE = 0xFFFFFFFF
+KSP2_KIND_NAMES = ("EXACT", "HBM", "LDS_U32", "LDS_U16")  # spf_ksp2_kind
 SPF_ROUTE_LFA = 0x1
 SPF_ROUTE_COMPACT = 0x2
 SPF_DELTA_DELETE = 0x80000000
@@ -84,6 +85,12 @@ class SpfGraph(C.Structure):
         ("link_id", C.POINTER(C.c_uint32)),
         ("overloaded", C.POINTER(C.c_uint8)),
     ]
+
+
+class SpfKsp2PlanInfo(C.Structure):  # spf_ksp2_plan_info
+    _fields_ = [("kind", C.c_uint32), ("waves", C.c_uint32), ("redo_waves", C.c_uint32),
+                ("chunk", C.c_uint32), ("delta", C.c_uint32), ("grab", C.c_uint32),
+                ("lds_bytes", C.c_uint64)]
 
 
 class OpenrLsdb(C.Structure):
@@ -226,6 +233,7 @@ PROTOTYPES = {
     "spf_ksp2_plan_create": (C.c_int, [_vp, _u32p, C.c_uint32, C.POINTER(_vp)]),
     "spf_ksp2_plan_destroy": (None, [_vp]),
     "spf_ksp2_plan_chunk": (C.c_uint32, [_vp]),
+    "spf_ksp2_plan_info": (C.c_int, [_vp, C.POINTER(SpfKsp2PlanInfo)]),
     "spf_ksp2_execute": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp]),
     "spf_ksp2_digest": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "spf_ksp2_enable_timing": (C.c_int, [_vp, C.c_uint32]),

@@ -1013,6 +1013,24 @@ spf_status spf_ksp2_plan_create(spf_ctx* c, const uint32_t* srcs, uint32_t n_src
 void spf_ksp2_plan_destroy(spf_ksp2_plan* p) { delete p; }
 uint32_t spf_ksp2_plan_chunk(const spf_ksp2_plan* p) { return p ? p->chunk : 0u; }
 
+spf_status spf_ksp2_plan_info(const spf_ksp2_plan* p, struct spf_ksp2_plan_info* out) {
+  if (!p || !out) return fail(p ? p->ctx : nullptr, SPF_E_INVALID, "spf_ksp2_plan_info: NULL argument");
+  *out = {};
+  if (p->exact) {
+    out->kind = SPF_KSP2_KIND_EXACT;
+    return SPF_OK;
+  }
+  // the same tests, in the same order, as spf_ksp2_execute's launch
+  out->kind = p->compact ? SPF_KSP2_KIND_LDS_U16 : p->lds_waves ? SPF_KSP2_KIND_LDS_U32 : SPF_KSP2_KIND_HBM;
+  out->waves = p->lds_waves ? p->lds_waves : (uint32_t)kKspWaves;
+  out->redo_waves = p->compact ? p->redo_waves : 0u;
+  out->chunk = p->chunk;
+  out->delta = p->delta;
+  out->grab = p->grab;
+  out->lds_bytes = p->lds;
+  return SPF_OK;
+}
+
 spf_status spf_ksp2_digest(spf_ksp2_plan* p, const spf_ksp2_pair* d_pairs, const uint32_t* d_pool,
                            const uint64_t* d_link_hash, uint64_t* d_out, void* stream) {
   if (!p || !d_pairs || !d_pool || !d_link_hash || !d_out)

@@ -195,6 +195,19 @@ class Ksp2Result:
         return out
 
 
+@dataclass(frozen=True)
+class Ksp2PlanInfo:
+    """What spf_ksp2_plan_create decided (spf_ksp2_plan_info)."""
+
+    kind: str  # "EXACT", "HBM", "LDS_U32" or "LDS_U16"
+    waves: int  # per workgroup of the pair kernel (0 on EXACT plans, as all below)
+    redo_waves: int  # per workgroup of the redo pass (LDS_U16 only)
+    chunk: int  # sources per workgroup
+    delta: int  # bucket width of the k = 2 SPF
+    grab: int  # pool words a wave reserves at a time
+    lds_bytes: int  # dynamic LDS of the pair kernel
+
+
 class Ksp2Plan(NativeHandle):
     """A fixed source batch for batched KSP2 (``spf_ksp2_plan``)."""
 
@@ -224,6 +237,13 @@ class Ksp2Plan(NativeHandle):
     def chunk(self) -> int:
         """Sources per KSP2 workgroup (spf_ksp2_plan_chunk)."""
         return int(N.lib.spf_ksp2_plan_chunk(self._h))
+
+    def info(self) -> Ksp2PlanInfo:
+        """The kernel the plan's executes launch and its launch parameters."""
+        x = N.SpfKsp2PlanInfo()
+        self._eng._err(N.lib.spf_ksp2_plan_info(self._h, C.byref(x)))
+        return Ksp2PlanInfo(N.KSP2_KIND_NAMES[x.kind], x.waves, x.redo_waves, x.chunk, x.delta,
+                            x.grab, x.lds_bytes)
 
     def enable_timing(self, max_executes: int) -> None:
         self._eng._err(N.lib.spf_ksp2_enable_timing(self._h, max_executes))

@@ -72,6 +72,85 @@ def link_key(link) -> list:
     return [a, b, c, d]
 
 
+def run_plan(eng, srcs, n, kinds=None):
+    """One spf_ksp2_execute of a fresh plan over `srcs` into device buffers
+    sized from the plan's own counter (a second run when the first pool was
+    too small): (Ksp2Result over the raw pool, the four counters).  `kinds`:
+    the plan kinds (Ksp2Plan.info().kind) the caller means to run -- asserted
+    before anything is launched.  Prints the kind (pytest -s / -rP)."""
+    import numpy as np
+
+    from openr_amd.engine import PAIR_DTYPE, Ksp2Result
+    from openr_amd.hiprt import DeviceArray
+
+    p = eng.ksp2_plan(srcs)
+    pairs = cnt = pool = None
+    try:
+        info = p.info()
+        print(f"ksp2 plan: {info}")
+        if kinds is not None:
+            assert info.kind in kinds, (info, kinds)
+        pairs = DeviceArray(len(srcs) * n * 4, np.uint32)
+        cnt = DeviceArray(4, np.uint64, zero=True)
+        words = len(srcs) * n * 24 + (1 << 22)
+        pool = DeviceArray(words, np.uint32)
+        p.execute(pairs.ptr, pool.ptr, words, cnt.ptr)
+        eng.check()
+        c = cnt.numpy().astype(np.int64)
+        if c[0] > words:  # size the pool from the counter and run again
+            pool.free()
+            words = int(c[0]) + int(c[0]) // 4 + (1 << 20)  # grab slack varies run to run
+            pool = DeviceArray(words, np.uint32)
+            p.execute(pairs.ptr, pool.ptr, words, cnt.ptr)
+            eng.check()
+            c = cnt.numpy().astype(np.int64)
+        assert c[0] <= words and not (c[2] & 3), c
+        res = Ksp2Result(np.asarray(srcs, np.uint32), n,
+                         pairs.numpy().view(PAIR_DTYPE).copy(), pool.numpy()[: c[0]].copy())
+        return res, c
+    finally:
+        p.close()
+        for b in (pairs, cnt, pool):
+            if b is not None:
+                b.free()
+
+
+def ksp2_canonical(res):
+    """A Ksp2Result in a form that does not depend on where the records lie
+    in the pool: (n_paths [pairs, 2], the path lengths in (pair, k, list)
+    order, their links concatenated in that order).  Two results give equal
+    triples exactly when paths(i, d, k) agree for every pair and k."""
+    import numpy as np
+
+    pool = np.asarray(res.pool, np.int64)
+    n_paths = np.asarray(res.pairs["n_paths"], np.int64)
+    pair_, k_, q_, at_ = [], [], [], []
+    for k in (0, 1):
+        at = np.asarray(res.pairs["first"][:, k], np.int64).copy()
+        live = np.nonzero(n_paths[:, k] > 0)[0]
+        q = 0
+        while len(live):
+            a = at[live]
+            assert a.min() >= 0 and a.max() + 2 <= len(pool), "a record outside the pool"
+            pair_.append(live)
+            k_.append(np.full(len(live), k))
+            q_.append(np.full(len(live), q))
+            at_.append(a)
+            at[live] = pool[a + 1]
+            q += 1
+            live = live[n_paths[live, k] > q]
+    if not pair_:
+        return n_paths, np.zeros(0, np.int64), np.zeros(0, np.int64)
+    pair_, k_, q_, at_ = (np.concatenate(x) for x in (pair_, k_, q_, at_))
+    order = np.lexsort((q_, k_, pair_))
+    at_ = at_[order]
+    lens = pool[at_]
+    assert (at_ + 2 + lens).max() <= len(pool), "a record runs past the pool"
+    first = np.cumsum(lens) - lens
+    idx = np.repeat(at_ + 2, lens) + (np.arange(int(lens.sum())) - np.repeat(first, lens))
+    return n_paths, lens, pool[idx]
+
+
 def spf_canonical(res) -> dict:
     """Product SpfResult -> the oracle's JSON shape."""
     return {

@@ -159,13 +159,22 @@ def test_large_graph_spf_ecmp_ba250k_matches_oracle(big, monkeypatch):
     _report(got, g["digest"][:n], "ba250k per-source digests", [names[int(s)] for s in srcs])
 
 
-def test_ksp2_wan2k_every_source_engine_digest_matches_oracle():
+@pytest.mark.parametrize("hbm,kinds", [(None, ("LDS_U16", "LDS_U32")), ("1", ("HBM",))],
+                         ids=["staged", "hbm"])
+def test_ksp2_wan2k_every_source_engine_digest_matches_oracle(hbm, kinds, monkeypatch):
     """Config 4's whole output -- getKthPaths(s, d, 1|2) for all 4M pairs --
     reduced on the GPU (spf_ksp2_digest, the reduction bench.py's wan_ksp2
     line checks) against the oracle's digests of every source
     (fullsize_wan2k_ksp2_all.npz), and the GPU reduction equals the oracle's
-    reduction (digest_ksp2) of the same output on the 256-source fixture."""
+    reduction (digest_ksp2) of the same output on the 256-source fixture.
+    Written by the staged-graph kernel (the default here) and by ksp2_kernel
+    (SPF_KSP2_HBM): spf_ksp2_digest reads whatever the plan's kernel wrote."""
     import sys
+
+    if hbm:
+        monkeypatch.setenv("SPF_KSP2_HBM", hbm)
+    else:
+        monkeypatch.delenv("SPF_KSP2_HBM", raising=False)
 
     from openr_amd.hiprt import DeviceArray
 
@@ -185,6 +194,8 @@ def test_ksp2_wan2k_every_source_engine_digest_matches_oracle():
     n = len(names)
     with _engine(csr) as eng:
         p = eng.ksp2_plan(srcs)
+        print(f"ksp2 plan: {p.info()}")
+        assert p.info().kind in kinds
         pairs = DeviceArray(len(srcs) * n * 4, np.uint32)
         cnt = DeviceArray(4, np.uint64, zero=True)
         words = 1 << 20

@@ -18,11 +18,10 @@ k = 2 SPF count must match, and sampled pairs must match the oracle.
 import numpy as np
 import pytest
 
-from helpers import link_key
+from helpers import link_key, run_plan
 from oracle import OracleLinkState
 from openr_amd import topology as T
-from openr_amd.engine import PAIR_DTYPE, Ksp2Result, SpfEngine
-from openr_amd.hiprt import DeviceArray
+from openr_amd.engine import SpfEngine
 from openr_amd.link_state import LinkState
 
 pytestmark = pytest.mark.gpu
@@ -34,33 +33,6 @@ CASES = [
      {"SPF_KSP2_DELTA": "4294967295"}, False),
     ("wan2000", lambda: T.wan(2000, 1000, seed=1), {}, False),
 ]
-
-
-def run_plan(eng, srcs, n):
-    p = eng.ksp2_plan(srcs)
-    pairs = DeviceArray(len(srcs) * n * 4, np.uint32)
-    cnt = DeviceArray(4, np.uint64, zero=True)
-    words = len(srcs) * n * 24 + (1 << 22)
-    pool = DeviceArray(words, np.uint32)
-    try:
-        p.execute(pairs.ptr, pool.ptr, words, cnt.ptr)
-        eng.check()
-        c = cnt.numpy().astype(np.int64)
-        if c[0] > words:  # size the pool from the counter and run again
-            pool.free()
-            words = int(c[0]) + int(c[0]) // 4 + (1 << 20)  # grab slack varies run to run
-            pool = DeviceArray(words, np.uint32)
-            p.execute(pairs.ptr, pool.ptr, words, cnt.ptr)
-            eng.check()
-            c = cnt.numpy().astype(np.int64)
-        assert c[0] <= words and not (c[2] & 3), c
-        res = Ksp2Result(np.asarray(srcs, np.uint32), n,
-                         pairs.numpy().view(PAIR_DTYPE).copy(), pool.numpy()[: c[0]].copy())
-        return res, c
-    finally:
-        p.close()
-        for b in (pairs, cnt, pool):
-            b.free()
 
 
 @pytest.mark.parametrize("name,make,env,expect_redo", CASES, ids=[c[0] for c in CASES])

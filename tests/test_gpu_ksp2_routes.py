@@ -104,9 +104,10 @@ def flat_sets(sets, prepends, id_of):
     return np.array(ptr, np.uint32), np.array(nodes, np.uint32), (pre if prepends else None)
 
 
-def product(lsdb, sets, prepends=None, me_names=None):
+def product(lsdb, sets, prepends=None, me_names=None, kinds=None):
     """{(me, p): rows in rec order}, rows = (ifName, metric, neighbour, action,
-    labels), and the call's totals."""
+    labels), and the call's totals.  `kinds`: the KSP2 plan kinds
+    (Ksp2Plan.info().kind) the paths may come from."""
     with LinkState(device=0) as ls:
         ls.updateAdjacencyDatabases(lsdb)
         names, _rp, col, _met, lid, _ovl = ls.flatten()
@@ -114,6 +115,9 @@ def product(lsdb, sets, prepends=None, me_names=None):
         me_names = list(names) if me_names is None else me_names
         set_ptr, set_nodes, pre = flat_sets(sets, prepends, id_of)
         totals = ls.allSourcesKsp2Routes(set_ptr, set_nodes, pre, [id_of[m] for m in me_names])
+        info = ls._k2r[0].plan.info()
+        print(f"ksp2 plan: {info}")
+        assert kinds is None or info.kind in kinds, (info, kinds)
         got, hops, words = {}, 0, 0
         for t, me in enumerate(me_names):
             rptr, rec, lptr, lab = ls.allSourcesKsp2RouteDb(t)
@@ -159,12 +163,12 @@ def names_of(lsdb):
         return list(ls.flatten()[0])
 
 
-def check(lsdb, sets, prepends=None, me_names=None):
+def check(lsdb, sets, prepends=None, me_names=None, kinds=None):
     """Every route of every me equals the oracle's; no duplicates in a route.
     Returns (got, want)."""
     me_names = names_of(lsdb) if me_names is None else me_names
     want = oracle_rows(lsdb, sets, prepends, me_names)
-    got, _ = product(lsdb, sets, prepends, me_names)
+    got, _ = product(lsdb, sets, prepends, me_names, kinds)
     assert set(got) == set(want)
     for k, rows in got.items():
         assert len(rows) == len(set(rows)), (k, rows)
@@ -295,9 +299,19 @@ def random_case():
     return topo.lsdb, dict(zip(topo.nodes, lab.tolist())), sets, pre
 
 
-def test_random_multigraph():
+# the paths the routes are built from: written by the staged-graph kernel (the
+# default on this graph) or by ksp2_kernel (SPF_KSP2_HBM)
+KSP2_KERNELS = [("staged", None, ("LDS_U16", "LDS_U32")), ("hbm", "1", ("HBM",))]
+
+
+@pytest.mark.parametrize("hbm,kinds", [k[1:] for k in KSP2_KERNELS], ids=[k[0] for k in KSP2_KERNELS])
+def test_random_multigraph(hbm, kinds, monkeypatch):
+    if hbm:
+        monkeypatch.setenv("SPF_KSP2_HBM", hbm)
+    else:
+        monkeypatch.delenv("SPF_KSP2_HBM", raising=False)
     lsdb, _label_of, sets, pre = random_case()
-    got, _ = check(lsdb, sets, pre)
+    got, _ = check(lsdb, sets, pre, kinds=kinds)
     assert sum(len(r) for r in got.values()) > 2 * len(got)  # (most routes have k = 2 paths too)
 
 
