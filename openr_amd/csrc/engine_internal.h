@@ -1,9 +1,10 @@
 // ============================================================================
 //  engine_internal.h -- state shared by the engine's translation units: the
 //  context (the graph's host state of graph_host.h plus its device copy and
-//  the kernels' scratch), the plans, and the launch functions each unit offers
-//  the others (graph.cpp: the spf_graph_* calls; spf_engine.hip: SPF/ECMP
-//  plans; ksp2.hip: batched KSP2; ...).  Not part of the C-ABI:
+//  the kernels' scratch), the plans (their host tables derived by
+//  plan_host.h), and the launch functions each unit offers the others
+//  (graph.cpp: the spf_graph_* calls; spf_engine.hip: SPF/ECMP plans;
+//  ksp2.hip: batched KSP2; ...).  Not part of the C-ABI:
 //  include/openr_spf.h is the boundary.
 // ============================================================================
 #pragma once
@@ -19,6 +20,7 @@
 
 #include "graph_host.h"
 #include "openr_spf.h"
+#include "plan_host.h"
 
 namespace spfi {
 
@@ -162,20 +164,8 @@ struct spf_ctx : spfi::GraphHost {
   spfi::DevBuf<unsigned long long> d_pred_key;
   spfi::DevBuf<uint32_t> d_gq, d_gq2, d_gbm, d_gctr;  // global-memory SSSP scratch
   spfi::DevBuf<uint32_t> d_gbar;  // its grid-barrier counters (whatif.hip XGrid)
-  // per-node eccentricity estimates (planes BFS batch order), for ecc_epoch
-  std::vector<uint32_t> ecc;
-  uint64_t ecc_epoch = ~0ull;
-  uint32_t dbound = 0;  // hop-distance upper bound (depth_bound), for dbound_epoch
-  // recent bounds by (sliced-ELL structure version, drain bits): a drain bit
-  // toggled back and forth (the BM_DecisionFabric publication) or a metric
-  // patch (the bound counts hops) finds its bound again without a BFS
-  struct DboundMemo {
-    uint64_t sell_ver;
-    std::vector<uint8_t> ovl;
-    uint32_t dbound;
-  };
-  std::vector<DboundMemo> dbound_memo;
-  uint64_t dbound_epoch = ~0ull;
+  // ecc_estimate's and depth_bound's memory of the graph (plan_host.h)
+  spfi::DepthCache depth;
   // mssp_kernel tables (mssp.hip), valid for graph epoch mp_epoch
   spfi::DevBuf<uint32_t> d_mp_ell, d_mp_smap;
   spfi::DevBuf<uint32_t> d_mp_dep;  // per slice: the slices its nodes' out-edges reach (CSR)

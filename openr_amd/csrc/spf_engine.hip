@@ -934,7 +934,6 @@ __global__ __launch_bounds__(kMsThreads) void msbfs_planes_kernel(
 constexpr int kEcmpUnroll = 4;         // neighbour rows per group (two groups in flight)
 constexpr uint32_t kEcmpChunk = 1024;  // destinations per wave
 constexpr uint32_t kEcmpWaves = kEcmpThreads / 64;
-constexpr uint32_t kEcmpRunsPerXcd = 64;  // source runs dealt to each XCD
 
 // Zero-byte flags of x at bit 7 of each byte (exact: no carries cross bytes).
 __device__ __forceinline__ uint32_t zero_bytes(uint32_t x) {
@@ -1174,8 +1173,7 @@ __global__ __launch_bounds__(kEcmpThreads) void ecmp_kernel(
 // v / 32 of bitmap j).  When maxd reaches the u8 copy's saturation (254)
 // the planes stay unwritten and the pass decides on the u32 rows.
 constexpr uint32_t kSlChunk = 2048;  // destinations per pass of a wave: one word per lane
-constexpr uint32_t kSlSlots = 8;     // plane slots per word of a sliced row
-constexpr uint32_t kSlSat = 254;     // maxd at which the u8 copy saturates
+// (kSlSlots plane slots per word of a sliced row, kSlSat: plan_host.h)
 
 // Sliced row r starts at S + r * kSlSlots * wpm; word w's P planes sit at
 // w * P .. w * P + P - 1, so a lane's planes are one P-dword load and a
@@ -1368,8 +1366,7 @@ __device__ __forceinline__ void sliced_pass(__amdgpu_buffer_rsrc_t rs, __amdgpu_
 // stay in registers and every neighbour row is loaded once for all of them
 // (the per-source pass loads it once per source -- the next-hop pass is
 // bound by those L2 reads).  gs <= kSlGroup sources; lane = output word w.
-constexpr uint32_t kSlGroup = 8;
-constexpr uint32_t kSlSeg = 4;  // neighbour positions per grouping segment (one uint4 of row offsets)
+// (kSlGroup, kSlSeg: plan_host.h, with plan_sliced_units, which forms the groups)
 template <int P>
 __device__ __forceinline__ void grouped_pass(__amdgpu_buffer_rsrc_t rs, uint32_t* __restrict__ nh,
                                              const uint64_t* __restrict__ nh_off,
@@ -1455,7 +1452,7 @@ __device__ __forceinline__ void grouped_pass(__amdgpu_buffer_rsrc_t rs, uint32_t
 // changed nothing (r02_v22).
 // neighbour-chunk matches per unit (at most, about): fabric_full's pass 68.5
 // us at 128, 66 at 512, 72 at 1024, 92 at 2048 (gpurun_out/r04_s1, r04_s2)
-constexpr uint32_t kSlUnit = 512;
+// (the figure is kSlUnit, plan_host.h)
 
 __global__ __launch_bounds__(kEcmpThreads) void ecmp_sliced_kernel(
     const uint32_t* __restrict__ S, const uint32_t* __restrict__ maxd,
@@ -1711,11 +1708,9 @@ __global__ void preds_kernel(const uint32_t* __restrict__ dist0,  // [n_src][pit
 }
 
 // ---------------------------------------------------------------------------
-//  host side
+//  host side: LDS sizes and batch sizes (still beside the kernels), what the
+//  other units call (spfi), the launches and build_plan, then the C-ABI
 // ---------------------------------------------------------------------------
-}  // namespace
-
-namespace {
 
 size_t sssp_lds_bytes(uint32_t N, uint32_t pitch, uint32_t big, bool q16) {
   const uint32_t bm_words = (N + 31) / 32;
@@ -1724,782 +1719,80 @@ size_t sssp_lds_bytes(uint32_t N, uint32_t pitch, uint32_t big, bool q16) {
   return (b + 15) & ~size_t(15);
 }
 
-uint32_t ms_batch(const spf_ctx* c, uint32_t rows);
-
-}  // namespace
-
-extern "C" {
-
-const char* spf_global_error(void) { return g_err.c_str(); }
-const char* spf_last_error(const spf_ctx* c) { return c ? c->err.c_str() : g_err.c_str(); }
-uint64_t spf_solves(const spf_ctx* c) { return c ? c->solves : 0; }
-uint32_t spf_row_pitch(const spf_ctx* c) { return c ? c->pitch : 0; }
-int spf_graph_has_nonpositive_metric(const spf_ctx* c) { return c && c->nonpos; }
-int spf_graph_needs_dist64(const spf_ctx* c) { return c && c->needs64; }
-
-spf_status spf_ctx_create(int device, spf_ctx** out) {
-  if (!out) return fail(nullptr, SPF_E_INVALID, "spf_ctx_create: out is NULL");
-  *out = nullptr;
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
-    return fail(nullptr, SPF_E_NO_DEVICE, "no HIP device visible");
-  if (device < 0 || device >= n)
-    return fail(nullptr, SPF_E_NO_DEVICE, "device %d out of range (%d visible)", device, n);
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) != hipSuccess)
-    return fail(nullptr, SPF_E_NO_DEVICE, "hipGetDeviceProperties failed");
-  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(nullptr, SPF_E_NO_DEVICE, "device %d is %s, engine is built for gfx950",
-                device, prop.gcnArchName);
-  auto c = std::make_unique<spf_ctx>();
-  c->device = device;
-  c->n_cu = (uint32_t)std::max(1, prop.multiProcessorCount);
-  if (hipSetDevice(device) != hipSuccess)
-    return fail(nullptr, SPF_E_HIP, "hipSetDevice(%d) failed", device);
-  // a BLOCKING stream: work enqueued with stream = NULL ("the context's
-  // stream") is ordered after earlier work on the legacy null stream, so a
-  // caller's hipMemset / hipMemcpy on the null stream before an execute is
-  // seen by it (round 3 lost a plan's first bitmaps to exactly that race
-  // with a non-blocking stream)
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamDefault) != hipSuccess)
-    return fail(nullptr, SPF_E_HIP, "hipStreamCreate failed");
-  if (c->d_fault.alloc(1) != hipSuccess || hipMemset(c->d_fault.p, 0, 4) != hipSuccess)
-    return fail(nullptr, SPF_E_HIP, "fault word allocation failed");
-  *out = c.release();
-  return SPF_OK;
+size_t msbfs_lds_bytes(uint32_t N, bool db = false) {
+  return 8ull * (N + 1) * (db ? 2 : 1) + 4ull * (4 * kMsBatch + 5);
 }
 
-void spf_ctx_destroy(spf_ctx* c) {
-  if (!c) return;
-  (void)hipSetDevice(c->device);
-  spfi::resident_forget(c);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  spf_plan_destroy(c->rt.plan);  // spf_routes' cached plan, before its context goes
-  c->rt.plan = nullptr;
-  if (c->stream) {
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipStreamDestroy(c->stream);
-  }
-  if (c->side) {
-    (void)hipStreamSynchronize(c->side);
-    (void)hipStreamDestroy(c->side);
-  }
-  if (c->side_fork) (void)hipEventDestroy(c->side_fork);
-  if (c->side_join) (void)hipEventDestroy(c->side_join);
-  delete c;
+// msbfs_kernel with a double-buffered frontier: when the columns do not fit
+// in LDS beside one F array but two F arrays do (SPF_MSBFS_DB=0: single, A/B)
+bool ms_double_buffer(const spf_ctx* c) {
+  const char* e = std::getenv("SPF_MSBFS_DB");
+  if (e && e[0] == '0') return false;
+  const size_t n_col = c->sell_ptr.back();
+  return msbfs_lds_bytes(c->N) + 2ull * n_col > kMaxLds && msbfs_lds_bytes(c->N, true) <= kMaxLds;
 }
 
-spf_status spf_src_neighbors(const spf_ctx* c, uint32_t src, uint32_t* out,
-                             uint32_t cap, uint32_t* count) {
-  if (!c || !c->loaded) return SPF_E_STATE;
-  if (src >= c->N) return SPF_E_INVALID;
-  const uint32_t b = c->nb_ptr[src], k = c->nb_ptr[src + 1] - b;
-  if (count) *count = k;
-  for (uint32_t i = 0; i < k && i < cap && out; ++i) out[i] = c->nb_id[b + i];
-  return SPF_OK;
+// LDS of msbfs_kernel's quotient variant: CF and QA (two buffers each), the
+// row/column tables, the small arrays, the source marks
+size_t msbfs_q_lds_bytes(uint32_t N, uint32_t n_cls, uint32_t n_vrow) {
+  const size_t nvp = (n_vrow + 7u) & ~7u;
+  return 32ull * (n_cls + 1) + 2ull * (1 + kQChunk) * nvp + 4ull * (4 * kMsBatch + 5) + ((N + 3u) & ~3u);
 }
 
-}  // extern "C"
-
-namespace {
-
-// Eccentricity estimate of every node (hop counts, drains ignored): the
-// largest BFS distance from a few landmarks -- the node farthest from node
-// 0, then repeatedly the node farthest from every landmark so far (on a grid:
-// the corners, which makes it exact).  Cached per graph epoch.
-const std::vector<uint32_t>& ecc_estimate(spf_ctx* c) {
-  if (c->ecc_epoch == c->epoch && c->ecc.size() == c->N) return c->ecc;
-  const uint32_t N = c->N;
-  std::vector<uint32_t> d(N), mind(N, kInf), q;
-  c->ecc.assign(N, 0);
-  auto bfs = [&](uint32_t r) {
-    std::fill(d.begin(), d.end(), kInf);
-    d[r] = 0;
-    q.assign(1, r);
-    for (size_t h = 0; h < q.size(); ++h) {
-      const uint32_t u = q[h];
-      for (uint32_t e = c->row_ptr[u]; e < c->row_ptr[u + 1]; ++e)
-        if (d[c->col[e]] == kInf) {
-          d[c->col[e]] = d[u] + 1;
-          q.push_back(c->col[e]);
-        }
-    }
-  };
-  uint32_t land = 0;
-  for (int j = 0; j < 9 && N; ++j) {
-    bfs(land);
-    uint32_t far = land, best = 0;
-    for (uint32_t v = 0; v < N; ++v) {
-      if (d[v] == kInf) continue;
-      if (j > 0) c->ecc[v] = std::max(c->ecc[v], d[v]);  // landmark 0 (node 0's far end) onwards
-      mind[v] = std::min(mind[v], d[v]);
-      if (j == 0 ? d[v] > best : mind[v] > best) {
-        best = j == 0 ? d[v] : mind[v];
-        far = v;
-      }
-    }
-    if (j == 0) std::fill(mind.begin(), mind.end(), kInf);  // node 0 is no landmark
-    land = far;
-  }
-  c->ecc_epoch = c->epoch;
-  return c->ecc;
+// The quotient sweep is taken when it reads at most half the columns of the
+// plain one (a grid or a ring has no twins: every node its own class) and its
+// tables fit in LDS.  SPF_QUOTIENT=0 keeps the plain sweep (A/B, parity tests).
+bool quotient_allowed(const spf_ctx* c) {
+  if (c->N > kMsMaxNodes || ms_own(c->N) > (uint32_t)kQMaxOwn) return false;
+  const char* e = std::getenv("SPF_QUOTIENT");
+  return !(e && e[0] == '0');
 }
 
-// An upper bound on every hop distance of the graph (any source, drained
-// nodes expanded only as the source, LinkState.cpp:831-838): paths run
-// s -> x -> ... -> y -> v with x .. y in H = the non-drained nodes, so
-// d(s, v) <= 2 + d_H(x, y) <= 2 + 2 ecc_H(r) for any r of x's component of
-// H.  One BFS in H per component.  Plans whose rows cannot saturate the u8
-// copy (bound < 254) never need u32 rows of non-source closure rows.
-uint32_t depth_bound(spf_ctx* c) {
-  if (c->dbound_epoch == c->epoch) return c->dbound;
-  for (const auto& m : c->dbound_memo)  // the same structure and drain bits as a recent epoch
-    if (m.sell_ver == c->sell_ver && m.ovl == c->ovl) {
-      c->dbound = m.dbound;
-      c->dbound_epoch = c->epoch;
-      return c->dbound;
-    }
-  // one level-synchronous BFS per component over the distinct up neighbours;
-  // drained nodes are neither roots nor transit, so they start out seen (one
-  // byte test per edge -- recomputed after every patch, on the path of the
-  // first plan build of a publication)
-  const uint32_t N = c->N;
-  std::vector<uint8_t> seen(N);
-  for (uint32_t v = 0; v < N; ++v) seen[v] = c->ovl[v] != 0;
-  std::vector<uint32_t> q(std::max<uint32_t>(N, 1));
-  const uint32_t* nbp = c->nb_ptr.data();
-  const uint32_t* nbi = c->nb_id.data();
-  uint32_t worst = 0;
-  for (uint32_t r = 0; r < N; ++r) {
-    if (seen[r]) continue;
-    seen[r] = 1;
-    size_t head = 0, tail = 0, level_end = 1;
-    q[tail++] = r;
-    uint32_t ecc = 0;
-    while (head < tail) {
-      const uint32_t u = q[head++];
-      for (uint32_t e = nbp[u]; e < nbp[u + 1]; ++e) {
-        const uint32_t x = nbi[e];
-        if (!seen[x]) {
-          seen[x] = 1;
-          q[tail++] = x;
-        }
-      }
-      if (head == level_end && head < tail) {  // the next level starts
-        ++ecc;
-        level_end = tail;
-      }
-    }
-    worst = std::max(worst, ecc);
-  }
-  c->dbound = 2 + 2 * worst;
-  c->dbound_epoch = c->epoch;
-  if (c->dbound_memo.size() >= 4) c->dbound_memo.erase(c->dbound_memo.begin());
-  c->dbound_memo.push_back({c->sell_ver, c->ovl, c->dbound});
-  return c->dbound;
+// Sources per workgroup that spread `rows` over every CU: the fewest rounds
+// of `full`-source workgroups the chip needs, then those rounds filled evenly
+// (a batch costs one edge sweep per level whatever its size, but its stores
+// scale with it).
+uint32_t spread_batch(const spf_ctx* c, uint32_t rows, uint32_t full) {
+  const uint32_t rounds = (rows + full * c->n_cu - 1) / (full * c->n_cu);
+  return std::min<uint32_t>(full, (rows + rounds * c->n_cu - 1) / (rounds * c->n_cu));
 }
 
-// u8 narrow rows for the next-hop pass: 4x fewer bytes per neighbour row
-// read, paid for by a second store per (source, slice, level) in
-// msbfs_kernel.  Worth it when next-hop work (sum of neighbour counts)
-// outweighs the BFS store work, which grows with the number of levels:
-// dense fabrics (degree ~23, 5 levels) yes; always with the register-plane
-// BFS (one coalesced store per row).  SPF_NARROW=0/1 overrides (experiments).
-bool use_narrow(const spf_ctx* c, const spf_plan* p) {
-  if (const char* e = std::getenv("SPF_NARROW")) return e[0] != '0';
-  // the register-plane BFS writes each row once, coalesced: the u8 copy
-  // costs one more row store and the next-hop pass reads 4x fewer bytes
-  if (use_planes(c)) return true;
-  uint64_t nb = 0;
-  for (uint32_t i = 0; i < p->n_src; ++i) nb += p->words[i];
-  return nb >= 8ull * p->n_src;  // average distinct degree >= 8
+// msbfs_kernel's sources per workgroup.  knob: SPF_MSBFS_BATCH=1..64 fixes it
+// (tests: full batches on graphs too small to fill the chip with them).
+uint32_t ms_batch(const spf_ctx* c, uint32_t rows, bool knob = true) {
+  if (const char* e = knob ? std::getenv("SPF_MSBFS_BATCH") : nullptr) {
+    const int b = atoi(e);
+    if (b >= 1 && b <= (int)kMsBatch) return (uint32_t)b;
+  }
+  return spread_batch(c, rows, kMsBatch);
 }
 
-// Everything a plan derives from the graph's current state (closure over
-// non-drained neighbours, narrow/exact mode, next-hop row tables).  Run at
-// creation and again by spf_plan_execute after an in-place graph patch
-// (spf_graph_set_overload / spf_graph_set_metric); the output layout
-// (nh_off, words) depends only on the CSR structure, which patches keep.
-spf_status build_plan(spf_ctx* c, spf_plan* p) {
-  // SPF_PLAN_DEBUG: per-phase host time of the build on stderr (diagnostics)
-  static const bool pd_on = std::getenv("SPF_PLAN_DEBUG") != nullptr;
-  auto pd_t0 = std::chrono::steady_clock::now();
-  auto PD = [&](const char* what) {
-    if (!pd_on) return;
-    (void)hipStreamSynchronize(c->stream);
-    const auto t = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "build_plan %s %.1f us\n", what, std::chrono::duration<double, std::micro>(t - pd_t0).count());
-    pd_t0 = t;
-  };
-  const uint32_t n_src = p->n_src;
-  const uint32_t* srcs = p->srcs.data();
-  const bool hop = (p->flags & SPF_FLAG_HOP_COUNT) != 0;
-  const bool d64 = (p->flags & SPF_FLAG_DIST64) != 0;
-  if (!hop && c->needs64 && !d64)
-    return fail(c, SPF_E_UNSUPPORTED,
-                "weighted distances of this graph may exceed 32 bits (negative metric or max "
-                "metric x hops >= 2^32): create the plan with SPF_FLAG_DIST64");
-  const uint32_t N = c->N;
-  // the exact kernel replays runSpf step for step: zero-metric plateaus
-  // (pop order), u64 labels, and graphs whose distance rows do not fit the
-  // LDS-resident kernels
-  const bool ms_ok = (hop || c->unit) && N <= kMsMaxNodes;
-  const bool lds_ok = sssp_lds_bytes(N, c->pitch, c->big_nodes, N <= 65535) <= kMaxLds;
-  p->exact = d64 || (!hop && c->nonpos);
-  // graphs beyond the LDS-resident kernels: the whole chip per source
-  // (spf_big_kernel); SPF_BIG=0 sends them to the exact kernel, SPF_BIG=1
-  // sends every plan it can take there (tests)
-  const char* be = std::getenv("SPF_BIG");
-  p->big = !p->exact && ((!ms_ok && !lds_ok) ? !(be && be[0] == '0') : (be && be[0] == '1'));
-  if (!ms_ok && !lds_ok && !p->big) p->exact = true;
-  if (p->exact || p->big) {
-    p->closure = p->srcs;
-    p->direct = true;
-    p->ms = false;
-    p->narrow = false;
-    p->sliced = false;
-    p->expand = false;
-    p->nh_off.resize(n_src);
-    p->words.resize(n_src);
-    uint64_t off = 0;
-    p->wmax = 1;
-    for (uint32_t i = 0; i < n_src; ++i) {
-      const uint32_t k = c->nb_ptr[srcs[i] + 1] - c->nb_ptr[srcs[i]];
-      p->words[i] = k;
-      p->nh_off[i] = off;
-      off += (uint64_t)k * (c->pitch / 32);
-      p->wmax = std::max(p->wmax, (k + 31) / 32);
-    }
-    p->nh_total = off;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (p->exact) {
-      const spf_status st = exact_reserve(c, &p->xs, n_src, p->wmax);
-      if (st != SPF_OK) return st;
-    }
-    HIP_TRY(c, stage_upload(c, p->d_srcs, p->srcs.data(), n_src));
-    HIP_TRY(c, stage_upload(c, p->d_nh_off, p->nh_off.data(), n_src));
-    HIP_TRY(c, stage_upload(c, p->d_words, p->words.data(), n_src));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    stage_done(c);
-    p->epoch = c->epoch;
-    return SPF_OK;
-  }
-  PD("start");
-  p->closure.clear();
-  std::vector<uint32_t> row_of(N, kInf);
-  bool distinct = true;
-  for (uint32_t i = 0; i < n_src; ++i) {
-    if (row_of[srcs[i]] != kInf) distinct = false;
-    else row_of[srcs[i]] = i;
-  }
-  // closure: every non-overloaded neighbour's distance row is needed
-  bool closed = distinct;
-  if (closed) {
-    for (uint32_t i = 0; i < n_src && closed; ++i) {
-      const uint32_t s = srcs[i];
-      for (uint32_t j = c->nb_ptr[s]; j < c->nb_ptr[s + 1]; ++j) {
-        const uint32_t x = c->nb_id[j];
-        if (!c->ovl[x] && row_of[x] == kInf) {
-          closed = false;
-          break;
-        }
-      }
-    }
-  }
-  p->direct = closed;
-  if (closed) {
-    p->closure = p->srcs;
-  } else {
-    std::fill(row_of.begin(), row_of.end(), kInf);
-    auto add = [&](uint32_t x) {
-      if (row_of[x] == kInf) {
-        row_of[x] = (uint32_t)p->closure.size();
-        p->closure.push_back(x);
-      }
-    };
-    // distinct sources first (rows 0 .. n_src - 1 are the request's rows:
-    // kernels that can write a row prefix straight into the caller's buffer
-    // do, msbfs_team_kernel), then the neighbours the next-hop pass reads
-    if (distinct)
-      for (uint32_t i = 0; i < n_src; ++i) add(srcs[i]);
-    for (uint32_t i = 0; i < n_src; ++i) {
-      const uint32_t s = srcs[i];
-      add(s);
-      for (uint32_t j = c->nb_ptr[s]; j < c->nb_ptr[s + 1]; ++j)
-        if (!c->ovl[c->nb_id[j]]) add(c->nb_id[j]);
-    }
-  }
-  // closure[i] == srcs[i] for i < n_src, and no row can saturate the u8
-  // copy (whose saturated entries the next-hop pass reads from u32 rows)
-  p->prefix = distinct && depth_bound(c) < kSlSat;
-  std::vector<uint32_t> req_rows(n_src);
-  for (uint32_t i = 0; i < n_src; ++i) req_rows[i] = row_of[srcs[i]];
-  // next-hop layout
-  p->nh_off.resize(n_src);
-  p->words.resize(n_src);
-  uint64_t off = 0;
-  for (uint32_t i = 0; i < n_src; ++i) {
-    const uint32_t k = c->nb_ptr[srcs[i] + 1] - c->nb_ptr[srcs[i]];
-    p->words[i] = k;  // one destination bitmap per distinct up neighbour
-    p->nh_off[i] = off;
-    off += (uint64_t)k * (c->pitch / 32);
-  }
-  p->nh_total = off;
-  p->q16 = N <= 65535;
-  p->lds_bytes = sssp_lds_bytes(N, c->pitch, c->big_nodes, p->q16);
-  HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, stage_upload(c, p->d_srcs, p->srcs.data(), n_src));
-  HIP_TRY(c, stage_upload(c, p->d_closure, p->closure.data(), p->closure.size()));
-  HIP_TRY(c, stage_upload(c, p->d_row_of, row_of.data(), N));
-  HIP_TRY(c, stage_upload(c, p->d_req_rows, req_rows.data(), n_src));
-  HIP_TRY(c, stage_upload(c, p->d_nh_off, p->nh_off.data(), n_src));
-  HIP_TRY(c, stage_upload(c, p->d_words, p->words.data(), n_src));
-  p->ms = (hop || c->unit) && N <= kMsMaxNodes;
-  // register-plane BFS: batches of similar depth, deepest first (more than
-  // one round of batches only; SPF_PL_ORDER=0 keeps the plan order, A/B)
-  p->pl_order = false;
-  if (p->ms && use_planes(c) && p->closure.size() > (size_t)kPlBatch * c->n_cu) {
-    const char* e = std::getenv("SPF_PL_ORDER");
-    if (!(e && e[0] == '0')) {
-      const std::vector<uint32_t>& ecc = ecc_estimate(c);
-      std::vector<uint32_t> order(p->closure.size());
-      std::iota(order.begin(), order.end(), 0u);
-      std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-        return ecc[p->closure[a]] > ecc[p->closure[b]];
-      });
-      HIP_TRY(c, stage_upload(c, p->d_pl_order, order.data(), order.size()));
-      p->pl_order = true;
-    }
-  }
-  // few batches (a rank's share of a multi-GPU pass): teams of workgroups
-  // per batch (msbfs_team.hip) instead of one workgroup sweeping everything
-  PD("uploads1");
-  p->tm_G = 0;
-  if (p->ms && !use_planes(c) && !p->expand && !c->team_off) {
-    const uint32_t G = msbfs_team_size(c, (uint32_t)p->closure.size());
-    if (G) {
-      const spf_status st = msbfs_team_prepare(c, p, G);
-      if (st != SPF_OK) return st;
-    }
-  }
-  // weighted: S sources per workgroup on mssp_kernel where it applies
-  PD("team");
-  p->mp = !p->ms && !hop && mssp_words(c) > 0;
-  if (p->mp) {
-    const spf_status st = mssp_prepare(c);
-    if (st != SPF_OK) return st;
-    HIP_TRY(c, p->d_redo.alloc(1 + p->closure.size()));
-  }
-  // weighted plans keep a u8 copy too when the pitches agree (the sssp
-  // kernel writes it beside the u32 row; the next-hop pass compares bytes and
-  // falls back to u32 rows per wave where the source's row saturates)
-  p->narrow = (p->ms || c->pitch == c->npitch) && use_narrow(c, p);
-  // bit-sliced rows behind the per-level-store BFS (it reports the deepest
-  // level); the register-plane BFS serves deep graphs, where planes would
-  // not pay.  SPF_NARROW=1 keeps the byte-row pass (experiments, tests).
-  {
-    const char* e = std::getenv("SPF_NARROW");
-    p->sliced = p->ms && p->narrow && !use_planes(c) && !(e && e[0] == '1');
-    // weighted plans on mssp_kernel: its u8 rows sliced too, next hops by
-    // bit-sliced sums d_x + w (sliced_pass<P, true>); SPF_WSLICED=0: byte rows
-    const char* ws = std::getenv("SPF_WSLICED");
-    if (p->mp && p->narrow && !(e && e[0] == '1') && !(ws && ws[0] == '0')) p->sliced = true;
-    // SPF_EXPAND=1 (A/B; measured slower): the BFS stores the u8
-    // rows only and the slicing pass expands them into the u32 rows.  By
-    // default the BFS stores both: its u32 stores drain behind its
-    // latency-bound sweeps (+0.06 ms on fabric_full) where a separate
-    // streaming pass costs 0.14 ms and a fused one 0.14 ms of the next-hop
-    // kernel's time (r02_v25/r02_v26)
-    const char* x = std::getenv("SPF_EXPAND");
-    p->expand = p->sliced && c->pitch <= c->npitch && x && x[0] == '1';
-    // team plans whose depth stays below the planes' all-ones code write the
-    // sliced rows themselves: no u8 rows, no slicing pass (SPF_SDIRECT=0: A/B)
-    const char* sd = std::getenv("SPF_SDIRECT");
-    p->sdirect = p->sliced && p->nh_total && p->tm_G && p->prefix && !p->expand &&
-                 depth_bound(c) < (1u << kTeamPlanes) - 1 && !(sd && sd[0] == '0');
-  }
-  const uint32_t wpm = c->pitch / 32;
-  const uint64_t rstride = (uint64_t)kSlSlots * wpm;  // sliced row: words
-  {
-    // per-source neighbour rows for the next-hop pass (kInf = drained)
-    std::vector<uint32_t> nb_row, nb_row_off(n_src), nb_drained(n_src, 0);
-    const uint32_t dead = p->sliced   ? (uint32_t)(p->closure.size() * rstride)
-                          : p->narrow ? (uint32_t)p->closure.size() * c->npitch
-                                      : kInf;
-    p->dead = dead;
-    for (uint32_t i = 0; i < n_src; ++i) {
-      nb_row_off[i] = (uint32_t)nb_row.size();
-      for (uint32_t e = c->nb_ptr[srcs[i]]; e < c->nb_ptr[srcs[i] + 1]; ++e) {
-        const uint32_t x = c->nb_id[e];
-        const bool dr = c->ovl[x] != 0;
-        nb_row.push_back(dr          ? dead
-                         : p->sliced ? (uint32_t)(row_of[x] * rstride)
-                         : p->narrow ? row_of[x] * c->npitch
-                                     : row_of[x]);
-        nb_drained[i] += dr;
-      }
-      const size_t k = nb_row.size() - nb_row_off[i];
-      nb_row.resize(nb_row_off[i] + (k + 7) / 8 * 8 + 8, dead);
-    }
-    HIP_TRY(c, stage_upload(c, p->d_nb_row, nb_row.data(), nb_row.size()));
-    HIP_TRY(c, stage_upload(c, p->d_nb_row_off, nb_row_off.data(), n_src));
-    HIP_TRY(c, stage_upload(c, p->d_nb_drained, nb_drained.data(), n_src));
-    // next-hop blocks per XCD: runs of consecutive sources of about
-    // 1/(8 * runs) of the work each, every run to the XCD with the least
-    // work so far (runs come in request order: the heavy spine and fabric
-    // switches first)
-    // (a rank's share of a multi-GPU pass -- ~1.3k sources -- does best with
-    // two long runs per XCD: 0.097 -> 0.095 ms per world-8 rank, r03_v25)
-    const char* env = std::getenv("SPF_ECMP_RUNS");
-    const uint32_t runs = env ? (uint32_t)atoi(env) : n_src >= 4096 ? kEcmpRunsPerXcd : 2u;
-    std::vector<uint32_t> lists[8];
-    if (runs == 0) {  // plain round-robin
-      for (uint32_t i = 0; i < n_src; ++i) lists[i % 8].push_back(i);
-    } else {
-      uint64_t total = 0, load[8] = {};
-      for (uint32_t i = 0; i < n_src; ++i) total += p->words[i] + 1;
-      const uint64_t target = std::max<uint64_t>(1, total / (8ull * runs));
-      for (uint32_t i = 0; i < n_src;) {
-        uint32_t e = i;
-        uint64_t w = 0;
-        while (e < n_src && w < target) w += p->words[e++] + 1;
-        const int g = (int)(std::min_element(load, load + 8) - load);
-        load[g] += w;
-        for (uint32_t t = i; t < e; ++t) lists[g].push_back(t);
-        i = e;
-      }
-    }
-    PD("nb_rows");
-    if (p->sliced) {
-      // sliced-pass work units per XCD, in the XCD's source order: a source
-      // whose neighbour-chunk matches fit kSlUnit is one unit, a heavier one
-      // is cut per chunk and per neighbour range (multiples of 8: the row
-      // offset lists are read 16-byte aligned)
-      const uint32_t chunks = (wpm + 63) / 64;
-      const char* ue = std::getenv("SPF_SLICED_UNIT");  // A/B knob
-      // small plans (a rank's share of a multi-GPU pass) get smaller units so
-      // the waves still cover the chip: about 16 units per CU, 16..kSlUnit
-      uint64_t matches = 0;
-      for (uint32_t i = 0; i < n_src; ++i) matches += (uint64_t)p->words[i] * chunks;
-      const uint32_t fill = (uint32_t)std::min<uint64_t>(
-          kSlUnit, std::max<uint64_t>(16, matches / (16ull * c->n_cu) / 8 * 8));
-      const uint32_t unit = ue ? (uint32_t)atoi(ue) : fill;
-      std::vector<uint32_t> units, unit_off(9, 0), gtab;
-      // Grouped units: neighbour positions are cut into segments of kSlSeg;
-      // sources of one XCD list whose segment q holds the same rows (none
-      // drained) share it -- one wave loads each of those rows once for up
-      // to kSlGroup sources.  Whole lists match for a pod's rack switches and
-      // a plane's spines; a fabric switch's list is [its plane's spines][its
-      // pod's rack switches], so the fabric switches of one plane share the
-      // first part and those of one pod the second.  Consecutive segments of
-      // one member set merge into one range; what no group takes stays with
-      // per-source units.  (SPF_SLICED_GROUP=0: no groups, =1: whole
-      // identical lists only -- round 3's rule; A/B.)
-      const char* ge = std::getenv("SPF_SLICED_GROUP");
-      // (weighted plans: no groups -- members share neighbour rows, not metrics)
-      const int gmode = p->mp ? 0 : ge ? atoi(ge) : 2;
-      p->max_xcd_units = 0;
-      for (int g = 0; g < 8; ++g) {
-        unit_off[g] = (uint32_t)(units.size() / 4);
-        // per source of the list: which segments a group took
-        std::map<uint32_t, std::vector<uint8_t>> taken;
-        // member set -> segments (q, end position) it shares
-        std::map<std::vector<uint32_t>, std::vector<std::pair<uint32_t, uint32_t>>> shared;
-        if (gmode) {
-          std::map<std::vector<uint32_t>, std::vector<uint32_t>> seg;
-          for (uint32_t i : lists[g]) {
-            const uint32_t k = p->words[i];
-            if (!k) continue;
-            const uint32_t* r = nb_row.data() + nb_row_off[i];
-            if (gmode == 1) {  // the whole list as one key
-              if (nb_drained[i]) continue;
-              std::vector<uint32_t> key{0u, k};
-              key.insert(key.end(), r, r + k);
-              seg[key].push_back(i);
-              continue;
-            }
-            for (uint32_t q = 0; q * kSlSeg < k; ++q) {
-              const uint32_t j = q * kSlSeg, e = std::min(k, j + kSlSeg);
-              bool dead_in = false;
-              for (uint32_t jj = j; jj < e; ++jj) dead_in |= r[jj] == dead;
-              if (dead_in) continue;
-              std::vector<uint32_t> key{q, e};
-              key.insert(key.end(), r + j, r + e);
-              seg[key].push_back(i);
-            }
-          }
-          for (auto& kv : seg) {
-            const auto& src = kv.second;
-            for (size_t a = 0; a + 1 < src.size(); a += kSlGroup) {
-              const size_t b = std::min(src.size(), a + kSlGroup);
-              if (b - a < 2) break;
-              std::vector<uint32_t> m(src.begin() + a, src.begin() + b);
-              const uint32_t q = kv.first[0], e = kv.first[1];
-              if (gmode == 1) {  // whole list: every segment of it
-                for (uint32_t qq = 0; qq * kSlSeg < e; ++qq)
-                  shared[m].emplace_back(qq, std::min(e, (qq + 1) * kSlSeg));
-              } else {
-                shared[m].emplace_back(q, e);
-              }
-              for (uint32_t i : m) {
-                auto& t = taken[i];
-                if (t.empty()) t.assign((p->words[i] + kSlSeg - 1) / kSlSeg, 0);
-                if (gmode == 1)
-                  std::fill(t.begin(), t.end(), 1);
-                else
-                  t[q] = 1;
-              }
-            }
-          }
-        }
-        // group units: per member set, runs of consecutive segments, per
-        // chunk, ranges of about `unit` matches (multiples of kSlSeg)
-        for (auto& kv : shared) {
-          auto& segs = kv.second;
-          std::sort(segs.begin(), segs.end());
-          const uint32_t gs = (uint32_t)kv.first.size();
-          const uint32_t goff = (uint32_t)gtab.size();
-          gtab.push_back(gs);
-          gtab.insert(gtab.end(), kv.first.begin(), kv.first.end());
-          for (size_t a = 0; a < segs.size();) {
-            size_t b = a + 1;
-            while (b < segs.size() && segs[b].first == segs[b - 1].first + 1) ++b;
-            const uint32_t j0 = segs[a].first * kSlSeg, j1 = segs[b - 1].second;
-            const uint32_t parts = (uint32_t)(((uint64_t)(j1 - j0) * gs + unit - 1) / unit);
-            const uint32_t jstep = ((j1 - j0 + parts - 1) / parts + kSlSeg - 1) / kSlSeg * kSlSeg;
-            for (uint32_t ch = 0; ch < chunks; ++ch)
-              for (uint32_t j = j0; j < j1; j += jstep)
-                units.insert(units.end(), {goff, ch | (1u << 31), j, std::min(j1, j + jstep)});
-            a = b;
-          }
-        }
-        // per-source units over what no group took
-        for (uint32_t i : lists[g]) {
-          const uint32_t k = p->words[i];
-          if (k == 0) continue;
-          const auto it = taken.find(i);
-          const std::vector<uint8_t>* t = it == taken.end() ? nullptr : &it->second;
-          for (uint32_t q = 0; q * kSlSeg < k;) {
-            if (t && (*t)[q]) {
-              ++q;
-              continue;
-            }
-            uint32_t q1 = q + 1;
-            while (q1 * kSlSeg < k && !(t && (*t)[q1])) ++q1;
-            const uint32_t j0 = q * kSlSeg, j1 = std::min(k, q1 * kSlSeg), kr = j1 - j0;
-            if ((uint64_t)kr * chunks <= unit) {
-              units.insert(units.end(), {i, 0u | (chunks << 16), j0, j1});
-            } else {  // per chunk, equal ranges of <= unit neighbours (multiples of kSlSeg)
-              const uint32_t parts = (kr + unit - 1) / unit;
-              const uint32_t jstep = ((kr + parts - 1) / parts + kSlSeg - 1) / kSlSeg * kSlSeg;
-              for (uint32_t ch = 0; ch < chunks; ++ch)
-                for (uint32_t j = j0; j < j1; j += jstep)
-                  units.insert(units.end(), {i, ch | ((ch + 1) << 16), j, std::min(j1, j + jstep)});
-            }
-            q = q1;
-          }
-        }
-        p->max_xcd_units = std::max(p->max_xcd_units, (uint32_t)(units.size() / 4) - unit_off[g]);
-      }
-      unit_off[8] = (uint32_t)(units.size() / 4);
-      if (units.empty()) units.assign(4, 0);
-      HIP_TRY(c, stage_upload(c, p->d_units, units.data(), units.size()));
-      HIP_TRY(c, stage_upload(c, p->d_unit_off, unit_off.data(), 9));
-      if (gtab.empty()) gtab.push_back(0);
-      HIP_TRY(c, stage_upload(c, p->d_gtab, gtab.data(), gtab.size()));
-    }
-    size_t most = 0;
-    for (auto& l : lists) most = std::max(most, l.size());
-    std::vector<uint32_t> slot(most * 8, kInf);
-    for (int g = 0; g < 8; ++g)
-      for (size_t t = 0; t < lists[g].size(); ++t) slot[t * 8 + g] = lists[g][t];
-    p->slots = slot.size();
-    if (slot.empty()) slot.push_back(kInf);
-    HIP_TRY(c, stage_upload(c, p->d_slot_src, slot.data(), slot.size()));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));  // host vectors end here
-    stage_done(c);
-  }
-  PD("units+slots");
-  if (!p->direct) HIP_TRY(c, p->d_D.alloc((size_t)p->closure.size() * c->pitch));
-  if (p->narrow && !p->sdirect) {  // narrow rows + the dead row (all 0xFF) of the next-hop pass
-    HIP_TRY(c, p->d_Dn.alloc((p->closure.size() + 1) * c->npitch));
-    HIP_TRY(c, hipMemsetAsync(p->d_Dn.p + p->closure.size() * c->npitch, 0xFF, c->npitch, c->stream));
-  }
-  if (p->sliced) {  // sliced rows + the dead row (all planes all-ones) + padding
-    const size_t rows = p->closure.size();
-    // a wave's last chunk reads up to 64 * kSlSlots words past a row's end
-    const size_t pad = 64 * kSlSlots + 64;
-    if (((rows + 1) * rstride + pad) * 4 >= (1ull << 31))  // buffer byte offsets
-      return fail(c, SPF_E_UNSUPPORTED, "sliced rows exceed 32-bit offsets");
-    HIP_TRY(c, p->d_S.alloc((rows + 1) * rstride + pad));
-    HIP_TRY(c, hipMemsetAsync(p->d_S.p + rows * rstride, 0xFF, (rstride + pad) * 4, c->stream));
-    HIP_TRY(c, p->d_maxd.alloc(1));
-  }
-  {
-    const spf_status st = set_lds_limits(c);  // kernels need > 64 KiB of dynamic LDS
-    if (st != SPF_OK) return st;
-  }
-  PD("allocs");
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  stage_done(c);
-  p->epoch = c->epoch;
-  return SPF_OK;
+// msbfs_planes_kernel's: full batches when the rows come deepest first
+uint32_t planes_batch(const spf_ctx* c, uint32_t rows, bool ordered) {
+  return ordered ? kPlBatch : spread_batch(c, rows, kPlBatch);
 }
 
-}  // namespace
-
-extern "C" {
-
-spf_status spf_plan_create(spf_ctx* c, const uint32_t* srcs, uint32_t n_src,
-                           uint32_t flags, spf_plan** out) {
-  if (!c || !out) return fail(c, SPF_E_INVALID, "spf_plan_create: NULL argument");
-  *out = nullptr;
-  if (!c->loaded) return fail(c, SPF_E_STATE, "no graph loaded");
-  if (n_src == 0 || !srcs) return fail(c, SPF_E_INVALID, "empty source list");
-  for (uint32_t i = 0; i < n_src; ++i)
-    if (srcs[i] >= c->N) return fail(c, SPF_E_INVALID, "source %u out of range", srcs[i]);
-  auto p = std::make_unique<spf_plan>();
-  p->ctx = c;
-  p->n_src = n_src;
-  p->flags = flags;
-  p->srcs.assign(srcs, srcs + n_src);
-  p->shape = c->shape;
-  p->layout = c->layout;
-  const spf_status st = build_plan(c, p.get());
-  if (st != SPF_OK) return st;
-  *out = p.release();
-  return SPF_OK;
-}
-
-
-void spf_plan_destroy(spf_plan* p) { delete p; }
-uint64_t spf_plan_nh_words(const spf_plan* p) { return p ? p->nh_total : 0; }
-uint32_t spf_plan_closure_rows(const spf_plan* p) { return p ? (uint32_t)p->closure.size() : 0; }
-
-spf_status spf_plan_kernels(const spf_plan* p, uint32_t* bfs, uint32_t* narrow) {
-  if (!p || !bfs || !narrow) return SPF_E_INVALID;
-  *bfs = p->big ? 4u : p->exact ? 3u : p->mp ? 5u : !p->ms ? 0u : p->tm_G ? 6u
-                                                          : use_planes(p->ctx) ? 2u : 1u;
-  *narrow = p->sdirect ? 3u : p->sliced ? 2u : p->narrow ? 1u : 0u;
-  return SPF_OK;
-}
-
-// Bytes each kernel of one execute must move between HBM and the CUs, given
-// the kernel's own structure: what `roofline.achieved` in bench.py divides by
-// the kernel's measured time (no credit for on-chip reuse).
-//   BFS (msbfs / planes): one read of the sliced-ELL columns and the drain
-//     bytes per workgroup (a batch of sources shares one sweep per level;
-//     repeated levels hit the L2), plus the distance rows (u32, pitch) and,
-//     in narrow mode, the u8 rows (npitch) written once.
-//   SSSP (weighted, one workgroup per source): one read of row_ptr, col,
-//     metric and drain bytes per source, plus the distance row written.
-//   ECMP: every distance row it compares read once (u8 rows in narrow mode,
-//     u32 rows otherwise) plus the next-hop bitmaps written once.
-spf_status spf_plan_traffic(const spf_plan* p, uint64_t* bfs_bytes, uint64_t* ecmp_bytes) {
-  if (!p || !bfs_bytes || !ecmp_bytes) return SPF_E_INVALID;
-  uint64_t b[3];
-  const spf_status st = spf_plan_traffic_phases(p, b);
-  if (st != SPF_OK) return st;
-  *bfs_bytes = b[0];
-  *ecmp_bytes = b[1] + b[2];
-  return SPF_OK;
-}
-
-//   Slicing (sliced plans): the u8 rows read, P planes per row written (and,
-//     in expand plans, the u32 rows); the sliced next-hop pass then reads P
-//     planes per row and writes the bitmaps.
-spf_status spf_plan_traffic_phases(const spf_plan* p, uint64_t* bytes) {
-  if (!p || !bytes) return SPF_E_INVALID;
-  uint64_t* bfs_bytes = &bytes[0];
-  uint64_t* ecmp_bytes = &bytes[2];
-  bytes[1] = 0;
-  const spf_ctx* c = p->ctx;
-  const uint64_t N = c->N, E = c->E, rows = p->closure.size();
-  uint64_t bfs = 0;
-  if (p->big) {  // per source: the CSR a few sweeps (counted once), the row, scratch + bitmaps
-    *bfs_bytes = rows * (4ull * (N + 1) + 12ull * E + N + 4ull * c->pitch) + 4ull * p->nh_total;
-    *ecmp_bytes = 0;
-    return SPF_OK;
-  }
-  if (p->exact) {  // per source: the CSR once, the labels, the outputs
-    const uint64_t lab = (p->flags & SPF_FLAG_DIST64) ? 8ull : 4ull;
-    *bfs_bytes = rows * (4ull * (N + 1) + 12ull * E + N + 17ull * N + lab * c->pitch) +
-                 4ull * p->nh_total;
-    *ecmp_bytes = 0;
-    return SPF_OK;
-  }
-  if (p->tm_G) {  // team BFS: each batch sweeps the column stream once (column + meta
-                  // words); rows written: u32 for the prefix when direct, u8 or planes
-    const uint64_t batches = (rows + p->tm_bs - 1) / p->tm_bs;
-    const bool direct = p->prefix && !p->direct && p->narrow;
-    const uint64_t wbytes = 4ull * (c->pitch / 32);
-    bfs = batches * (8ull * c->sell_ptr.back() + N) + (direct ? p->n_src : rows) * c->pitch * 4ull +
-          (p->sdirect ? rows * kTeamPlanes * wbytes : p->narrow ? rows * c->npitch : 0ull);
-  } else if (p->ms) {
-    const bool planes = use_planes(c);
-    const uint32_t batch = planes ? kPlBatch : kMsBatch;
-    const uint64_t rounds = (rows + (uint64_t)batch * c->n_cu - 1) / ((uint64_t)batch * c->n_cu);
-    const uint64_t bs = std::min<uint64_t>(batch, (rows + rounds * c->n_cu - 1) / (rounds * c->n_cu));
-    const uint64_t groups = (rows + bs - 1) / bs;
-    const uint64_t n_slices = c->sell_ptr.size() - 1;
-    // (quotient sweep: the class and row/column tables instead of the columns)
-    const uint64_t csr = planes ? 8ull * c->sell4_ptr.back() + 4ull * (n_slices + 1)
-                         : use_quotient(c) ? 2ull * (c->qt.cls.size() + c->qt.tab.size())
-                                           : 4ull * c->sell_ptr.back() + 4ull * (n_slices + 1);
-    // expand plans: the u32 rows are written by the slicing pass instead
-    bfs = groups * (csr + N) + (p->expand ? 0ull : rows * c->pitch * 4ull) +
-          (p->narrow ? rows * c->npitch : 0ull);
-  } else if (p->mp) {  // per workgroup: the packed ELL + slice map once; rows written once
-    const uint64_t S = mssp_sources(c);
-    const uint64_t groups = (rows + S - 1) / S;
-    bfs = groups * (4ull * c->sell_ptr.back() + 4ull * c->sell_ptr.size() + 4ull * (N + 1) + N) +
-          rows * (4ull * c->pitch + (p->narrow ? c->npitch : 0ull));
-  } else {
-    bfs = rows * (4ull * (N + 1) + 8ull * E + N + 4ull * c->pitch + (p->narrow ? c->npitch : 0ull));
-  }
-  *bfs_bytes = bfs;
-  if (p->sliced && p->nh_total) {
-    // planes in use: from the last execute's deepest level (one 4-byte read)
-    // (sdirect: kTeamPlanes planes written by the BFS itself, no slicing pass)
-    const uint64_t wbytes = 4ull * (c->pitch / 32);
-    if (p->sdirect) {
-      *ecmp_bytes = rows * kTeamPlanes * wbytes + 4ull * p->nh_total;
-      return SPF_OK;
-    }
-    uint32_t md = 0;
-    HIP_TRY(p->ctx, hipMemcpy(&md, p->d_maxd.p, 4, hipMemcpyDeviceToHost));
-    const uint64_t expand = p->expand ? rows * 4ull * c->pitch : 0ull;  // u32 rows written
-    if (md < kSlSat) {
-      const uint64_t P = 32u - __builtin_clz(md + 1u);
-      bytes[1] = rows * c->npitch + rows * P * wbytes + expand;
-      *ecmp_bytes = rows * P * wbytes + 4ull * p->nh_total;
-    } else {
-      bytes[1] = expand ? rows * c->npitch + expand : 0ull;
-      *ecmp_bytes = rows * 4ull * c->pitch + 4ull * p->nh_total;
-    }
-    return SPF_OK;
-  }
-  const uint64_t row_bytes = p->narrow ? c->npitch : 4ull * c->pitch;
-  *ecmp_bytes = p->nh_total ? rows * row_bytes + 4ull * p->nh_total : 0ull;
-  return SPF_OK;
-}
-
-spf_status spf_plan_nh_layout(const spf_plan* p, uint64_t* nh_off, uint32_t* words) {
-  if (!p) return SPF_E_INVALID;
-  for (uint32_t i = 0; i < p->n_src; ++i) {
-    if (nh_off) nh_off[i] = p->nh_off[i];
-    if (words) words[i] = p->words[i];
-  }
-  return SPF_OK;
-}
-
-}  // extern "C"
-
-namespace {
+size_t planes_lds_bytes(uint32_t own) { return 8ull * own * kMsThreads + 4ull * (kPlBatch + 4); }
 
 }  // namespace
 
 namespace spfi {
+
+bool use_quotient(const spf_ctx* c) {
+  const spf_ctx::Quotient& q = c->qt;
+  if (!quotient_allowed(c) || q.stale || q.n_cls == 0 || 2 * q.n_edge > c->nb_id.size()) return false;
+  return msbfs_q_lds_bytes(c->N, q.n_cls, q.n_vrow) <= kMaxLds;
+}
+
+// Which BFS variant: the register-plane kernel needs N <= 10240; it wins
+// when levels are many (partial-line rewrites dominate msbfs_kernel) and
+// loses when the edge sweep dominates (it runs 32 sources per sweep, not
+// 64).  SPF_MSBFS=planes|masks overrides (experiments).
+bool use_planes(const spf_ctx* c) {
+  if (c->N > 10 * (uint32_t)kMsThreads || c->sell4.empty()) return false;
+  if (const char* e = std::getenv("SPF_MSBFS")) return e[0] == 'p';
+  return c->sell_ptr.back() <= 8ull * c->N;  // sliced-ELL width <= 8 on average
+}
 
 // Launch the SSSP kernel over `rows` closure rows (device list rows_src).
 spf_status launch_sssp(spf_ctx* c, const uint32_t* rows_src, uint32_t rows, bool hop,
@@ -2539,218 +1832,6 @@ spf_status launch_sssp(spf_ctx* c, const uint32_t* rows_src, uint32_t rows, bool
   return SPF_OK;
 }
 
-}  // namespace spfi
-
-namespace {
-
-size_t msbfs_lds_bytes(uint32_t N, bool db = false) {
-  return 8ull * (N + 1) * (db ? 2 : 1) + 4ull * (4 * kMsBatch + 5);
-}
-
-// msbfs_kernel with a double-buffered frontier: when the columns do not fit
-// in LDS beside one F array but two F arrays do (SPF_MSBFS_DB=0: single, A/B)
-bool ms_double_buffer(const spf_ctx* c) {
-  const char* e = std::getenv("SPF_MSBFS_DB");
-  if (e && e[0] == '0') return false;
-  const size_t n_col = c->sell_ptr.back();
-  return msbfs_lds_bytes(c->N) + 2ull * n_col > kMaxLds && msbfs_lds_bytes(c->N, true) <= kMaxLds;
-}
-
-// LDS of msbfs_kernel's quotient variant: CF and QA (two buffers each), the
-// row/column tables, the small arrays, the source marks
-size_t msbfs_q_lds_bytes(uint32_t N, uint32_t n_cls, uint32_t n_vrow) {
-  const size_t nvp = (n_vrow + 7u) & ~7u;
-  return 32ull * (n_cls + 1) + 2ull * (1 + kQChunk) * nvp + 4ull * (4 * kMsBatch + 5) + ((N + 3u) & ~3u);
-}
-
-// The quotient sweep is taken when it reads at most half the columns of the
-// plain one (a grid or a ring has no twins: every node its own class) and its
-// tables fit in LDS.  SPF_QUOTIENT=0 keeps the plain sweep (A/B, parity tests).
-bool quotient_allowed(const spf_ctx* c) {
-  if (c->N > kMsMaxNodes || ms_own(c->N) > (uint32_t)kQMaxOwn) return false;
-  const char* e = std::getenv("SPF_QUOTIENT");
-  return !(e && e[0] == '0');
-}
-}  // namespace
-bool spfi::use_quotient(const spf_ctx* c) {
-  const spf_ctx::Quotient& q = c->qt;
-  if (!quotient_allowed(c) || q.stale || q.n_cls == 0 || 2 * q.n_edge > c->nb_id.size()) return false;
-  return msbfs_q_lds_bytes(c->N, q.n_cls, q.n_vrow) <= kMaxLds;
-}
-namespace {
-
-// msbfs_kernel's sources per workgroup.  SPF_MSBFS_BATCH=1..64 fixes it
-// (tests: full batches on graphs too small to fill the chip with them).
-uint32_t ms_batch(const spf_ctx* c, uint32_t rows) {
-  if (const char* e = std::getenv("SPF_MSBFS_BATCH")) {
-    const int b = atoi(e);
-    if (b >= 1 && b <= (int)kMsBatch) return (uint32_t)b;
-  }
-  const uint32_t rounds = (rows + kMsBatch * c->n_cu - 1) / (kMsBatch * c->n_cu);
-  return std::min<uint32_t>(kMsBatch, (rows + rounds * c->n_cu - 1) / (rounds * c->n_cu));
-}
-
-template <int OWN>
-void msbfs_launch(spf_ctx* c, const uint32_t* rows_src, uint32_t rows, uint32_t* D, uint8_t* Dn,
-                  uint32_t* maxd, uint32_t d_from, hipStream_t s) {
-  const uint32_t n_col = c->sell_ptr.back();
-  const size_t lds = msbfs_lds_bytes(c->N), lds_col = lds + 2ull * n_col;
-  const bool lcol = lds_col <= kMaxLds;
-  // one workgroup per CU per round: a batch costs one edge sweep per level
-  // whatever its size, but its stores scale with it, so spread the sources
-  // over every CU rather than fill 64-source batches on fewer CUs
-  const uint32_t bs = ms_batch(c, rows);
-  const uint16_t* const no_q = nullptr;
-  if constexpr (OWN <= kQMaxOwn) {
-    if (use_quotient(c)) {
-      hipLaunchKernelGGL((msbfs_kernel<OWN, false, false, true>), dim3((rows + bs - 1) / bs),
-                       dim3(kMsThreads), msbfs_q_lds_bytes(c->N, c->qt.n_cls, c->qt.n_vrow), s,
-                       c->d_sell_ptr.p, c->d_sell_col.p, n_col, c->d_row_ptr.p, c->d_col.p, c->d_ovl.p,
-                       rows_src, rows, bs, c->N, c->pitch, c->npitch, D, Dn, maxd, d_from,
-                       c->d_ms_smap.p, c->d_stamps.p, c->d_qcls.p, c->d_qtab.p, c->qt.n_cls,
-                       c->qt.n_vrow);
-      return;
-    }
-  }
-  if (lcol)
-    hipLaunchKernelGGL((msbfs_kernel<OWN, true>), dim3((rows + bs - 1) / bs), dim3(kMsThreads),
-                       lds_col, s, c->d_sell_ptr.p, c->d_sell_col.p, n_col, c->d_row_ptr.p, c->d_col.p,
-                       c->d_ovl.p, rows_src, rows, bs, c->N, c->pitch, c->npitch, D, Dn,
-                       maxd, d_from, c->d_ms_smap.p, c->d_stamps.p, no_q, no_q, 0u, 0u);
-  else if (ms_double_buffer(c))
-    hipLaunchKernelGGL((msbfs_kernel<OWN, false, true>), dim3((rows + bs - 1) / bs), dim3(kMsThreads),
-                       msbfs_lds_bytes(c->N, true), s, c->d_sell_ptr.p, c->d_sell_col.p, n_col,
-                       c->d_row_ptr.p, c->d_col.p, c->d_ovl.p, rows_src, rows, bs, c->N, c->pitch,
-                       c->npitch, D, Dn, maxd, d_from, c->d_ms_smap.p, c->d_stamps.p, no_q, no_q, 0u, 0u);
-  else
-    hipLaunchKernelGGL((msbfs_kernel<OWN, false>), dim3((rows + bs - 1) / bs), dim3(kMsThreads),
-                       lds, s, c->d_sell_ptr.p, c->d_sell_col.p, n_col, c->d_row_ptr.p, c->d_col.p,
-                       c->d_ovl.p, rows_src, rows, bs, c->N, c->pitch, c->npitch, D, Dn,
-                       maxd, d_from, c->d_ms_smap.p, c->d_stamps.p, no_q, no_q, 0u, 0u);
-}
-
-size_t planes_lds_bytes(uint32_t own) { return 8ull * own * kMsThreads + 4ull * (kPlBatch + 4); }
-
-//   order (optional): rows sorted by estimated eccentricity, deepest first.
-//   A batch runs until its deepest source's search ends, so batches of
-//   similar depth waste no levels, and the deep ones start first while the
-//   shallow ones fill the CUs that free up (grid 100x100: eccentricities
-//   100..198; 313 full batches are 1.22 rounds of the chip); without it the
-//   batches are spread evenly over rounds.
-template <int OWN>
-void planes_launch(spf_ctx* c, const uint32_t* rows_src, uint32_t rows, uint32_t* D, uint8_t* Dn,
-                   const uint32_t* order, hipStream_t s) {
-  const uint32_t n4 = c->sell4_ptr.back();
-  const size_t lds = planes_lds_bytes(OWN), lds_col = lds + 8ull * n4;
-  const bool lcol = lds_col <= kMaxLds;
-  const uint32_t rounds = (rows + kPlBatch * c->n_cu - 1) / (kPlBatch * c->n_cu);
-  const uint32_t bs = order ? kPlBatch
-                            : std::min<uint32_t>(kPlBatch, (rows + rounds * c->n_cu - 1) / (rounds * c->n_cu));
-  const uint2* col4 = reinterpret_cast<const uint2*>(c->d_sell4.p);
-  if (lcol)
-    hipLaunchKernelGGL((msbfs_planes_kernel<OWN, true>), dim3((rows + bs - 1) / bs), dim3(kMsThreads),
-                       lds_col, s, c->d_sell4_ptr.p, col4, n4, c->d_ovl.p, rows_src, rows, bs, c->N,
-                       c->pitch, c->npitch, D, Dn, order);
-  else
-    hipLaunchKernelGGL((msbfs_planes_kernel<OWN, false>), dim3((rows + bs - 1) / bs), dim3(kMsThreads),
-                       lds, s, c->d_sell4_ptr.p, col4, n4, c->d_ovl.p, rows_src, rows, bs, c->N,
-                       c->pitch, c->npitch, D, Dn, order);
-}
-
-// Which BFS variant: the register-plane kernel needs N <= 10240; it wins
-// when levels are many (partial-line rewrites dominate msbfs_kernel) and
-// loses when the edge sweep dominates (it runs 32 sources per sweep, not
-// 64).  SPF_MSBFS=planes|masks overrides (experiments).
-}  // namespace
-bool spfi::use_planes(const spf_ctx* c) {
-  if (c->N > 10 * (uint32_t)kMsThreads || c->sell4.empty()) return false;
-  if (const char* e = std::getenv("SPF_MSBFS")) return e[0] == 'p';
-  return c->sell_ptr.back() <= 8ull * c->N;  // sliced-ELL width <= 8 on average
-}
-namespace {
-
-spf_status launch_msbfs(spf_ctx* c, const uint32_t* rows_src, uint32_t rows, uint32_t* D,
-                        uint8_t* Dn, uint32_t* maxd, hipStream_t s, uint32_t d_from = 0,
-                        const uint32_t* order = nullptr) {
-  if (!c->d_stamps.p && std::getenv("SPF_STAMPS")) {
-    HIP_TRY(c, c->d_stamps.alloc(kStampWords));
-    HIP_TRY(c, hipMemsetAsync(c->d_stamps.p, 0, 64 * 16 * 8, s));
-    const unsigned long long wg = std::strtoull(std::getenv("SPF_STAMPS"), nullptr, 10);
-    HIP_TRY(c, hipMemcpyAsync(c->d_stamps.p + 64 * 16, &wg, 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-  }
-  const uint32_t own = ms_own(c->N);
-  if (use_planes(c)) {
-    if (own <= 1) planes_launch<1>(c, rows_src, rows, D, Dn, order, s);
-    else if (own <= 2) planes_launch<2>(c, rows_src, rows, D, Dn, order, s);
-    else if (own <= 4) planes_launch<4>(c, rows_src, rows, D, Dn, order, s);
-    else if (own <= 8) planes_launch<8>(c, rows_src, rows, D, Dn, order, s);
-    else planes_launch<10>(c, rows_src, rows, D, Dn, order, s);
-    HIP_TRY(c, hipGetLastError());
-    return SPF_OK;
-  }
-  if (quotient_allowed(c)) {  // (else the tables stay stale: nothing is built for a path not taken)
-    const spf_status st = quotient_prepare(c);
-    if (st != SPF_OK) return st;
-  }
-  if (own == 1) msbfs_launch<1>(c, rows_src, rows, D, Dn, maxd, d_from, s);
-  else if (own == 2) msbfs_launch<2>(c, rows_src, rows, D, Dn, maxd, d_from, s);
-  else if (own == 4) msbfs_launch<4>(c, rows_src, rows, D, Dn, maxd, d_from, s);
-  else if (own == 8) msbfs_launch<8>(c, rows_src, rows, D, Dn, maxd, d_from, s);
-  else if (own == 10) msbfs_launch<10>(c, rows_src, rows, D, Dn, maxd, d_from, s);
-  else if (own == 12) msbfs_launch<12>(c, rows_src, rows, D, Dn, maxd, d_from, s);
-  else msbfs_launch<16>(c, rows_src, rows, D, Dn, maxd, d_from, s);
-  HIP_TRY(c, hipGetLastError());
-  return SPF_OK;
-}
-
-template <bool NARROW>
-spf_status launch_ecmp(spf_ctx* c, spf_plan* p, const uint8_t* Dn, const uint32_t* D, bool hop,
-                       uint32_t* d_nh, hipStream_t s) {
-  const uint32_t per_block = kEcmpChunk * kEcmpWaves;
-  const uint32_t chunks = (c->N + per_block - 1) / per_block;
-  const uint32_t nb = chunks * (uint32_t)p->slots;
-  const uint32_t weighted = NARROW && !hop && !c->unit ? 1u : 0u;
-  hipLaunchKernelGGL((ecmp_kernel<NARROW>), dim3(nb), dim3(kEcmpThreads), 0, s, Dn, c->npitch, D,
-                     c->pitch, c->N, p->d_srcs.p, p->d_row_of.p, c->d_nb_ptr.p, c->d_nb_id.p,
-                     c->d_nb_w.p, p->d_nb_row.p, p->d_nb_row_off.p, p->d_nb_drained.p, p->dead,
-                     hop ? 1u : 0u, weighted,
-                     p->d_nh_off.p, d_nh, chunks, p->d_slot_src.p);
-  HIP_TRY(c, hipGetLastError());
-  return SPF_OK;
-}
-
-spf_status launch_sliced(spf_ctx* c, spf_plan* p, const uint32_t* D, bool hop, uint32_t* d_nh,
-                         hipStream_t s) {
-  const uint32_t wpm = c->pitch / 32;
-  const uint32_t rows = (uint32_t)p->closure.size();
-  const uint64_t words = (uint64_t)rows * wpm;
-  const uint32_t sb = (uint32_t)std::min<uint64_t>((words + 255) / 256, 16ull * c->n_cu);
-  hipLaunchKernelGGL(slice_rows_kernel, dim3(std::max(sb, 1u)), dim3(256), 0, s, p->d_Dn.p, c->npitch,
-                     rows, wpm, p->d_maxd.p, p->d_S.p, p->expand ? const_cast<uint32_t*>(D) : nullptr,
-                     c->pitch);
-  HIP_TRY(c, hipGetLastError());
-  return SPF_OK;
-}
-
-spf_status launch_ecmp_sliced(spf_ctx* c, spf_plan* p, const uint32_t* D, bool hop, uint32_t* d_nh,
-                              hipStream_t s) {
-  // one wave per unit; block b serves XCD b % 8 (round-robin placement)
-  const uint32_t blocks = 8 * std::max(1u, (p->max_xcd_units + kEcmpWaves - 1) / kEcmpWaves);
-  hipLaunchKernelGGL(ecmp_sliced_kernel, dim3(blocks), dim3(kEcmpThreads), 0, s, p->d_S.p,
-                     p->d_maxd.p, D, c->pitch, p->d_srcs.p, p->d_row_of.p,
-                     c->d_nb_ptr.p, c->d_nb_id.p, c->d_nb_w.p, p->d_nb_row.p, p->d_nb_row_off.p,
-                     p->d_nb_drained.p, p->dead, hop ? 1u : 0u, p->d_nh_off.p, d_nh,
-                     reinterpret_cast<const uint4*>(p->d_units.p), p->d_unit_off.p, p->d_gtab.p,
-                     (uint32_t)(p->d_S.n * 4), p->sdirect ? kTeamPlanes : 0u, p->mp ? 1u : 0u);
-  HIP_TRY(c, hipGetLastError());
-  return SPF_OK;
-}
-
-}  // namespace
-
-namespace spfi {
-
 spf_status set_lds_limits(spf_ctx* c) {
   static bool done = false;
   if (done) return SPF_OK;
@@ -2775,14 +1856,6 @@ spf_status set_lds_limits(spf_ctx* c) {
   done = true;
   return SPF_OK;
 }
-
-}  // namespace spfi
-
-namespace {
-
-}  // namespace
-
-namespace spfi {
 
 // Process-wide order of the launches whose workgroups wait on each other
 // (engine_internal.h resident_order): per device, the stream of the last
@@ -2887,7 +1960,611 @@ spf_status upload_ignore(spf_ctx* c, const uint32_t* ignore, uint32_t n_ignore,
 
 }  // namespace spfi
 
+namespace {
+
+template <int OWN>
+void msbfs_launch(spf_ctx* c, const uint32_t* rows_src, uint32_t rows, uint32_t* D, uint8_t* Dn,
+                  uint32_t* maxd, uint32_t d_from, hipStream_t s) {
+  const uint32_t n_col = c->sell_ptr.back();
+  const size_t lds = msbfs_lds_bytes(c->N), lds_col = lds + 2ull * n_col;
+  const bool lcol = lds_col <= kMaxLds;
+  // one workgroup per CU per round: a batch costs one edge sweep per level
+  // whatever its size, but its stores scale with it, so spread the sources
+  // over every CU rather than fill 64-source batches on fewer CUs
+  const uint32_t bs = ms_batch(c, rows);
+  const uint16_t* const no_q = nullptr;
+  if constexpr (OWN <= kQMaxOwn) {
+    if (use_quotient(c)) {
+      hipLaunchKernelGGL((msbfs_kernel<OWN, false, false, true>), dim3((rows + bs - 1) / bs),
+                       dim3(kMsThreads), msbfs_q_lds_bytes(c->N, c->qt.n_cls, c->qt.n_vrow), s,
+                       c->d_sell_ptr.p, c->d_sell_col.p, n_col, c->d_row_ptr.p, c->d_col.p, c->d_ovl.p,
+                       rows_src, rows, bs, c->N, c->pitch, c->npitch, D, Dn, maxd, d_from,
+                       c->d_ms_smap.p, c->d_stamps.p, c->d_qcls.p, c->d_qtab.p, c->qt.n_cls,
+                       c->qt.n_vrow);
+      return;
+    }
+  }
+  if (lcol)
+    hipLaunchKernelGGL((msbfs_kernel<OWN, true>), dim3((rows + bs - 1) / bs), dim3(kMsThreads),
+                       lds_col, s, c->d_sell_ptr.p, c->d_sell_col.p, n_col, c->d_row_ptr.p, c->d_col.p,
+                       c->d_ovl.p, rows_src, rows, bs, c->N, c->pitch, c->npitch, D, Dn,
+                       maxd, d_from, c->d_ms_smap.p, c->d_stamps.p, no_q, no_q, 0u, 0u);
+  else if (ms_double_buffer(c))
+    hipLaunchKernelGGL((msbfs_kernel<OWN, false, true>), dim3((rows + bs - 1) / bs), dim3(kMsThreads),
+                       msbfs_lds_bytes(c->N, true), s, c->d_sell_ptr.p, c->d_sell_col.p, n_col,
+                       c->d_row_ptr.p, c->d_col.p, c->d_ovl.p, rows_src, rows, bs, c->N, c->pitch,
+                       c->npitch, D, Dn, maxd, d_from, c->d_ms_smap.p, c->d_stamps.p, no_q, no_q, 0u, 0u);
+  else
+    hipLaunchKernelGGL((msbfs_kernel<OWN, false>), dim3((rows + bs - 1) / bs), dim3(kMsThreads),
+                       lds, s, c->d_sell_ptr.p, c->d_sell_col.p, n_col, c->d_row_ptr.p, c->d_col.p,
+                       c->d_ovl.p, rows_src, rows, bs, c->N, c->pitch, c->npitch, D, Dn,
+                       maxd, d_from, c->d_ms_smap.p, c->d_stamps.p, no_q, no_q, 0u, 0u);
+}
+
+//   order (optional): rows sorted by estimated eccentricity, deepest first.
+//   A batch runs until its deepest source's search ends, so batches of
+//   similar depth waste no levels, and the deep ones start first while the
+//   shallow ones fill the CUs that free up (grid 100x100: eccentricities
+//   100..198; 313 full batches are 1.22 rounds of the chip); without it the
+//   batches are spread evenly over rounds.
+template <int OWN>
+void planes_launch(spf_ctx* c, const uint32_t* rows_src, uint32_t rows, uint32_t* D, uint8_t* Dn,
+                   const uint32_t* order, hipStream_t s) {
+  const uint32_t n4 = c->sell4_ptr.back();
+  const size_t lds = planes_lds_bytes(OWN), lds_col = lds + 8ull * n4;
+  const bool lcol = lds_col <= kMaxLds;
+  const uint32_t bs = planes_batch(c, rows, order != nullptr);
+  const uint2* col4 = reinterpret_cast<const uint2*>(c->d_sell4.p);
+  if (lcol)
+    hipLaunchKernelGGL((msbfs_planes_kernel<OWN, true>), dim3((rows + bs - 1) / bs), dim3(kMsThreads),
+                       lds_col, s, c->d_sell4_ptr.p, col4, n4, c->d_ovl.p, rows_src, rows, bs, c->N,
+                       c->pitch, c->npitch, D, Dn, order);
+  else
+    hipLaunchKernelGGL((msbfs_planes_kernel<OWN, false>), dim3((rows + bs - 1) / bs), dim3(kMsThreads),
+                       lds, s, c->d_sell4_ptr.p, col4, n4, c->d_ovl.p, rows_src, rows, bs, c->N,
+                       c->pitch, c->npitch, D, Dn, order);
+}
+
+spf_status launch_msbfs(spf_ctx* c, const uint32_t* rows_src, uint32_t rows, uint32_t* D,
+                        uint8_t* Dn, uint32_t* maxd, hipStream_t s, uint32_t d_from = 0,
+                        const uint32_t* order = nullptr) {
+  if (!c->d_stamps.p && std::getenv("SPF_STAMPS")) {
+    HIP_TRY(c, c->d_stamps.alloc(kStampWords));
+    HIP_TRY(c, hipMemsetAsync(c->d_stamps.p, 0, 64 * 16 * 8, s));
+    const unsigned long long wg = std::strtoull(std::getenv("SPF_STAMPS"), nullptr, 10);
+    HIP_TRY(c, hipMemcpyAsync(c->d_stamps.p + 64 * 16, &wg, 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+  }
+  const uint32_t own = ms_own(c->N);
+  if (use_planes(c)) {
+    if (own <= 1) planes_launch<1>(c, rows_src, rows, D, Dn, order, s);
+    else if (own <= 2) planes_launch<2>(c, rows_src, rows, D, Dn, order, s);
+    else if (own <= 4) planes_launch<4>(c, rows_src, rows, D, Dn, order, s);
+    else if (own <= 8) planes_launch<8>(c, rows_src, rows, D, Dn, order, s);
+    else planes_launch<10>(c, rows_src, rows, D, Dn, order, s);
+    HIP_TRY(c, hipGetLastError());
+    return SPF_OK;
+  }
+  if (quotient_allowed(c)) {  // (else the tables stay stale: nothing is built for a path not taken)
+    const spf_status st = quotient_prepare(c);
+    if (st != SPF_OK) return st;
+  }
+  if (own == 1) msbfs_launch<1>(c, rows_src, rows, D, Dn, maxd, d_from, s);
+  else if (own == 2) msbfs_launch<2>(c, rows_src, rows, D, Dn, maxd, d_from, s);
+  else if (own == 4) msbfs_launch<4>(c, rows_src, rows, D, Dn, maxd, d_from, s);
+  else if (own == 8) msbfs_launch<8>(c, rows_src, rows, D, Dn, maxd, d_from, s);
+  else if (own == 10) msbfs_launch<10>(c, rows_src, rows, D, Dn, maxd, d_from, s);
+  else if (own == 12) msbfs_launch<12>(c, rows_src, rows, D, Dn, maxd, d_from, s);
+  else msbfs_launch<16>(c, rows_src, rows, D, Dn, maxd, d_from, s);
+  HIP_TRY(c, hipGetLastError());
+  return SPF_OK;
+}
+
+template <bool NARROW>
+spf_status launch_ecmp(spf_ctx* c, spf_plan* p, const uint8_t* Dn, const uint32_t* D, bool hop,
+                       uint32_t* d_nh, hipStream_t s) {
+  const uint32_t per_block = kEcmpChunk * kEcmpWaves;
+  const uint32_t chunks = (c->N + per_block - 1) / per_block;
+  const uint32_t nb = chunks * (uint32_t)p->slots;
+  const uint32_t weighted = NARROW && !hop && !c->unit ? 1u : 0u;
+  hipLaunchKernelGGL((ecmp_kernel<NARROW>), dim3(nb), dim3(kEcmpThreads), 0, s, Dn, c->npitch, D,
+                     c->pitch, c->N, p->d_srcs.p, p->d_row_of.p, c->d_nb_ptr.p, c->d_nb_id.p,
+                     c->d_nb_w.p, p->d_nb_row.p, p->d_nb_row_off.p, p->d_nb_drained.p, p->dead,
+                     hop ? 1u : 0u, weighted,
+                     p->d_nh_off.p, d_nh, chunks, p->d_slot_src.p);
+  HIP_TRY(c, hipGetLastError());
+  return SPF_OK;
+}
+
+spf_status launch_sliced(spf_ctx* c, spf_plan* p, const uint32_t* D, bool hop, uint32_t* d_nh,
+                         hipStream_t s) {
+  const uint32_t wpm = c->pitch / 32;
+  const uint32_t rows = (uint32_t)p->closure.size();
+  const uint64_t words = (uint64_t)rows * wpm;
+  const uint32_t sb = (uint32_t)std::min<uint64_t>((words + 255) / 256, 16ull * c->n_cu);
+  hipLaunchKernelGGL(slice_rows_kernel, dim3(std::max(sb, 1u)), dim3(256), 0, s, p->d_Dn.p, c->npitch,
+                     rows, wpm, p->d_maxd.p, p->d_S.p, p->expand ? const_cast<uint32_t*>(D) : nullptr,
+                     c->pitch);
+  HIP_TRY(c, hipGetLastError());
+  return SPF_OK;
+}
+
+spf_status launch_ecmp_sliced(spf_ctx* c, spf_plan* p, const uint32_t* D, bool hop, uint32_t* d_nh,
+                              hipStream_t s) {
+  // one wave per unit; block b serves XCD b % 8 (round-robin placement)
+  const uint32_t blocks = 8 * std::max(1u, (p->max_xcd_units + kEcmpWaves - 1) / kEcmpWaves);
+  hipLaunchKernelGGL(ecmp_sliced_kernel, dim3(blocks), dim3(kEcmpThreads), 0, s, p->d_S.p,
+                     p->d_maxd.p, D, c->pitch, p->d_srcs.p, p->d_row_of.p,
+                     c->d_nb_ptr.p, c->d_nb_id.p, c->d_nb_w.p, p->d_nb_row.p, p->d_nb_row_off.p,
+                     p->d_nb_drained.p, p->dead, hop ? 1u : 0u, p->d_nh_off.p, d_nh,
+                     reinterpret_cast<const uint4*>(p->d_units.p), p->d_unit_off.p, p->d_gtab.p,
+                     (uint32_t)(p->d_S.n * 4), p->sdirect ? kTeamPlanes : 0u, p->mp ? 1u : 0u);
+  HIP_TRY(c, hipGetLastError());
+  return SPF_OK;
+}
+
+// The environment's knobs of a plan build (experiments, A/B runs, tests), read
+// anew by every build: tests change them between plan creations.
+struct PlanKnobs {
+  int narrow = -1;  // SPF_NARROW: -1 unset; 0: u32 rows; 1: byte rows, never sliced; 2 (anything else): narrow
+  int big = -1;     // SPF_BIG: 0: the exact kernel instead of spf_big_kernel; 1: every plan it can take
+  bool pl_order = true;  // SPF_PL_ORDER=0: the register-plane BFS keeps the plan order
+  bool wsliced = true;   // SPF_WSLICED=0: weighted plans keep byte rows
+  bool expand = false;   // SPF_EXPAND=1: the slicing pass expands the u32 rows
+  bool sdirect = true;   // SPF_SDIRECT=0: team plans never slice their rows themselves
+  int64_t ecmp_runs = -1;    // SPF_ECMP_RUNS: source runs per XCD (-1: by the plan's size)
+  int64_t sliced_unit = -1;  // SPF_SLICED_UNIT: matches per work unit (-1: plan_sliced_unit)
+  int sliced_group = 2;      // SPF_SLICED_GROUP: plan_sliced_units' group mode
+};
+
+PlanKnobs plan_knobs() {
+  auto first = [](const char* name) {  // the value's first character, -1 when unset
+    const char* e = std::getenv(name);
+    return e ? (int)(unsigned char)e[0] : -1;
+  };
+  auto number = [](const char* name) {
+    const char* e = std::getenv(name);
+    return e ? (int64_t)(uint32_t)atoi(e) : -1;
+  };
+  PlanKnobs k;
+  const int nw = first("SPF_NARROW"), big = first("SPF_BIG");
+  k.narrow = nw < 0 ? -1 : nw == '0' ? 0 : nw == '1' ? 1 : 2;
+  k.big = big == '0' ? 0 : big == '1' ? 1 : -1;
+  k.pl_order = first("SPF_PL_ORDER") != '0';
+  k.wsliced = first("SPF_WSLICED") != '0';
+  k.expand = first("SPF_EXPAND") == '1';
+  k.sdirect = first("SPF_SDIRECT") != '0';
+  k.ecmp_runs = number("SPF_ECMP_RUNS");
+  k.sliced_unit = number("SPF_SLICED_UNIT");
+  if (const char* e = std::getenv("SPF_SLICED_GROUP")) k.sliced_group = atoi(e);
+  return k;
+}
+
+// SPF_PLAN_DEBUG: per-phase host time of a plan build on stderr (diagnostics)
+bool plan_debug() {
+  static const bool on = std::getenv("SPF_PLAN_DEBUG") != nullptr;
+  return on;
+}
+
+// u8 narrow rows for the next-hop pass: 4x fewer bytes per neighbour row
+// read, paid for by a second store per (source, slice, level) in
+// msbfs_kernel.  Worth it when next-hop work (sum of neighbour counts)
+// outweighs the BFS store work, which grows with the number of levels:
+// dense fabrics (degree ~23, 5 levels) yes; always with the register-plane
+// BFS (one coalesced store per row).  SPF_NARROW=0/1 overrides (experiments).
+bool use_narrow(const spf_ctx* c, const spf_plan* p, const PlanKnobs& kn) {
+  if (kn.narrow >= 0) return kn.narrow != 0;
+  // the register-plane BFS writes each row once, coalesced: the u8 copy
+  // costs one more row store and the next-hop pass reads 4x fewer bytes
+  if (use_planes(c)) return true;
+  uint64_t nb = 0;
+  for (uint32_t i = 0; i < p->n_src; ++i) nb += p->words[i];
+  return nb >= 8ull * p->n_src;  // average distinct degree >= 8
+}
+
+// Everything a plan derives from the graph's current state (closure over
+// non-drained neighbours, narrow/exact mode, next-hop row tables).  Run at
+// creation and again by spf_plan_execute after an in-place graph patch
+// (spf_graph_set_overload / spf_graph_set_metric); the output layout
+// (nh_off, words) depends only on the CSR structure, which patches keep.
+// The modes are decided here; the tables come from plan_host.h and go up
+// through the pinned stage on c->stream, so each stays alive until the
+// synchronize that ends its copy.
+spf_status build_plan(spf_ctx* c, spf_plan* p) {
+  auto pd_t0 = std::chrono::steady_clock::now();
+  auto PD = [&](const char* what) {
+    if (!plan_debug()) return;
+    (void)hipStreamSynchronize(c->stream);
+    const auto t = std::chrono::steady_clock::now();
+    std::fprintf(stderr, "build_plan %s %.1f us\n", what, std::chrono::duration<double, std::micro>(t - pd_t0).count());
+    pd_t0 = t;
+  };
+  const PlanKnobs kn = plan_knobs();
+  const uint32_t n_src = p->n_src;
+  const uint32_t* srcs = p->srcs.data();
+  const bool hop = (p->flags & SPF_FLAG_HOP_COUNT) != 0;
+  const bool d64 = (p->flags & SPF_FLAG_DIST64) != 0;
+  if (!hop && c->needs64 && !d64)
+    return fail(c, SPF_E_UNSUPPORTED,
+                "weighted distances of this graph may exceed 32 bits (negative metric or max "
+                "metric x hops >= 2^32): create the plan with SPF_FLAG_DIST64");
+  const uint32_t N = c->N;
+  // the exact kernel replays runSpf step for step: zero-metric plateaus
+  // (pop order), u64 labels, and graphs whose distance rows do not fit the
+  // LDS-resident kernels
+  const bool ms_ok = (hop || c->unit) && N <= kMsMaxNodes;
+  const bool lds_ok = sssp_lds_bytes(N, c->pitch, c->big_nodes, N <= 65535) <= kMaxLds;
+  p->exact = d64 || (!hop && c->nonpos);
+  // graphs beyond the LDS-resident kernels: the whole chip per source
+  // (spf_big_kernel); SPF_BIG=0 sends them to the exact kernel, SPF_BIG=1
+  // sends every plan it can take there (tests)
+  p->big = !p->exact && ((!ms_ok && !lds_ok) ? kn.big != 0 : kn.big == 1);
+  if (!ms_ok && !lds_ok && !p->big) p->exact = true;
+  {
+    NhLayout l = plan_nh_layout(*c, srcs, n_src);
+    p->words = std::move(l.words);
+    p->nh_off = std::move(l.nh_off);
+    p->nh_total = l.nh_total;
+    p->wmax = l.wmax;
+  }
+  if (p->exact || p->big) {  // the request is its own closure; no next-hop pass of ours
+    p->closure = p->srcs;
+    p->direct = true;
+    p->ms = false;
+    p->narrow = false;
+    p->sliced = false;
+    p->expand = false;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (p->exact) {
+      const spf_status st = exact_reserve(c, &p->xs, n_src, p->wmax);
+      if (st != SPF_OK) return st;
+    }
+    HIP_TRY(c, stage_upload(c, p->d_srcs, p->srcs.data(), n_src));
+    HIP_TRY(c, stage_upload(c, p->d_nh_off, p->nh_off.data(), n_src));
+    HIP_TRY(c, stage_upload(c, p->d_words, p->words.data(), n_src));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    stage_done(c);
+    p->epoch = c->epoch;
+    return SPF_OK;
+  }
+  PD("start");
+  PlanRows rows = plan_rows(*c, srcs, n_src);
+  p->closure = std::move(rows.closure);
+  p->direct = rows.direct;
+  const size_t n_rows = p->closure.size();
+  // closure[i] == srcs[i] for i < n_src, and no row can saturate the u8
+  // copy (whose saturated entries the next-hop pass reads from u32 rows)
+  p->prefix = rows.distinct && depth_bound(*c, &c->depth) < kSlSat;
+  p->q16 = N <= 65535;
+  p->lds_bytes = sssp_lds_bytes(N, c->pitch, c->big_nodes, p->q16);
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, stage_upload(c, p->d_srcs, p->srcs.data(), n_src));
+  HIP_TRY(c, stage_upload(c, p->d_closure, p->closure.data(), n_rows));
+  HIP_TRY(c, stage_upload(c, p->d_row_of, rows.row_of.data(), N));
+  HIP_TRY(c, stage_upload(c, p->d_req_rows, rows.req_rows.data(), n_src));
+  HIP_TRY(c, stage_upload(c, p->d_nh_off, p->nh_off.data(), n_src));
+  HIP_TRY(c, stage_upload(c, p->d_words, p->words.data(), n_src));
+  p->ms = ms_ok;
+  // register-plane BFS: batches of similar depth, deepest first (more than
+  // one round of batches only; SPF_PL_ORDER=0 keeps the plan order, A/B)
+  p->pl_order = p->ms && use_planes(c) && n_rows > (size_t)kPlBatch * c->n_cu && kn.pl_order;
+  if (p->pl_order) {
+    const std::vector<uint32_t> order = plan_depth_order(p->closure, ecc_estimate(*c, &c->depth));
+    HIP_TRY(c, stage_upload(c, p->d_pl_order, order.data(), order.size()));
+  }
+  // few batches (a rank's share of a multi-GPU pass): teams of workgroups
+  // per batch (msbfs_team.hip) instead of one workgroup sweeping everything
+  // (p->expand: as the plan's previous build left it)
+  PD("uploads1");
+  p->tm_G = 0;
+  if (p->ms && !use_planes(c) && !p->expand && !c->team_off) {
+    const uint32_t G = msbfs_team_size(c, (uint32_t)n_rows);
+    if (G) {
+      const spf_status st = msbfs_team_prepare(c, p, G);
+      if (st != SPF_OK) return st;
+    }
+  }
+  // weighted: S sources per workgroup on mssp_kernel where it applies
+  PD("team");
+  p->mp = !p->ms && !hop && mssp_words(c) > 0;
+  if (p->mp) {
+    const spf_status st = mssp_prepare(c);
+    if (st != SPF_OK) return st;
+    HIP_TRY(c, p->d_redo.alloc(1 + n_rows));
+  }
+  // The rows the next-hop pass reads.  Weighted plans keep a u8 copy too when
+  // the pitches agree (the sssp kernel writes it beside the u32 row; the
+  // next-hop pass compares bytes and falls back to u32 rows per wave where
+  // the source's row saturates).
+  p->narrow = (p->ms || c->pitch == c->npitch) && use_narrow(c, p, kn);
+  // bit-sliced rows behind the per-level-store BFS (it reports the deepest
+  // level); the register-plane BFS serves deep graphs, where planes would
+  // not pay.  SPF_NARROW=1 keeps the byte-row pass (experiments, tests).
+  // Weighted plans on mssp_kernel: its u8 rows sliced too, next hops by
+  // bit-sliced sums d_x + w (sliced_pass<P, true>); SPF_WSLICED=0: byte rows
+  p->sliced = p->narrow && kn.narrow != 1 && ((p->ms && !use_planes(c)) || (p->mp && kn.wsliced));
+  // SPF_EXPAND=1 (A/B; measured slower): the BFS stores the u8
+  // rows only and the slicing pass expands them into the u32 rows.  By
+  // default the BFS stores both: its u32 stores drain behind its
+  // latency-bound sweeps (+0.06 ms on fabric_full) where a separate
+  // streaming pass costs 0.14 ms and a fused one 0.14 ms of the next-hop
+  // kernel's time (r02_v25/r02_v26)
+  p->expand = p->sliced && c->pitch <= c->npitch && kn.expand;
+  // team plans whose depth stays below the planes' all-ones code write the
+  // sliced rows themselves: no u8 rows, no slicing pass (SPF_SDIRECT=0: A/B)
+  p->sdirect = p->sliced && p->nh_total && p->tm_G && p->prefix && !p->expand &&
+               depth_bound(*c, &c->depth) < (1u << kTeamPlanes) - 1 && kn.sdirect;
+  const uint32_t wpm = c->pitch / 32;
+  const uint64_t rstride = (uint64_t)kSlSlots * wpm;  // sliced row: words
+  // per-source neighbour rows for the next-hop pass
+  const NbRows nb = plan_nb_rows(*c, srcs, n_src, rows.row_of,
+                                 p->sliced ? rstride : p->narrow ? c->npitch : 0, n_rows);
+  p->dead = nb.dead;
+  HIP_TRY(c, stage_upload(c, p->d_nb_row, nb.nb_row.data(), nb.nb_row.size()));
+  HIP_TRY(c, stage_upload(c, p->d_nb_row_off, nb.nb_row_off.data(), n_src));
+  HIP_TRY(c, stage_upload(c, p->d_nb_drained, nb.nb_drained.data(), n_src));
+  // next-hop blocks per XCD (a rank's share of a multi-GPU pass -- ~1.3k
+  // sources -- does best with two long runs per XCD: 0.097 -> 0.095 ms per
+  // world-8 rank, r03_v25)
+  const XcdLists xcd = plan_xcd_lists(
+      p->words, kn.ecmp_runs >= 0 ? (uint32_t)kn.ecmp_runs : n_src >= 4096 ? kEcmpRunsPerXcd : 2u);
+  PD("nb_rows");
+  SlicedUnits su;
+  if (p->sliced) {
+    const uint32_t chunks = (wpm + 63) / 64;
+    const uint32_t unit =
+        kn.sliced_unit >= 0 ? (uint32_t)kn.sliced_unit : plan_sliced_unit(p->words, chunks, c->n_cu);
+    // (weighted plans: no groups -- members share neighbour rows, not metrics)
+    su = plan_sliced_units(xcd.list, p->words, nb, chunks, unit, p->mp ? 0 : kn.sliced_group);
+    p->max_xcd_units = su.max_xcd_units;
+    HIP_TRY(c, stage_upload(c, p->d_units, su.units.data(), su.units.size()));
+    HIP_TRY(c, stage_upload(c, p->d_unit_off, su.unit_off.data(), 9));
+    HIP_TRY(c, stage_upload(c, p->d_gtab, su.gtab.data(), su.gtab.size()));
+  }
+  p->slots = xcd.slots;
+  HIP_TRY(c, stage_upload(c, p->d_slot_src, xcd.slot.data(), xcd.slot.size()));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // the host tables' copies end here
+  stage_done(c);
+  PD("units+slots");
+  if (!p->direct) HIP_TRY(c, p->d_D.alloc(n_rows * c->pitch));
+  if (p->narrow && !p->sdirect) {  // narrow rows + the dead row (all 0xFF) of the next-hop pass
+    HIP_TRY(c, p->d_Dn.alloc((n_rows + 1) * c->npitch));
+    HIP_TRY(c, hipMemsetAsync(p->d_Dn.p + n_rows * c->npitch, 0xFF, c->npitch, c->stream));
+  }
+  if (p->sliced) {  // sliced rows + the dead row (all planes all-ones) + padding
+    // a wave's last chunk reads up to 64 * kSlSlots words past a row's end
+    const size_t pad = 64 * kSlSlots + 64;
+    if (((n_rows + 1) * rstride + pad) * 4 >= (1ull << 31))  // buffer byte offsets
+      return fail(c, SPF_E_UNSUPPORTED, "sliced rows exceed 32-bit offsets");
+    HIP_TRY(c, p->d_S.alloc((n_rows + 1) * rstride + pad));
+    HIP_TRY(c, hipMemsetAsync(p->d_S.p + n_rows * rstride, 0xFF, (rstride + pad) * 4, c->stream));
+    HIP_TRY(c, p->d_maxd.alloc(1));
+  }
+  {
+    const spf_status st = set_lds_limits(c);  // kernels need > 64 KiB of dynamic LDS
+    if (st != SPF_OK) return st;
+  }
+  PD("allocs");
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  stage_done(c);
+  p->epoch = c->epoch;
+  return SPF_OK;
+}
+
+}  // namespace
+
 extern "C" {
+
+const char* spf_global_error(void) { return g_err.c_str(); }
+const char* spf_last_error(const spf_ctx* c) { return c ? c->err.c_str() : g_err.c_str(); }
+uint64_t spf_solves(const spf_ctx* c) { return c ? c->solves : 0; }
+uint32_t spf_row_pitch(const spf_ctx* c) { return c ? c->pitch : 0; }
+int spf_graph_has_nonpositive_metric(const spf_ctx* c) { return c && c->nonpos; }
+int spf_graph_needs_dist64(const spf_ctx* c) { return c && c->needs64; }
+
+spf_status spf_ctx_create(int device, spf_ctx** out) {
+  if (!out) return fail(nullptr, SPF_E_INVALID, "spf_ctx_create: out is NULL");
+  *out = nullptr;
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
+    return fail(nullptr, SPF_E_NO_DEVICE, "no HIP device visible");
+  if (device < 0 || device >= n)
+    return fail(nullptr, SPF_E_NO_DEVICE, "device %d out of range (%d visible)", device, n);
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, device) != hipSuccess)
+    return fail(nullptr, SPF_E_NO_DEVICE, "hipGetDeviceProperties failed");
+  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+    return fail(nullptr, SPF_E_NO_DEVICE, "device %d is %s, engine is built for gfx950",
+                device, prop.gcnArchName);
+  auto c = std::make_unique<spf_ctx>();
+  c->device = device;
+  c->n_cu = (uint32_t)std::max(1, prop.multiProcessorCount);
+  if (hipSetDevice(device) != hipSuccess)
+    return fail(nullptr, SPF_E_HIP, "hipSetDevice(%d) failed", device);
+  // a BLOCKING stream: work enqueued with stream = NULL ("the context's
+  // stream") is ordered after earlier work on the legacy null stream, so a
+  // caller's hipMemset / hipMemcpy on the null stream before an execute is
+  // seen by it (round 3 lost a plan's first bitmaps to exactly that race
+  // with a non-blocking stream)
+  if (hipStreamCreateWithFlags(&c->stream, hipStreamDefault) != hipSuccess)
+    return fail(nullptr, SPF_E_HIP, "hipStreamCreate failed");
+  if (c->d_fault.alloc(1) != hipSuccess || hipMemset(c->d_fault.p, 0, 4) != hipSuccess)
+    return fail(nullptr, SPF_E_HIP, "fault word allocation failed");
+  *out = c.release();
+  return SPF_OK;
+}
+
+void spf_ctx_destroy(spf_ctx* c) {
+  if (!c) return;
+  (void)hipSetDevice(c->device);
+  spfi::resident_forget(c);
+  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  spf_plan_destroy(c->rt.plan);  // spf_routes' cached plan, before its context goes
+  c->rt.plan = nullptr;
+  if (c->stream) {
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipStreamDestroy(c->stream);
+  }
+  if (c->side) {
+    (void)hipStreamSynchronize(c->side);
+    (void)hipStreamDestroy(c->side);
+  }
+  if (c->side_fork) (void)hipEventDestroy(c->side_fork);
+  if (c->side_join) (void)hipEventDestroy(c->side_join);
+  delete c;
+}
+
+spf_status spf_src_neighbors(const spf_ctx* c, uint32_t src, uint32_t* out,
+                             uint32_t cap, uint32_t* count) {
+  if (!c || !c->loaded) return SPF_E_STATE;
+  if (src >= c->N) return SPF_E_INVALID;
+  const uint32_t b = c->nb_ptr[src], k = c->nb_ptr[src + 1] - b;
+  if (count) *count = k;
+  for (uint32_t i = 0; i < k && i < cap && out; ++i) out[i] = c->nb_id[b + i];
+  return SPF_OK;
+}
+
+spf_status spf_plan_create(spf_ctx* c, const uint32_t* srcs, uint32_t n_src,
+                           uint32_t flags, spf_plan** out) {
+  if (!c || !out) return fail(c, SPF_E_INVALID, "spf_plan_create: NULL argument");
+  *out = nullptr;
+  if (!c->loaded) return fail(c, SPF_E_STATE, "no graph loaded");
+  if (n_src == 0 || !srcs) return fail(c, SPF_E_INVALID, "empty source list");
+  for (uint32_t i = 0; i < n_src; ++i)
+    if (srcs[i] >= c->N) return fail(c, SPF_E_INVALID, "source %u out of range", srcs[i]);
+  auto p = std::make_unique<spf_plan>();
+  p->ctx = c;
+  p->n_src = n_src;
+  p->flags = flags;
+  p->srcs.assign(srcs, srcs + n_src);
+  p->shape = c->shape;
+  p->layout = c->layout;
+  const spf_status st = build_plan(c, p.get());
+  if (st != SPF_OK) return st;
+  *out = p.release();
+  return SPF_OK;
+}
+
+
+void spf_plan_destroy(spf_plan* p) { delete p; }
+uint64_t spf_plan_nh_words(const spf_plan* p) { return p ? p->nh_total : 0; }
+uint32_t spf_plan_closure_rows(const spf_plan* p) { return p ? (uint32_t)p->closure.size() : 0; }
+
+spf_status spf_plan_kernels(const spf_plan* p, uint32_t* bfs, uint32_t* narrow) {
+  if (!p || !bfs || !narrow) return SPF_E_INVALID;
+  *bfs = p->big ? 4u : p->exact ? 3u : p->mp ? 5u : !p->ms ? 0u : p->tm_G ? 6u
+                                                          : use_planes(p->ctx) ? 2u : 1u;
+  *narrow = p->sdirect ? 3u : p->sliced ? 2u : p->narrow ? 1u : 0u;
+  return SPF_OK;
+}
+
+// Bytes each kernel of one execute must move between HBM and the CUs, given
+// the kernel's own structure: what `roofline.achieved` in bench.py divides by
+// the kernel's measured time (no credit for on-chip reuse).
+//   BFS (msbfs / planes): one read of the sliced-ELL columns and the drain
+//     bytes per workgroup (a batch of sources shares one sweep per level;
+//     repeated levels hit the L2), plus the distance rows (u32, pitch) and,
+//     in narrow mode, the u8 rows (npitch) written once.
+//   SSSP (weighted, one workgroup per source): one read of row_ptr, col,
+//     metric and drain bytes per source, plus the distance row written.
+//   ECMP: every distance row it compares read once (u8 rows in narrow mode,
+//     u32 rows otherwise) plus the next-hop bitmaps written once.
+spf_status spf_plan_traffic(const spf_plan* p, uint64_t* bfs_bytes, uint64_t* ecmp_bytes) {
+  if (!p || !bfs_bytes || !ecmp_bytes) return SPF_E_INVALID;
+  uint64_t b[3];
+  const spf_status st = spf_plan_traffic_phases(p, b);
+  if (st != SPF_OK) return st;
+  *bfs_bytes = b[0];
+  *ecmp_bytes = b[1] + b[2];
+  return SPF_OK;
+}
+
+//   Slicing (sliced plans): the u8 rows read, P planes per row written (and,
+//     in expand plans, the u32 rows); the sliced next-hop pass then reads P
+//     planes per row and writes the bitmaps.
+spf_status spf_plan_traffic_phases(const spf_plan* p, uint64_t* bytes) {
+  if (!p || !bytes) return SPF_E_INVALID;
+  uint64_t* bfs_bytes = &bytes[0];
+  uint64_t* ecmp_bytes = &bytes[2];
+  bytes[1] = 0;
+  const spf_ctx* c = p->ctx;
+  const uint64_t N = c->N, E = c->E, rows = p->closure.size();
+  uint64_t bfs = 0;
+  if (p->big) {  // per source: the CSR a few sweeps (counted once), the row, scratch + bitmaps
+    *bfs_bytes = rows * (4ull * (N + 1) + 12ull * E + N + 4ull * c->pitch) + 4ull * p->nh_total;
+    *ecmp_bytes = 0;
+    return SPF_OK;
+  }
+  if (p->exact) {  // per source: the CSR once, the labels, the outputs
+    const uint64_t lab = (p->flags & SPF_FLAG_DIST64) ? 8ull : 4ull;
+    *bfs_bytes = rows * (4ull * (N + 1) + 12ull * E + N + 17ull * N + lab * c->pitch) +
+                 4ull * p->nh_total;
+    *ecmp_bytes = 0;
+    return SPF_OK;
+  }
+  if (p->tm_G) {  // team BFS: each batch sweeps the column stream once (column + meta
+                  // words); rows written: u32 for the prefix when direct, u8 or planes
+    const uint64_t batches = (rows + p->tm_bs - 1) / p->tm_bs;
+    const bool direct = p->prefix && !p->direct && p->narrow;
+    const uint64_t wbytes = 4ull * (c->pitch / 32);
+    bfs = batches * (8ull * c->sell_ptr.back() + N) + (direct ? p->n_src : rows) * c->pitch * 4ull +
+          (p->sdirect ? rows * kTeamPlanes * wbytes : p->narrow ? rows * c->npitch : 0ull);
+  } else if (p->ms) {
+    const bool planes = use_planes(c);
+    // (the model takes neither SPF_MSBFS_BATCH nor a deepest-first order into account)
+    const uint64_t bs = planes ? planes_batch(c, (uint32_t)rows, false) : ms_batch(c, (uint32_t)rows, false);
+    const uint64_t groups = (rows + bs - 1) / bs;
+    const uint64_t n_slices = c->sell_ptr.size() - 1;
+    // (quotient sweep: the class and row/column tables instead of the columns)
+    const uint64_t csr = planes ? 8ull * c->sell4_ptr.back() + 4ull * (n_slices + 1)
+                         : use_quotient(c) ? 2ull * (c->qt.cls.size() + c->qt.tab.size())
+                                           : 4ull * c->sell_ptr.back() + 4ull * (n_slices + 1);
+    // expand plans: the u32 rows are written by the slicing pass instead
+    bfs = groups * (csr + N) + (p->expand ? 0ull : rows * c->pitch * 4ull) +
+          (p->narrow ? rows * c->npitch : 0ull);
+  } else if (p->mp) {  // per workgroup: the packed ELL + slice map once; rows written once
+    const uint64_t S = mssp_sources(c);
+    const uint64_t groups = (rows + S - 1) / S;
+    bfs = groups * (4ull * c->sell_ptr.back() + 4ull * c->sell_ptr.size() + 4ull * (N + 1) + N) +
+          rows * (4ull * c->pitch + (p->narrow ? c->npitch : 0ull));
+  } else {
+    bfs = rows * (4ull * (N + 1) + 8ull * E + N + 4ull * c->pitch + (p->narrow ? c->npitch : 0ull));
+  }
+  *bfs_bytes = bfs;
+  if (p->sliced && p->nh_total) {
+    // planes in use: from the last execute's deepest level (one 4-byte read)
+    // (sdirect: kTeamPlanes planes written by the BFS itself, no slicing pass)
+    const uint64_t wbytes = 4ull * (c->pitch / 32);
+    if (p->sdirect) {
+      *ecmp_bytes = rows * kTeamPlanes * wbytes + 4ull * p->nh_total;
+      return SPF_OK;
+    }
+    uint32_t md = 0;
+    HIP_TRY(p->ctx, hipMemcpy(&md, p->d_maxd.p, 4, hipMemcpyDeviceToHost));
+    const uint64_t expand = p->expand ? rows * 4ull * c->pitch : 0ull;  // u32 rows written
+    if (md < kSlSat) {
+      const uint64_t P = 32u - __builtin_clz(md + 1u);
+      bytes[1] = rows * c->npitch + rows * P * wbytes + expand;
+      *ecmp_bytes = rows * P * wbytes + 4ull * p->nh_total;
+    } else {
+      bytes[1] = expand ? rows * c->npitch + expand : 0ull;
+      *ecmp_bytes = rows * 4ull * c->pitch + 4ull * p->nh_total;
+    }
+    return SPF_OK;
+  }
+  const uint64_t row_bytes = p->narrow ? c->npitch : 4ull * c->pitch;
+  *ecmp_bytes = p->nh_total ? rows * row_bytes + 4ull * p->nh_total : 0ull;
+  return SPF_OK;
+}
+
+spf_status spf_plan_nh_layout(const spf_plan* p, uint64_t* nh_off, uint32_t* words) {
+  if (!p) return SPF_E_INVALID;
+  for (uint32_t i = 0; i < p->n_src; ++i) {
+    if (nh_off) nh_off[i] = p->nh_off[i];
+    if (words) words[i] = p->words[i];
+  }
+  return SPF_OK;
+}
 
 spf_status spf_plan_execute(spf_plan* p, uint32_t* d_dist, uint32_t* d_nh, void* stream) {
   if (!p) return fail(nullptr, SPF_E_INVALID, "spf_plan_execute: NULL plan");

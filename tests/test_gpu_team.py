@@ -90,6 +90,22 @@ def test_sliced_next_hops_grouped_and_per_source(group, monkeypatch):
         compare(names, eng, orc, list(range(len(names))))
 
 
+@pytest.mark.parametrize("knobs", [{"SPF_SLICED_UNIT": "16", "SPF_ECMP_RUNS": "0"},
+                                   {"SPF_SLICED_GROUP": "2"}],
+                         ids=["unit16-round-robin", "group2"])
+def test_sliced_next_hops_cut_units_and_segment_groups(knobs, monkeypatch):
+    """The sliced next-hop pass over work units of 16 matches (a fabric
+    switch's and a group's neighbour range cut into several units) with the
+    sources dealt to the XCDs round-robin, and with per-segment groups asked
+    for by name."""
+    for name, value in knobs.items():
+        monkeypatch.setenv(name, value)
+    monkeypatch.setenv("SPF_NARROW", "2")
+    names, eng, orc = load(T.fabric(1000, full=True))
+    assert eng.plan([0]).row_mode() in ("sliced", "sliced_bfs")
+    compare(names, eng, orc, list(range(len(names))))
+
+
 def test_team_timeout_turns_teams_off_and_the_plan_reruns_on_msbfs_kernel(monkeypatch):
     """A team barrier that times out (another process's grid holding CUs;
     here the kernel's test hook SPF_TEAM_FLUSH_DBG=32 reports one) fails the
