@@ -188,6 +188,15 @@ uint32_t spf_plan_closure_rows(const spf_plan* plan); /* sources actually solved
  * planes itself (4 per word; no u8 rows, no slicing pass).
  * No reference counterpart (engine introspection). */
 spf_status spf_plan_kernels(const spf_plan* plan, uint32_t* bfs, uint32_t* narrow);
+/* Class rows: *in_use = 1 when the plan's unit-metric BFS solves one row per
+ * false-twin class among its closure rows (class_bfs_kernel) and
+ * expand_rows_kernel writes the node rows, their bit planes and, once asked
+ * for, their u8 copies from those -- msbfs_kernel plans (spf_plan_kernels
+ * keeps reporting *bfs = 1 and *narrow = 2 for them) on a graph whose
+ * quotient is in use; SPF_CLASS_ROWS=0 in the environment at the plan's build
+ * keeps msbfs_kernel's rows.  *n_class_sources = the rows the BFS solves (0 when
+ * not in use).  Either output may be NULL.  Engine introspection. */
+spf_status spf_plan_class_rows(const spf_plan* plan, uint32_t* n_class_sources, uint32_t* in_use);
 /* Bytes the distance kernel and the next-hop kernel of one execute must move
  * to or from HBM (compulsory traffic given each kernel's structure: one
  * column sweep per BFS workgroup or per SSSP source, every output written

@@ -277,6 +277,17 @@ struct spf_plan {
   spfi::DevBuf<uint32_t> d_units, d_unit_off;  // sliced pass: uint4 work units per XCD
   spfi::DevBuf<uint32_t> d_gtab;  // sliced pass: source groups ([n, sources...] each)
   uint32_t max_xcd_units = 0;
+  // class rows (ms plans on a quotient graph, plan_host.h ClassRows):
+  // class_bfs_kernel solves cls_k class sources into d_Dc[cls_k][cls_pitch]
+  // (u16), expand_rows_kernel writes the u32 rows and the bit planes from
+  // them.  The u8 rows exist only once someone asked (plan_ensure_narrow):
+  // keep_narrow then has every execute's expansion write them too.
+  bool cls = false, keep_narrow = false;
+  bool cls_ready = false;  // d_Dc holds the class rows of an execute on the current tables
+  uint32_t cls_k = 0, cls_pitch = 0;
+  spfi::DevBuf<uint32_t> d_csrc, d_crow_of;
+  spfi::DevBuf<uint8_t> d_cfwd;
+  spfi::DevBuf<uint16_t> d_Dc;
   bool big = false;  // spf_big_kernel (whatif.hip): graphs beyond the LDS kernels
   spfi::DevBuf<uint32_t> b_q, b_q2, b_bm, b_ctr, b_nbr_bit, b_nhb, b_lvl, b_order, b_misc, b_parent;
   spfi::DevBuf<uint32_t> b_bar;  // spf_big_kernel's grid-barrier counters
@@ -437,6 +448,12 @@ spf_status set_lds_limits(spf_ctx* c);
 spf_status quotient_prepare(spf_ctx* c);
 bool use_quotient(const spf_ctx* c);
 bool use_planes(const spf_ctx* c);
+// The u8 rows of a plan (closure order, npitch bytes each, the dead row behind
+// them) for readers outside the step: true when the plan can provide them;
+// plan_ensure_narrow makes p->d_Dn hold the last execute's (class plans fill
+// them on the first call, on stream s, and keep them from then on).
+bool plan_has_narrow(const spf_plan* p);
+spf_status plan_ensure_narrow(spf_plan* p, hipStream_t s);
 // Order a launch whose workgroups wait on each other (grid barriers, team
 // BFS) on stream s after the previous such launch of this process on the
 // same device, whatever context or stream that was on: two of them running

@@ -885,7 +885,7 @@ spf_status route_prepare(spf_mplan* mp, const uint32_t* set_ptr, const uint32_t*
     for (uint32_t r = 0; r < mp->n_parts && u8; ++r) {
       const spf_plan* pl = mp->parts[r].plan;
       if (!pl) continue;
-      u8 = pl->narrow && pl->sliced && !pl->sdirect && !pl->expand && pl->d_Dn.p && pl->d_maxd.p;
+      u8 = pl->narrow && pl->sliced && !pl->sdirect && !pl->expand && plan_has_narrow(pl) && pl->d_maxd.p;
       if (!u8) break;
       uint32_t md = ~0u;
       M_HIP(m, hipSetDevice(m->members[r]->device));
@@ -895,8 +895,13 @@ spf_status route_prepare(spf_mplan* mp, const uint32_t* set_ptr, const uint32_t*
     if (u8) {
       mp->h_nrowp.assign(N, 0);
       for (uint32_t r = 0; r < mp->n_parts; ++r) {
-        const spf_plan* pl = mp->parts[r].plan;
+        spf_plan* pl = mp->parts[r].plan;
         if (!pl) continue;
+        // (class plans fill their u8 rows on the first request)
+        M_HIP(m, hipSetDevice(m->members[r]->device));
+        if (plan_ensure_narrow(pl, m->exec[r]) != SPF_OK)
+          return mfail(m, SPF_E_HIP, "%s", spf_last_error(m->members[r]));
+        M_HIP(m, hipStreamSynchronize(m->exec[r]));
         const uint32_t np = m->members[r]->npitch;
         for (size_t ci = 0; ci < pl->closure.size(); ++ci)
           mp->h_nrowp[pl->closure[ci]] = (unsigned long long)(uintptr_t)(pl->d_Dn.p + ci * np);

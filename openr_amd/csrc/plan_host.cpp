@@ -95,6 +95,25 @@ NbRows plan_nb_rows(const GraphHost& g, const uint32_t* srcs, uint32_t n_src,
   return nb;
 }
 
+ClassRows plan_class_rows(const GraphHost& g, const std::vector<uint32_t>& closure) {
+  ClassRows cr;
+  const std::vector<uint16_t>& cls = g.qt.cls;
+  cr.fwd.assign(g.qt.n_cls, 0);
+  for (uint32_t v = 0; v < g.N; ++v)
+    if (!g.ovl[v]) cr.fwd[cls[v]] = 1;
+  std::vector<uint32_t> src_of(g.qt.n_cls, kInf);  // class -> its class source
+  cr.crow_of.resize(closure.size());
+  for (size_t r = 0; r < closure.size(); ++r) {
+    uint32_t& k = src_of[cls[closure[r]]];
+    if (k == kInf) {
+      k = (uint32_t)cr.csrc.size();
+      cr.csrc.push_back(closure[r]);
+    }
+    cr.crow_of[r] = k;
+  }
+  return cr;
+}
+
 XcdLists plan_xcd_lists(const std::vector<uint32_t>& words, uint32_t runs) {
   XcdLists x;
   const uint32_t n_src = (uint32_t)words.size();

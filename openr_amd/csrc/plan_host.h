@@ -91,6 +91,23 @@ SlicedUnits plan_sliced_units(const std::vector<uint32_t> (&list)[8], const std:
 // the unit size of a plan left to itself: about 16 units per CU, 16 .. kSlUnit
 uint32_t plan_sliced_unit(const std::vector<uint32_t>& words, uint32_t chunks, uint32_t n_cu);
 
+// Class rows (unit-metric plans on a graph whose twin-class quotient is in
+// use): for a fixed source, every node of one class other than the source
+// lies at the same distance, and twin sources agree outside themselves, so
+// the BFS solves one row per distinct class among the closure rows and the
+// expansion kernel writes the node rows from those.
+//   csrc[k]: the node standing for class source k (the first closure row of
+//     its class, class sources in closure order);
+//   crow_of[r]: the class source of closure row r (closure[r]'s class);
+//   fwd[c]: 1 when some member of class c is not drained (a class reached by
+//     the BFS forwards then: twins share their neighbours).
+// Needs g.qt built (graph_host_quotient) for the graph as it stands.
+struct ClassRows {
+  std::vector<uint32_t> csrc, crow_of;
+  std::vector<uint8_t> fwd;
+};
+ClassRows plan_class_rows(const GraphHost& g, const std::vector<uint32_t>& closure);
+
 // What the two bounds below remember of the graph they were taken from.
 struct DepthCache {
   std::vector<uint32_t> ecc;  // per-node eccentricity estimates, for ecc_epoch

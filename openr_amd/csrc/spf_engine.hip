@@ -1239,6 +1239,235 @@ __global__ __launch_bounds__(256) void slice_rows_kernel(const uint8_t* __restri
   }
 }
 
+// ---------------------------------------------------------------------------
+//  1d. class rows: the BFS over class sources, and the rows expanded from it
+// ---------------------------------------------------------------------------
+// On a quotient graph d(s, v), v != s, depends only on the classes of s and
+// v: msbfs_kernel's Q sweep with classes for nodes.  A class
+// source's bit starts in its class's frontier slot and expands whatever its
+// drain bit; its own class is not marked visited, so it is reached again
+// through a forwarding neighbour (level 2, usually) and Dc[k][own class]
+// comes out as the distance of the source's twins.  A class reached later
+// forwards when one of its members is not drained (fwd).  Visited masks live
+// in LDS (VIS): a thread owns classes tid, tid + 1024, ...
+// Dc[k][c] (u16, 0xFFFF unreachable, also the padding up to cpitch) is stored
+// per level, 64 consecutive classes of one class source per wave store.
+__global__ __launch_bounds__(kMsThreads) void class_bfs_kernel(
+    const uint16_t* __restrict__ q_cls, const uint16_t* __restrict__ q_tab, uint32_t q_nc,
+    uint32_t q_nv, const uint32_t* __restrict__ csrc, uint32_t K, uint32_t bs,
+    const uint8_t* __restrict__ fwd, uint16_t* __restrict__ Dc, uint32_t cpitch,
+    uint32_t* __restrict__ maxd) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const uint32_t q_nvp = (q_nv + 7u) & ~7u;
+  const uint32_t nc1 = (q_nc + 2u) & ~1u;  // slots per array: q_nc + 1, even (16-byte tables behind)
+  uint64_t* const CF = reinterpret_cast<uint64_t*>(smem);  // [2][nc1]
+  uint64_t* const QA = CF + 2 * nc1;                       // [2][nc1]
+  uint64_t* const VIS = QA + 2 * nc1;                      // [nc1]
+  uint16_t* const vrow = reinterpret_cast<uint16_t*>(VIS + nc1);  // [q_nvp]
+  uint16_t* const vcol = vrow + q_nvp;                                    // [kQChunk][q_nvp]
+  uint32_t* const flag = reinterpret_cast<uint32_t*>(vcol + kQChunk * q_nvp);  // [4]
+  uint8_t* const fw = reinterpret_cast<uint8_t*>(flag + 4);                    // [q_nc]
+
+  const uint32_t tid = threadIdx.x, lane = tid & 63;
+  const uint32_t row0 = blockIdx.x * bs;
+  const uint32_t nb = min(bs, K - row0);
+  const uint64_t all = nb == 64 ? ~0ull : ((1ull << nb) - 1ull);
+  for (uint32_t t = tid; t < 5 * nc1; t += kMsThreads) CF[t] = 0;  // CF, QA, VIS
+  const uint4* tab4 = reinterpret_cast<const uint4*>(q_tab);
+  for (uint32_t t = tid; t < (1 + kQChunk) * q_nvp / 8; t += kMsThreads)
+    reinterpret_cast<uint4*>(vrow)[t] = tab4[t];
+  for (uint32_t t = tid; t < q_nc; t += kMsThreads) fw[t] = fwd[t];
+  if (tid < 3) flag[tid] = 0;
+  __syncthreads();
+  if (tid < nb)
+    atomicOr(reinterpret_cast<unsigned long long*>(&CF[q_cls[csrc[row0 + tid]]]), 1ull << tid);
+  __syncthreads();
+  uint32_t last = 0;
+  for (uint32_t L = 0;; ++L) {
+    const uint64_t* CFc = CF + (L & 1u) * nc1;
+    uint64_t* CFn = CF + ((L + 1) & 1u) * nc1;
+    uint64_t* QAc = QA + (L & 1u) * nc1;
+    uint64_t* QAn = QA + ((L + 1) & 1u) * nc1;
+    for (uint32_t r = tid; r < q_nv; r += kMsThreads) {
+      uint32_t k[kQChunk];
+#pragma unroll
+      for (uint32_t j = 0; j < kQChunk; ++j) k[j] = vcol[j * q_nvp + r];
+      uint64_t acc = 0;
+#pragma unroll
+      for (uint32_t j = 0; j < kQChunk; ++j) acc |= CFc[k[j]];
+      if (acc) atomicOr(reinterpret_cast<unsigned long long*>(&QAc[vrow[r]]), acc);
+    }
+    for (uint32_t t = tid; t <= q_nc; t += kMsThreads) {
+      CFn[t] = 0;
+      QAn[t] = 0;
+    }
+    __syncthreads();
+    uint64_t any = 0;
+    for (uint32_t t0 = tid - lane; t0 < q_nc; t0 += kMsThreads) {  // wave-uniform trips
+      const uint32_t t = t0 + lane;
+      uint64_t nx = 0;
+      if (t < q_nc) {
+        const uint64_t v = VIS[t];
+        nx = QAc[t] & ~v;
+        if (nx) {
+          VIS[t] = v | nx;
+          if (fw[t]) CFn[t] = nx;
+        }
+      }
+      any |= nx;
+      for (uint64_t m = wave_or64(nx); m; m &= m - 1) {
+        const uint32_t s = __ffsll((unsigned long long)m) - 1;
+        if ((nx >> s) & 1ull) Dc[(size_t)(row0 + s) * cpitch + t] = (uint16_t)(L + 1);
+      }
+    }
+    if (any) flag[L % 3] = 1;
+    if (tid == 0) flag[(L + 1) % 3] = 0;
+    __syncthreads();
+    if (!flag[L % 3]) {
+      last = L;
+      break;
+    }
+  }
+  if (tid == 0) atomicMax(maxd, last);
+  // unreachable classes and the padding of the batch's rows
+  for (uint32_t t0 = tid - lane; t0 < q_nc; t0 += kMsThreads) {
+    const uint32_t t = t0 + lane;
+    const uint64_t miss = t < q_nc ? ~VIS[t] & all : 0ull;
+    for (uint64_t m = wave_or64(miss); m; m &= m - 1) {
+      const uint32_t s = __ffsll((unsigned long long)m) - 1;
+      if ((miss >> s) & 1ull) Dc[(size_t)(row0 + s) * cpitch + t] = 0xFFFFu;
+    }
+  }
+  const uint32_t pw = cpitch - q_nc;
+  for (uint32_t t = tid; t < nb * pw; t += kMsThreads)
+    Dc[(size_t)(row0 + t / pw) * cpitch + q_nc + t % pw] = 0xFFFFu;
+}
+
+// Node rows from class rows.  A workgroup owns kExNodes consecutive nodes
+// (four per thread: one 16-byte store per row) and walks a range of closure
+// rows, kExRows at a time: the classes of its nodes get local numbers once
+// (LDS map; local class 0 = the padding past N, always unreachable), per row
+// group the class rows' entries of those classes are staged transposed in
+// LDS (T[local class] = its kExRows distances), and a thread reads its four
+// nodes' distances of the whole group with four 16-byte LDS loads.
+//   d(closure[r], v) = Dc[crow_of[r]][class of v]; the node closure[r] itself
+//   gets 0.
+//   D:  the u32 rows (pitch; unreachable and padding kInf), streaming stores.
+//   S:  with maxd < kSlSat, the rows' bit planes in ecmp_sliced_kernel's
+//       layout (S + r * kSlSlots * wpm + w * P): a thread's four nodes give a
+//       nibble per plane, eight lanes' nibbles one word (three xor shuffles),
+//       and lane 8q + b of a wave stores plane b of the wave's word q.
+//   Dn: the u8 rows (npitch; min(d, 254), 255 unreachable and padding).
+// Any of the three may be null.
+constexpr uint32_t kExThreads = 256;
+constexpr uint32_t kExNodes = 4 * kExThreads;
+constexpr uint32_t kExRows = 8;
+__global__ __launch_bounds__(kExThreads) void expand_rows_kernel(
+    const uint16_t* __restrict__ Dc, uint32_t cpitch, const uint32_t* __restrict__ crow_of,
+    const uint32_t* __restrict__ closure, uint32_t rows, uint32_t rows_per,
+    const uint16_t* __restrict__ q_cls, uint32_t q_nc, uint32_t N, uint32_t pitch, uint32_t npitch,
+    uint32_t* __restrict__ D, uint8_t* __restrict__ Dn, uint32_t* __restrict__ S,
+    const uint32_t* __restrict__ maxd) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint4* const T = reinterpret_cast<uint4*>(smem);              // [kExNodes + 1]
+  uint32_t* const list = reinterpret_cast<uint32_t*>(T + kExNodes + 1);  // [kExNodes + 1]
+  uint32_t* const cnt = list + kExNodes + 1;                    // [1] (+ 2 unused)
+  uint32_t* const map = cnt + 3;                                // [q_nc]
+  constexpr uint32_t kEmpty = 0xFFFFFFFFu, kClaimed = 0xFFFFFFFEu;
+
+  const uint32_t tid = threadIdx.x, lane = tid & 63;
+  const uint32_t cbase = blockIdx.x * kExNodes, v0 = cbase + tid * 4;
+  const uint32_t r_begin = blockIdx.y * rows_per, r_end = min(rows, r_begin + rows_per);
+  const uint32_t md = *maxd;
+  const uint32_t P = (S && md < kSlSat) ? 32u - __clz(md + 1u) : 0u;
+  const uint32_t wpm = pitch / 32;
+
+  for (uint32_t t = tid; t < q_nc; t += kExThreads) map[t] = kEmpty;
+  if (tid == 0) {
+    *cnt = 1;
+    T[0] = make_uint4(~0u, ~0u, ~0u, ~0u);
+  }
+  __syncthreads();
+  uint32_t cl[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    cl[k] = v0 + k < N ? q_cls[v0 + k] : kEmpty;
+    if (cl[k] != kEmpty && atomicCAS(&map[cl[k]], kEmpty, kClaimed) == kEmpty) {
+      const uint32_t id = atomicAdd(cnt, 1u);
+      list[id] = cl[k];
+      map[cl[k]] = id;
+    }
+  }
+  __syncthreads();
+  const uint32_t n_loc = *cnt;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) cl[k] = cl[k] != kEmpty ? map[cl[k]] : 0u;  // local numbers
+
+  // the lane's word of its wave (8 lanes = 32 nodes) and the plane it stores
+  const uint32_t w = v0 / 32, pb = lane & 7u, nsh = 4u * pb;
+  const bool d_live = D && v0 < pitch, n_live = Dn && v0 < npitch, s_live = pb < P && w < wpm;
+  for (uint32_t r0 = r_begin; r0 < r_end; r0 += kExRows) {
+    __syncthreads();  // the previous group's T is read
+    for (uint32_t lc = 1 + tid; lc < n_loc; lc += kExThreads) {
+      const uint32_t gc = list[lc];
+      uint32_t x[kExRows];
+#pragma unroll
+      for (uint32_t j = 0; j < kExRows; ++j)
+        x[j] = r0 + j < r_end ? Dc[(size_t)crow_of[r0 + j] * cpitch + gc] : 0xFFFFu;
+      T[lc] = make_uint4(x[0] | x[1] << 16, x[2] | x[3] << 16, x[4] | x[5] << 16, x[6] | x[7] << 16);
+    }
+    __syncthreads();
+    uint4 t[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) t[k] = T[cl[k]];
+#pragma unroll
+    for (uint32_t j = 0; j < kExRows; ++j) {
+      const uint32_t r = r0 + j;
+      if (r >= r_end) break;  // uniform
+      uint32_t d[4];  // 0xFFFF sign-extends to kInf; finite distances stay below 2^15
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const uint32_t pair = j / 2 == 0 ? t[k].x : j / 2 == 1 ? t[k].y : j / 2 == 2 ? t[k].z : t[k].w;
+        d[k] = (uint32_t)(int32_t)(int16_t)(pair >> (16 * (j & 1)));
+      }
+      const uint32_t self = closure[r] - v0;  // the row's own node: distance 0
+      if (closure[r] - cbase < kExNodes) {    // uniform
+#pragma unroll
+        for (int k = 0; k < 4; ++k) d[k] = self == (uint32_t)k ? 0u : d[k];
+      }
+      if (d_live) {
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        const u32x4 o = {d[0], d[1], d[2], d[3]};
+        __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(D + (size_t)r * pitch + v0));
+      }
+      if (n_live) {
+        uint32_t b = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) b |= (d[k] == kInf ? 0xFFu : min(d[k], 254u)) << (8 * k);
+        __builtin_nontemporal_store(b, reinterpret_cast<uint32_t*>(Dn + (size_t)r * npitch + v0));
+      }
+      if (P) {  // uniform
+        uint32_t mine = 0;
+        for (uint32_t b = 0; b < P; ++b) {
+          uint32_t nib = ((d[0] >> b) & 1u) | ((d[1] >> b) & 1u) << 1 | ((d[2] >> b) & 1u) << 2 |
+                         ((d[3] >> b) & 1u) << 3;
+          nib <<= nsh;
+          // lanes ^ 1, ^ 2 (quad permutes), then the other quad of the eight
+          // lanes: row_shl 4 into quads 0 and 2, row_shr 4 into quads 1 and 3
+          nib |= (uint32_t)__builtin_amdgcn_update_dpp(0u, nib, 0xB1, 0xf, 0xf, true);
+          nib |= (uint32_t)__builtin_amdgcn_update_dpp(0u, nib, 0x4E, 0xf, 0xf, true);
+          nib |= (uint32_t)__builtin_amdgcn_update_dpp(0u, nib, 0x104, 0xf, 0x5, true) |
+                 (uint32_t)__builtin_amdgcn_update_dpp(0u, nib, 0x114, 0xf, 0xa, true);
+          mine = pb == b ? nib : mine;
+        }
+        // (plain stores: the next-hop pass reads the planes next, from L2;
+        // streaming ones cost it 12 us on fabric_full)
+        if (s_live) S[(size_t)r * kSlSlots * wpm + (size_t)w * P + pb] = mine;
+      }
+    }
+  }
+}
+
 template <int P>
 struct Planes {
   uint32_t v[P];
@@ -1748,6 +1977,15 @@ bool quotient_allowed(const spf_ctx* c) {
   return !(e && e[0] == '0');
 }
 
+// LDS of class_bfs_kernel (frontiers, row results and visited masks per class,
+// the quotient tables, the flags, the forwards bytes) and of expand_rows_kernel
+// (the staged class rows, the local class list, the class map)
+size_t class_bfs_lds_bytes(uint32_t n_cls, uint32_t n_vrow) {
+  const size_t nvp = (n_vrow + 7u) & ~7u, nc1 = (n_cls + 2u) & ~1u;
+  return 40ull * nc1 + 2ull * (1 + kQChunk) * nvp + 16 + ((n_cls + 15u) & ~15u);
+}
+size_t expand_lds_bytes(uint32_t n_cls) { return 20ull * (kExNodes + 1) + 12 + 4ull * n_cls + 16; }
+
 // Sources per workgroup that spread `rows` over every CU: the fewest rounds
 // of `full`-source workgroups the chip needs, then those rounds filled evenly
 // (a batch costs one edge sweep per level whatever its size, but its stores
@@ -1782,6 +2020,10 @@ bool use_quotient(const spf_ctx* c) {
   const spf_ctx::Quotient& q = c->qt;
   if (!quotient_allowed(c) || q.stale || q.n_cls == 0 || 2 * q.n_edge > c->nb_id.size()) return false;
   return msbfs_q_lds_bytes(c->N, q.n_cls, q.n_vrow) <= kMaxLds;
+}
+
+bool plan_has_narrow(const spf_plan* p) {
+  return !p->exact && !p->big && p->narrow && !p->sdirect && (p->d_Dn.p || p->cls);
 }
 
 // Which BFS variant: the register-plane kernel needs N <= 10240; it wins
@@ -1844,7 +2086,8 @@ spf_status set_lds_limits(spf_ctx* c) {
                        MSB(1), MSB(2), MSB(4), MSB(8), MSB(10), MSB(12), MSB(16),
                        MSQ(1), MSQ(2), MSQ(4), MSQ(8), MSQ(10), MSQ(12),
 #define PLB(o) (const void*)msbfs_planes_kernel<o, false>, (const void*)msbfs_planes_kernel<o, true>
-                       PLB(1), PLB(2), PLB(4), PLB(8), PLB(10)};
+                       PLB(1), PLB(2), PLB(4), PLB(8), PLB(10),
+                       (const void*)class_bfs_kernel, (const void*)expand_rows_kernel};
 #undef PLB
 #undef MSQ
 #undef MSB
@@ -2103,6 +2346,41 @@ spf_status launch_ecmp_sliced(spf_ctx* c, spf_plan* p, const uint32_t* D, bool h
   return SPF_OK;
 }
 
+// Class rows need the quotient sweep and both kernels' tables in LDS.
+bool class_rows_fit(const spf_ctx* c) {
+  return use_quotient(c) && class_bfs_lds_bytes(c->qt.n_cls, c->qt.n_vrow) <= kMaxLds &&
+         expand_lds_bytes(c->qt.n_cls) <= kMaxLds;
+}
+
+// The plan's class sources, spread over the CUs as ms_batch spreads rows.
+spf_status launch_class_bfs(spf_ctx* c, spf_plan* p, hipStream_t s) {
+  const uint32_t bs = ms_batch(c, p->cls_k);
+  hipLaunchKernelGGL(class_bfs_kernel, dim3((p->cls_k + bs - 1) / bs), dim3(kMsThreads),
+                     class_bfs_lds_bytes(c->qt.n_cls, c->qt.n_vrow), s, c->d_qcls.p, c->d_qtab.p,
+                     c->qt.n_cls, c->qt.n_vrow, p->d_csrc.p, p->cls_k, bs, p->d_cfwd.p, p->d_Dc.p,
+                     p->cls_pitch, p->d_maxd.p);
+  HIP_TRY(c, hipGetLastError());
+  return SPF_OK;
+}
+
+// The closure rows from the class rows: u32 rows into D, bit planes into S,
+// u8 rows into Dn (each optional).  Node chunks x row ranges, about eight
+// workgroups per CU, ranges whole row groups.
+spf_status launch_expand(spf_ctx* c, spf_plan* p, uint32_t* D, uint8_t* Dn, uint32_t* S,
+                         hipStream_t s) {
+  const uint32_t rows = (uint32_t)p->closure.size();
+  const uint32_t span = std::max(D ? c->pitch : 0u, Dn ? c->npitch : 0u);
+  const uint32_t chunks = std::max(1u, (span + kExNodes - 1) / kExNodes);
+  const uint32_t ranges = std::max(1u, 8 * c->n_cu / chunks);
+  const uint32_t rows_per = ((rows + ranges - 1) / ranges + kExRows - 1) / kExRows * kExRows;
+  hipLaunchKernelGGL(expand_rows_kernel, dim3(chunks, (rows + rows_per - 1) / rows_per),
+                     dim3(kExThreads), expand_lds_bytes(c->qt.n_cls), s, p->d_Dc.p, p->cls_pitch,
+                     p->d_crow_of.p, p->d_closure.p, rows, rows_per, c->d_qcls.p, c->qt.n_cls, c->N,
+                     c->pitch, c->npitch, D, Dn, S, p->d_maxd.p);
+  HIP_TRY(c, hipGetLastError());
+  return SPF_OK;
+}
+
 // The environment's knobs of a plan build (experiments, A/B runs, tests), read
 // anew by every build: tests change them between plan creations.
 struct PlanKnobs {
@@ -2112,6 +2390,7 @@ struct PlanKnobs {
   bool wsliced = true;   // SPF_WSLICED=0: weighted plans keep byte rows
   bool expand = false;   // SPF_EXPAND=1: the slicing pass expands the u32 rows
   bool sdirect = true;   // SPF_SDIRECT=0: team plans never slice their rows themselves
+  bool class_rows = true;  // SPF_CLASS_ROWS=0: quotient plans keep msbfs_kernel's node rows
   int64_t ecmp_runs = -1;    // SPF_ECMP_RUNS: source runs per XCD (-1: by the plan's size)
   int64_t sliced_unit = -1;  // SPF_SLICED_UNIT: matches per work unit (-1: plan_sliced_unit)
   int sliced_group = 2;      // SPF_SLICED_GROUP: plan_sliced_units' group mode
@@ -2134,6 +2413,7 @@ PlanKnobs plan_knobs() {
   k.wsliced = first("SPF_WSLICED") != '0';
   k.expand = first("SPF_EXPAND") == '1';
   k.sdirect = first("SPF_SDIRECT") != '0';
+  k.class_rows = first("SPF_CLASS_ROWS") != '0';
   k.ecmp_runs = number("SPF_ECMP_RUNS");
   k.sliced_unit = number("SPF_SLICED_UNIT");
   if (const char* e = std::getenv("SPF_SLICED_GROUP")) k.sliced_group = atoi(e);
@@ -2264,6 +2544,24 @@ spf_status build_plan(spf_ctx* c, spf_plan* p) {
       if (st != SPF_OK) return st;
     }
   }
+  // class rows: one BFS row per twin class among the closure rows, the node
+  // rows expanded from those (SPF_CLASS_ROWS=0: msbfs_kernel's rows, A/B)
+  p->cls = false;
+  p->cls_ready = false;
+  ClassRows cr;
+  if (p->ms && !p->tm_G && !use_planes(c) && kn.class_rows && quotient_allowed(c)) {
+    const spf_status st = quotient_prepare(c);
+    if (st != SPF_OK) return st;
+    p->cls = class_rows_fit(c);
+  }
+  if (p->cls) {
+    cr = plan_class_rows(*c, p->closure);
+    p->cls_k = (uint32_t)cr.csrc.size();
+    p->cls_pitch = (c->qt.n_cls + 63u) & ~63u;
+    HIP_TRY(c, stage_upload(c, p->d_csrc, cr.csrc.data(), cr.csrc.size()));
+    HIP_TRY(c, stage_upload(c, p->d_crow_of, cr.crow_of.data(), cr.crow_of.size()));
+    HIP_TRY(c, stage_upload(c, p->d_cfwd, cr.fwd.data(), cr.fwd.size()));
+  }
   // weighted: S sources per workgroup on mssp_kernel where it applies
   PD("team");
   p->mp = !p->ms && !hop && mssp_words(c) > 0;
@@ -2289,7 +2587,10 @@ spf_status build_plan(spf_ctx* c, spf_plan* p) {
   // latency-bound sweeps (+0.06 ms on fabric_full) where a separate
   // streaming pass costs 0.14 ms and a fused one 0.14 ms of the next-hop
   // kernel's time (r02_v25/r02_v26)
-  p->expand = p->sliced && c->pitch <= c->npitch && kn.expand;
+  p->expand = p->sliced && c->pitch <= c->npitch && kn.expand && !p->cls;
+  // class plans write u8 rows only for whoever reads them: the byte-row
+  // next-hop pass (SPF_NARROW=1), or a caller that asked (plan_ensure_narrow)
+  if (p->cls && p->narrow && !p->sliced) p->keep_narrow = true;
   // team plans whose depth stays below the planes' all-ones code write the
   // sliced rows themselves: no u8 rows, no slicing pass (SPF_SDIRECT=0: A/B)
   p->sdirect = p->sliced && p->nh_total && p->tm_G && p->prefix && !p->expand &&
@@ -2327,7 +2628,8 @@ spf_status build_plan(spf_ctx* c, spf_plan* p) {
   stage_done(c);
   PD("units+slots");
   if (!p->direct) HIP_TRY(c, p->d_D.alloc(n_rows * c->pitch));
-  if (p->narrow && !p->sdirect) {  // narrow rows + the dead row (all 0xFF) of the next-hop pass
+  if (p->cls) HIP_TRY(c, p->d_Dc.alloc((size_t)p->cls_k * p->cls_pitch));
+  if (p->narrow && !p->sdirect && (!p->cls || p->keep_narrow)) {  // narrow rows + the dead row (all 0xFF) of the next-hop pass
     HIP_TRY(c, p->d_Dn.alloc((n_rows + 1) * c->npitch));
     HIP_TRY(c, hipMemsetAsync(p->d_Dn.p + n_rows * c->npitch, 0xFF, c->npitch, c->stream));
   }
@@ -2338,8 +2640,8 @@ spf_status build_plan(spf_ctx* c, spf_plan* p) {
       return fail(c, SPF_E_UNSUPPORTED, "sliced rows exceed 32-bit offsets");
     HIP_TRY(c, p->d_S.alloc((n_rows + 1) * rstride + pad));
     HIP_TRY(c, hipMemsetAsync(p->d_S.p + n_rows * rstride, 0xFF, (rstride + pad) * 4, c->stream));
-    HIP_TRY(c, p->d_maxd.alloc(1));
   }
+  if (p->sliced || p->cls) HIP_TRY(c, p->d_maxd.alloc(1));
   {
     const spf_status st = set_lds_limits(c);  // kernels need > 64 KiB of dynamic LDS
     if (st != SPF_OK) return st;
@@ -2352,6 +2654,24 @@ spf_status build_plan(spf_ctx* c, spf_plan* p) {
 }
 
 }  // namespace
+
+namespace spfi {
+
+spf_status plan_ensure_narrow(spf_plan* p, hipStream_t s) {
+  spf_ctx* c = p->ctx;
+  if (!plan_has_narrow(p)) return fail(c, SPF_E_UNSUPPORTED, "the plan keeps no u8 rows");
+  if (!p->cls || p->keep_narrow) return SPF_OK;
+  // a class plan asked for the first time: the rows of its last execute from
+  // that execute's class rows, and every later expansion writes them too
+  const size_t n_rows = p->closure.size();
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, p->d_Dn.alloc((n_rows + 1) * c->npitch));
+  HIP_TRY(c, hipMemsetAsync(p->d_Dn.p + n_rows * c->npitch, 0xFF, c->npitch, s));
+  p->keep_narrow = true;
+  return p->cls_ready ? launch_expand(c, p, nullptr, p->d_Dn.p, nullptr, s) : SPF_OK;
+}
+
+}  // namespace spfi
 
 extern "C" {
 
@@ -2450,6 +2770,13 @@ void spf_plan_destroy(spf_plan* p) { delete p; }
 uint64_t spf_plan_nh_words(const spf_plan* p) { return p ? p->nh_total : 0; }
 uint32_t spf_plan_closure_rows(const spf_plan* p) { return p ? (uint32_t)p->closure.size() : 0; }
 
+spf_status spf_plan_class_rows(const spf_plan* p, uint32_t* n_class_sources, uint32_t* in_use) {
+  if (!p) return SPF_E_INVALID;
+  if (n_class_sources) *n_class_sources = p->cls ? p->cls_k : 0u;
+  if (in_use) *in_use = p->cls ? 1u : 0u;
+  return SPF_OK;
+}
+
 spf_status spf_plan_kernels(const spf_plan* p, uint32_t* bfs, uint32_t* narrow) {
   if (!p || !bfs || !narrow) return SPF_E_INVALID;
   *bfs = p->big ? 4u : p->exact ? 3u : p->mp ? 5u : !p->ms ? 0u : p->tm_G ? 6u
@@ -2509,6 +2836,11 @@ spf_status spf_plan_traffic_phases(const spf_plan* p, uint64_t* bytes) {
     const uint64_t wbytes = 4ull * (c->pitch / 32);
     bfs = batches * (8ull * c->sell_ptr.back() + N) + (direct ? p->n_src : rows) * c->pitch * 4ull +
           (p->sdirect ? rows * kTeamPlanes * wbytes : p->narrow ? rows * c->npitch : 0ull);
+  } else if (p->cls) {  // class BFS: the quotient tables and the forwards bytes per workgroup, Dc written
+    const uint64_t bs = ms_batch(c, p->cls_k, false);
+    const uint64_t groups = (p->cls_k + bs - 1) / bs;
+    bfs = groups * (2ull * (c->qt.cls.size() + c->qt.tab.size()) + c->qt.n_cls) +
+          2ull * p->cls_k * p->cls_pitch;
   } else if (p->ms) {
     const bool planes = use_planes(c);
     // (the model takes neither SPF_MSBFS_BATCH nor a deepest-first order into account)
@@ -2531,6 +2863,11 @@ spf_status spf_plan_traffic_phases(const spf_plan* p, uint64_t* bytes) {
     bfs = rows * (4ull * (N + 1) + 8ull * E + N + 4ull * c->pitch + (p->narrow ? c->npitch : 0ull));
   }
   *bfs_bytes = bfs;
+  // expansion: Dc and the class ids read, the u32 rows (and kept u8 rows) written
+  const uint64_t cls_expand = p->cls ? 2ull * p->cls_k * p->cls_pitch + 2ull * N + rows * 4ull * c->pitch +
+                                           (p->keep_narrow ? rows * c->npitch : 0ull)
+                                     : 0ull;
+  bytes[1] = cls_expand;
   if (p->sliced && p->nh_total) {
     // planes in use: from the last execute's deepest level (one 4-byte read)
     // (sdirect: kTeamPlanes planes written by the BFS itself, no slicing pass)
@@ -2544,10 +2881,10 @@ spf_status spf_plan_traffic_phases(const spf_plan* p, uint64_t* bytes) {
     const uint64_t expand = p->expand ? rows * 4ull * c->pitch : 0ull;  // u32 rows written
     if (md < kSlSat) {
       const uint64_t P = 32u - __builtin_clz(md + 1u);
-      bytes[1] = rows * c->npitch + rows * P * wbytes + expand;
+      bytes[1] = p->cls ? cls_expand + rows * P * wbytes : rows * c->npitch + rows * P * wbytes + expand;
       *ecmp_bytes = rows * P * wbytes + 4ull * p->nh_total;
     } else {
-      bytes[1] = expand ? rows * c->npitch + expand : 0ull;
+      bytes[1] = p->cls ? cls_expand : expand ? rows * c->npitch + expand : 0ull;
       *ecmp_bytes = rows * 4ull * c->pitch + 4ull * p->nh_total;
     }
     return SPF_OK;
@@ -2583,7 +2920,7 @@ spf_status spf_plan_execute(spf_plan* p, uint32_t* d_dist, uint32_t* d_nh, void*
                                     "created (its next-hop layout): recreate it", p->srcs[i]);
     p->layout = c->layout;
   }
-  if (p->epoch != c->epoch || (p->tm_G && c->team_off)) {
+  if (p->epoch != c->epoch || (p->tm_G && c->team_off) || (p->cls && !use_quotient(c))) {
     // patched in place, or teams turned off by a timeout: re-derive, same
     // output layout
     const spf_status st = build_plan(c, p);
@@ -2618,7 +2955,7 @@ spf_status spf_plan_execute(spf_plan* p, uint32_t* d_dist, uint32_t* d_nh, void*
   uint32_t* D = (p->direct || team_direct) ? d_dist : p->d_D.p;
   const uint32_t rows = (uint32_t)p->closure.size();
   const bool sliced = p->sliced && p->nh_total;
-  if (sliced && !p->sdirect)  // msbfs_kernel's atomicMax target (sdirect plans: planes fixed)
+  if ((sliced && !p->sdirect) || p->cls)  // the BFS's atomicMax target (sdirect plans: planes fixed)
     HIP_TRY(c, hipMemsetAsync(p->d_maxd.p, 0, 4, s));
   hipEvent_t* ev = nullptr;
   if (p->timing_cap) {
@@ -2627,7 +2964,8 @@ spf_status spf_plan_execute(spf_plan* p, uint32_t* d_dist, uint32_t* d_nh, void*
     HIP_TRY(c, hipEventRecord(ev[0], s));
   }
   spf_status st =
-      p->tm_G ? launch_msbfs_team(c, p, p->d_closure.p, rows, D,
+      p->cls ? launch_class_bfs(c, p, s)
+      : p->tm_G ? launch_msbfs_team(c, p, p->d_closure.p, rows, D,
                                   p->narrow && !p->sdirect ? p->d_Dn.p : nullptr,
                                   sliced && !p->sdirect ? p->d_maxd.p : nullptr, s,
                                   team_direct ? p->n_src : rows,
@@ -2643,7 +2981,11 @@ spf_status spf_plan_execute(spf_plan* p, uint32_t* d_dist, uint32_t* d_nh, void*
                                       nullptr, p->narrow ? p->d_Dn.p : nullptr);
   if (st != SPF_OK) return st;
   if (ev) HIP_TRY(c, hipEventRecord(ev[1], s));
-  if (sliced && !p->sdirect) {
+  if (p->cls) {  // (the phase timed as slicing)
+    st = launch_expand(c, p, D, p->keep_narrow ? p->d_Dn.p : nullptr, sliced ? p->d_S.p : nullptr, s);
+    if (st != SPF_OK) return st;
+    p->cls_ready = true;
+  } else if (sliced && !p->sdirect) {
     st = launch_sliced(c, p, D, hop, d_nh, s);
     if (st != SPF_OK) return st;
   }
@@ -2667,11 +3009,13 @@ spf_status spf_plan_execute(spf_plan* p, uint32_t* d_dist, uint32_t* d_nh, void*
 spf_status spf_plan_copy_narrow_rows(spf_plan* p, uint8_t* d_out, void* stream) {
   if (!p || !d_out) return fail(p ? p->ctx : nullptr, SPF_E_INVALID, "spf_plan_copy_narrow_rows: NULL");
   spf_ctx* c = p->ctx;
-  if (p->exact || p->big || !p->narrow || !p->d_Dn.p)
+  if (!plan_has_narrow(p))
     return fail(c, SPF_E_UNSUPPORTED, "spf_plan_copy_narrow_rows: the plan keeps no u8 rows");
   if (c->npitch != c->pitch)
     return fail(c, SPF_E_UNSUPPORTED, "spf_plan_copy_narrow_rows: u8 and u32 row pitches differ");
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  const spf_status st = plan_ensure_narrow(p, s);
+  if (st != SPF_OK) return st;
   hipLaunchKernelGGL(gather_rows_u8_kernel, dim3(std::min<uint32_t>((c->npitch / 16 + 255) / 256, 64), p->n_src),
                      dim3(256), 0, s, p->d_Dn.p, c->npitch, p->d_req_rows.p, d_out);
   HIP_TRY(c, hipGetLastError());
