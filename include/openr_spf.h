@@ -520,6 +520,64 @@ spf_status spf_whatif_enable_timing(spf_whatif_plan* plan, uint32_t max_executes
 /* summed ms of the unfailed solve (SPF + next hops + hash) and of the failures */
 spf_status spf_whatif_timing(spf_whatif_plan* plan, double* base_ms, double* fail_ms,
                              uint32_t* n);
+/* ---- what-if change lists: what each failure changes, not only its digest.
+ * For failure i of the plan's list: the nodes v whose metric changed, whose
+ * nextHops() changed or which became unreachable under runSpf(src, true,
+ * {l_i}) against the unfailed runSpf(src) -- the union of what n_dist_changed
+ * and n_nh_changed count.  Per entry:
+ *   node      u32  csr id
+ *   dist      u64  the new metric, UINT64_MAX when v is now unreachable (u64 so
+ *                  that exact / u64-label plans share the layout)
+ *   nh[W]     u32  the new next-hop set, the digest's bitset (bits over the
+ *                  distinct up neighbours of src in the unfailed graph,
+ *                  ascending id), W = max(1, ceil(k / 32)); all zero when v is
+ *                  unreachable
+ * One exactly sized set per plan, on the device until the next call:
+ *   cptr[n_fail + 1]   u64  failure i owns entries cptr[i] .. cptr[i + 1]
+ *   cnode[total]       u32
+ *   cdist[total]       u64
+ *   cnh[total * W]     u32
+ * A cold failure owns none.  The order of a failure's entries on the device
+ * is unspecified (spf_whatif_changes_db sorts).  Built as count, exclusive
+ * scan, fill: the repairs run twice, the second time writing entry k of
+ * failure i at cptr[i] + k; a repair that meets more entries than were
+ * counted for it drops them and the call reports SPF_E_HIP.
+ *
+ * spf_whatif_changes does what spf_whatif_execute does plus the lists: d_out
+ * ([n_fail]) and d_base are optional device digests, equal to
+ * spf_whatif_execute's.  *n_entries = total, *pool_bytes = 8 (n_fail + 1) +
+ * total (12 + 4 W), *kernel_ms = count + scan + fill (spf_whatif_changes_timing:
+ * apart); the outputs are optional.  Waits (the scan's total is read to size
+ * the pools, which are kept while they are large enough).  SPF_E_NOMEM: the
+ * pools do not fit beside the repair scratch; SPF_E_STATE: the graph changed
+ * since the plan was created.  After a failed call the plan holds no lists. */
+spf_status spf_whatif_changes(spf_whatif_plan* plan, spf_whatif_digest* d_out,
+                              spf_whatif_digest* d_base, uint64_t* n_entries,
+                              uint64_t* pool_bytes, double* kernel_ms, void* stream);
+/* ms[3] = count pass, scan, fill pass of the last spf_whatif_changes. */
+spf_status spf_whatif_changes_timing(const spf_whatif_plan* plan, double* ms);
+/* Failure i's entries, ascending by node (sorted on the host): *n of them;
+ * node[cap], dist[cap], nh[cap * W] are filled when cap >= *n, SPF_E_NOMEM
+ * (with *n set) otherwise.  Every output may be NULL.  SPF_E_STATE when the
+ * plan holds no lists. */
+spf_status spf_whatif_changes_db(spf_whatif_plan* plan, uint32_t i, uint32_t* node, uint64_t* dist,
+                                 uint32_t* nh, uint64_t cap, uint64_t* n);
+/* The whole set in one copy per array, in device order: ptr[n_fail + 1],
+ * node[total], dist[total], nh[total * W], total = a previous call's
+ * n_entries.  Every output may be NULL.  SPF_E_STATE when the plan holds no
+ * lists. */
+spf_status spf_whatif_changes_read(spf_whatif_plan* plan, uint64_t* ptr, uint32_t* node,
+                                   uint64_t* dist, uint32_t* nh);
+/* The device arrays, for device-side consumers (valid until the next
+ * spf_whatif_changes on the plan); every output may be NULL. */
+spf_status spf_whatif_changes_buffers(spf_whatif_plan* plan, const uint64_t** d_ptr,
+                                      const uint32_t** d_node, const uint64_t** d_dist,
+                                      const uint32_t** d_nh, uint32_t* W, uint64_t* n_entries);
+/* The unfailed result the lists are a patch against: dist[n_nodes] (UINT64_MAX
+ * = unreachable), nh[n_nodes * W] in the same bitset (zero rows for
+ * unreachable nodes), *W; every output may be NULL.  Waits for the last
+ * execute / changes call; SPF_E_STATE before the first. */
+spf_status spf_whatif_base(spf_whatif_plan* plan, uint64_t* dist, uint32_t* nh, uint32_t* W);
 /* Convenience: plan + execute + copy back. out = [n_fail] (n_fail = number of
  * up links when fail_links is NULL), base may be NULL. */
 spf_status spf_whatif_solve(spf_ctx* ctx, uint32_t src, const uint32_t* fail_links,

@@ -108,6 +108,21 @@ struct ExactScratch {
 // What-if batches on the exact kernel (zero / negative metrics, u64): one
 // replayed runSpf per failure that touches a pathLink, digests vs the
 // unfailed run (exact.hip).
+// Change lists of a what-if batch (spf_whatif_changes; the EMIT instances of
+// the repair kernels and of exact_whatif_kernel).  Count pass (cnode NULL): a
+// team writes cnt[f] = the entries of failure f.  Fill pass: failure f's
+// entries go to cptr[f] .. cptr[f + 1]; an entry past cptr[f + 1] sets bit 6
+// of the context's fault word and is dropped.
+struct WiEmit {
+  uint32_t* cnt = nullptr;                    // [n_fail], zeroed before the count pass
+  const unsigned long long* cptr = nullptr;   // [n_fail + 1] scanned counts
+  uint32_t* cnode = nullptr;                  // [total]
+  unsigned long long* cdist = nullptr;        // [total] (~0: now unreachable)
+  uint32_t* cnh = nullptr;                    // [total][W]
+  uint32_t W = 1;                             // words per entry
+  uint32_t* fault = nullptr;
+};
+
 struct ExactWhatIf {
   ExactScratch xs;
   DevBuf<uint32_t> fails, link_edge, base_pop, base_nh;
@@ -425,9 +440,11 @@ spf_status exact_reserve(spf_ctx* c, ExactScratch* x, uint32_t n_src, uint32_t W
 spf_status exact_whatif_prepare(spf_ctx* c, ExactWhatIf* x, uint32_t src,
                                 const std::vector<uint32_t>& fails,
                                 const std::vector<uint32_t>& link_edge);
+// em (change lists): the EMIT instance, one pass (count or fill) per call;
+// base_run false skips the unfailed run (the fill pass: base_* are there).
 spf_status exact_whatif_launch(spf_ctx* c, ExactWhatIf* x, spf_whatif_digest* d_out,
-                               spf_whatif_digest* d_base, hipStream_t s, hipEvent_t mid);
-spf_status exact_ksp2_prepare(spf_ctx* c, ExactKsp2* x, const std::vector<uint32_t>& srcs);
+                               spf_whatif_digest* d_base, hipStream_t s, hipEvent_t mid,
+                               const WiEmit* em = nullptr, bool base_run = true);spf_status exact_ksp2_prepare(spf_ctx* c, ExactKsp2* x, const std::vector<uint32_t>& srcs);
 spf_status exact_ksp2_launch(spf_ctx* c, ExactKsp2* x, spf_ksp2_pair* d_pairs, uint32_t* d_pool,
                              uint64_t pool_words, uint64_t* d_counters, hipStream_t s,
                              hipEvent_t mid);

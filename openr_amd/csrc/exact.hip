@@ -309,7 +309,18 @@ __device__ bool base_tight(const ExactArgs& a, const ExactWiArgs& w, uint32_t e,
   return w.base_d[u] + (uint64_t)(int64_t)a.met[e] == w.base_d[v];
 }
 
-__global__ __launch_bounds__(kExactThreads) void exact_whatif_kernel(ExactArgs a, ExactWiArgs w) {
+// the EMIT instance's trailing argument (a pack: the production instance
+// keeps its argument list)
+__device__ __forceinline__ const WiEmit* emit_arg(const WiEmit& e) { return &e; }
+
+// EMIT (spf_whatif_changes): after a failure's digest the wave also counts
+// (em.cnode NULL) or writes the failure's change list -- the nodes whose label
+// or next-hop words differ from the unfailed run, ascending within the wave's
+// strides by ballot compaction; a cold failure has none (its count stays 0).
+template <bool EMIT = false, class... EM>
+__global__ __launch_bounds__(kExactThreads) void exact_whatif_kernel(ExactArgs a, ExactWiArgs w,
+                                                                     EM... em) {
+  static_assert(sizeof...(EM) == (EMIT ? 1 : 0), "EMIT: one WiEmit");
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t wave = (uint64_t)blockIdx.x * (kExactThreads / 64) + (threadIdx.x >> 6);
   if (wave >= a.waves) return;
@@ -363,6 +374,41 @@ __global__ __launch_bounds__(kExactThreads) void exact_whatif_kernel(ExactArgs a
       nn += __shfl_xor(nn, o, 64);
     }
     if (lane == 0) w.out[i] = spf_whatif_digest{nd, nn, h};
+    if constexpr (EMIT) {
+      const WiEmit& e = *emit_arg(em...);
+      const bool fill = e.cnode != nullptr;
+      const uint64_t at = fill ? e.cptr[i] : 0ull;
+      const uint32_t room = fill ? (uint32_t)(e.cptr[i + 1] - at) : 0u;
+      uint32_t kq = 0;
+      for (uint32_t v0 = 0; v0 < N && !w.base_run; v0 += 64) {  // wave-uniform
+        const uint32_t v = v0 + lane;
+        bool done = false, changed = false;
+        uint64_t d = ~0ull;
+        if (v < N) {
+          done = s.state[v] == kDone;
+          d = done ? s.key[v] : ~0ull;
+          changed = d != w.base_d[v];
+          for (uint32_t x = 0; done && x < Wk && !changed; ++x)
+            changed = s.nh[(size_t)v * W + x] != w.base_nh[(size_t)v * W + x];
+        }
+        const uint64_t m = __ballot(changed);
+        if (fill && changed) {
+          const uint32_t q = kq + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
+                                                            __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+          if (q < room) {
+            __builtin_nontemporal_store(v, &e.cnode[at + q]);
+            __builtin_nontemporal_store((unsigned long long)d, &e.cdist[at + q]);
+            for (uint32_t x = 0; x < e.W; ++x)  // an unreachable node: zeros, not the stale row
+              __builtin_nontemporal_store(done && x < Wk ? s.nh[(size_t)v * W + x] : 0u,
+                                          &e.cnh[(at + q) * e.W + x]);
+          } else if (e.fault) {
+            __hip_atomic_fetch_or(e.fault, 64u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          }
+        }
+        kq += (uint32_t)__popcll(m);
+      }
+      if (!fill && lane == 0 && !w.base_run) e.cnt[i] = kq;
+    }
     wave_fence();
   }
 }
@@ -619,15 +665,18 @@ spf_status exact_whatif_prepare(spf_ctx* c, ExactWhatIf* x, uint32_t src,
 }
 
 spf_status exact_whatif_launch(spf_ctx* c, ExactWhatIf* x, spf_whatif_digest* d_out,
-                               spf_whatif_digest* d_base, hipStream_t s, hipEvent_t mid) {
+                               spf_whatif_digest* d_base, hipStream_t s, hipEvent_t mid,
+                               const WiEmit* em, bool base_run) {
   ExactArgs a{c->d_row_ptr.p, c->d_col.p, c->d_met.p, c->d_ovl.p, c->d_link.p, nullptr,
               c->d_nb_ptr.p, c->d_nb_id.p, nullptr, 0, c->N, c->pitch, 0u, 1u, x->xs.wmax,
               nullptr, nullptr, nullptr, nullptr, x->xs.buf.p, x->xs.per_wave, x->xs.ctr.p, 1u};
   ExactWiArgs w{x->fails.p, x->link_edge.p, c->d_rev.p, x->n_fail, x->src, x->base_d.p,
                 x->base_pop.p, x->base_nh.p, x->base_dig.p, 1u};
-  HIP_TRY(c, hipMemsetAsync(x->xs.ctr.p, 0, 4, s));
-  hipLaunchKernelGGL(exact_whatif_kernel, dim3(1), dim3(kExactThreads), 0, s, a, w);
-  HIP_TRY(c, hipGetLastError());
+  if (base_run) {
+    HIP_TRY(c, hipMemsetAsync(x->xs.ctr.p, 0, 4, s));
+    hipLaunchKernelGGL(exact_whatif_kernel<false>, dim3(1), dim3(kExactThreads), 0, s, a, w);
+    HIP_TRY(c, hipGetLastError());
+  }
   if (d_base)
     HIP_TRY(c, hipMemcpyAsync(d_base, x->base_dig.p, sizeof(spf_whatif_digest), hipMemcpyDeviceToDevice, s));
   if (mid) HIP_TRY(c, hipEventRecord(mid, s));
@@ -636,7 +685,12 @@ spf_status exact_whatif_launch(spf_ctx* c, ExactWhatIf* x, spf_whatif_digest* d_
   w.out = d_out;
   w.base_run = 0;
   HIP_TRY(c, hipMemsetAsync(x->xs.ctr.p, 0, 4, s));
-  hipLaunchKernelGGL(exact_whatif_kernel, dim3((a.waves + 3) / 4), dim3(kExactThreads), 0, s, a, w);
+  if (em)
+    hipLaunchKernelGGL((exact_whatif_kernel<true, WiEmit>), dim3((a.waves + 3) / 4), dim3(kExactThreads),
+                       0, s, a, w, *em);
+  else
+    hipLaunchKernelGGL(exact_whatif_kernel<false>, dim3((a.waves + 3) / 4), dim3(kExactThreads), 0, s, a,
+                       w);
   HIP_TRY(c, hipGetLastError());
   hipLaunchKernelGGL(exact_whatif_fill_kernel, dim3((x->n_fail + 255) / 256), dim3(256), 0, s, d_out,
                      x->n_fail, x->base_dig.p);

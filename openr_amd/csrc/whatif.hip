@@ -950,6 +950,65 @@ __device__ __forceinline__ void stq(unsigned long long* p, unsigned long long v)
   else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// ---- change lists (spf_whatif_changes): the EMIT instances ----
+// The kernels' optional trailing argument (a pack: the production instances
+// keep their argument list).
+__device__ __forceinline__ const WiEmit* emit_arg() { return nullptr; }
+__device__ __forceinline__ const WiEmit* emit_arg(const WiEmit& e) { return &e; }
+
+// Is D node i (graph node v, new distance d1) an entry of its failure's list:
+// its metric or its next-hop row differs from the unfailed result.  (A node
+// of D is reachable in the unfailed run, so becoming unreachable is a metric
+// change.)
+template <bool GROUP>
+__device__ __forceinline__ bool entry_changed(const WiBase& B, const uint32_t* nhn, uint32_t W,
+                                              uint32_t v, uint32_t i, uint32_t d1) {
+  bool changed = d1 != B.dist[v];
+  for (uint32_t w = 0; w < W && !changed; ++w)
+    changed = B.nhb[(size_t)v * W + w] != ldw<GROUP>(&nhn[(size_t)i * W + w]);
+  return changed;
+}
+
+// Fill pass, one wave's chunk of D: the lanes in `m` (= __ballot(changed))
+// hold an entry each, which goes to at + q0 + (its rank in m) of the pools --
+// node, metric (~0 when unreachable) and the W words of its new row (zeros
+// when unreachable, not the stale row).  Rows of up to 4 words are copied by
+// the entry's own lane, wider ones by the wave, lane = word.  Nothing reads
+// the pools again on the device: streaming stores.  An entry past the
+// failure's allocated count (`room`) is dropped and sets bit 6 of the fault
+// word.  Every lane of the wave must be active.
+template <bool GROUP>
+__device__ __forceinline__ void emit_entries(const WiEmit& em, uint64_t at, uint32_t room,
+                                             uint32_t q0, uint64_t m, bool changed, uint32_t v,
+                                             uint32_t i, uint32_t d1, const uint32_t* nhn,
+                                             uint32_t lane) {
+  const uint32_t W = em.W;
+  const uint32_t q = q0 + lanes_below(m);
+  const bool put = changed && q < room;
+  if (changed && !put && em.fault)
+    __hip_atomic_fetch_or(em.fault, 64u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (put) {
+    __builtin_nontemporal_store(v, &em.cnode[at + q]);
+    __builtin_nontemporal_store(d1 == kInf ? ~0ull : (unsigned long long)d1, &em.cdist[at + q]);
+  }
+  if (W <= 4) {
+    if (put)
+      for (uint32_t w = 0; w < W; ++w)
+        __builtin_nontemporal_store(d1 == kInf ? 0u : ldw<GROUP>(&nhn[(size_t)i * W + w]),
+                                    &em.cnh[(at + q) * W + w]);
+  } else {
+    for (uint64_t r = m; r; r &= r - 1) {  // wave-uniform
+      const uint32_t bl = __ffsll((unsigned long long)r) - 1;
+      const uint32_t qb = __builtin_amdgcn_readlane(q, bl);
+      if (qb >= room) continue;
+      const uint32_t ib = __builtin_amdgcn_readlane(i, bl), db = __builtin_amdgcn_readlane(d1, bl);
+      for (uint32_t j = lane; j < W; j += 64)
+        __builtin_nontemporal_store(db == kInf ? 0u : ldw<GROUP>(&nhn[(size_t)ib * W + j]),
+                                    &em.cnh[(at + qb) * W + j]);
+    }
+  }
+}
+
 // FNV-1a of both next-hop rows of a D node and whether they differ: the
 // words in batches of 8, loads of a batch in flight together.  A node's hash
 // is mix64(mix64(v + 1) + d) ^ FNV-1a(row), as in the base pass's result hash.
@@ -1074,11 +1133,13 @@ __device__ __forceinline__ void ph_max(uint64_t* ph, int k, uint64_t v, bool lea
 // index is range-checked before use; an out-of-range one sets bit 4 of the
 // fault word with the site in bits 16-23 and is replaced by a safe value
 // (results then invalid, reported by spf_device_check).
-template <int TEAM, bool GROUP = false, bool CHK = false, bool GPH = false>
+// EMIT (spf_whatif_changes): the repair also counts (em->cnode NULL) or
+// writes (fill pass) failure f's change list, before the digest loop.
+template <int TEAM, bool GROUP = false, bool CHK = false, bool GPH = false, bool EMIT = false>
 __device__ bool repair(const WiGraph& g, const WiBase& B, uint32_t* mark, uint32_t* dlist,
                        uint32_t* dnew, uint32_t* nhn, uint32_t* lvl, uint32_t* ord, uint32_t cap,
                        TeamCtl* ctl, uint32_t tt, uint32_t e_fail, spf_whatif_digest* out,
-                       uint64_t* ph = nullptr) {
+                       uint64_t* ph = nullptr, const WiEmit* em = nullptr, uint32_t f = 0) {
   // diagnostics (SPF_WHATIF_PROF): 12 counters, accumulated over the team's
   // failures (ph_add) -- [0] repairs, [1..5] 100 MHz ticks in D discovery,
   // seeds, Dial, fallback sweeps, digest; [8] sum |D|, [9] sum Dial levels,
@@ -1459,6 +1520,43 @@ __device__ bool repair(const WiGraph& g, const WiBase& B, uint32_t* mark, uint32
     }
   }
   WI_STAMP(4);
+  if constexpr (EMIT) {
+    // ---- change list: the D nodes whose metric or row changed, a wave per
+    // 64 of them; ctl->n is free (|D| was read into n) and counts the team's
+    // entries -- summed per wave in the count pass, one returning atomic per
+    // wave chunk (ballot + mbcnt ranks) in the fill pass ----
+    const bool fill = em->cnode != nullptr;
+    const uint64_t at = fill ? em->cptr[f] : 0ull;
+    const uint32_t room = fill ? (uint32_t)(em->cptr[f + 1] - at) : 0u;
+    if (tt == 0) stw<GROUP>(&ctl->n, 0u);
+    team_sync<TEAM, GROUP>(ctl, g.fault);
+    uint32_t kw = 0;
+    for (uint32_t c0 = wv * 64; c0 < n; c0 += TEAM) {  // wave-uniform
+      const uint32_t i = c0 + lane;
+      uint32_t v = 0, d1 = kInf;
+      bool changed = false;
+      if (i < n) {
+        v = dlist[i];
+        d1 = ldw<GROUP>(&dnew[i]);
+        changed = entry_changed<GROUP>(B, nhn, W, v, i, d1);
+      }
+      const uint64_t m = __ballot(changed);
+      if (!m) continue;
+      if (fill) {
+        uint32_t q0 = 0;
+        if (lane == 0) q0 = atomicAdd(&ctl->n, (uint32_t)__popcll(m));
+        q0 = __builtin_amdgcn_readlane(q0, 0);
+        emit_entries<GROUP>(*em, at, room, q0, m, changed, v, i, d1, nhn, lane);
+      } else {
+        kw += (uint32_t)__popcll(m);
+      }
+    }
+    if (!fill) {
+      if (lane == 0 && kw) atomicAdd(&ctl->n, kw);
+      team_sync<TEAM, GROUP>(ctl, g.fault);
+      if (tt == 0) em->cnt[f] = ldw<GROUP>(&ctl->n);
+    }
+  }
   // ---- digest delta over D, scratch reset ----
   uint32_t nd_ = 0, nn_ = 0;
   uint64_t dh = 0;
@@ -1549,11 +1647,11 @@ __device__ __forceinline__ uint32_t ws_find(const WaveSet& s, uint32_t v) {
 // (ballot + mbcnt compaction instead of counter atomics); the level list of
 // a D of <= 64 nodes never leaves the registers (ds_permute).  |D| <= cap <=
 // kDialLevels distinct values, so Dial always settles (no fallback sweeps).
-template <bool CHK, bool GPH = false>
+template <bool CHK, bool GPH = false, bool EMIT = false>
 __device__ bool repair_wave(const WiGraph& g, const WiBase& B, const WaveSet& hs, uint32_t* dlist,
                             uint32_t* dnew, uint32_t* nhn, uint32_t* ord, uint32_t cap,
                             TeamCtl* ctl, uint32_t lane, uint32_t e_fail, spf_whatif_digest* out,
-                            uint64_t* ph) {
+                            uint64_t* ph, const WiEmit* em = nullptr, uint32_t f = 0) {
   uint64_t tprev = ph ? wall_clock64() : 0ull;
 #define WI_STAMP(k)                                \
   do {                                             \
@@ -1752,6 +1850,29 @@ __device__ bool repair_wave(const WiGraph& g, const WiBase& B, const WaveSet& hs
     if (ph) ph_add<GPH>(ph, 9, 1, lane == 0);
   }
   WI_STAMP(3);
+  if constexpr (EMIT) {
+    // ---- change list: the D nodes whose metric or row changed (read here:
+    // the digest loop overwrites dnew with slot indices); the team is one
+    // wave, so the entry counter is a register ----
+    const bool fill = em->cnode != nullptr;
+    const uint64_t at = fill ? em->cptr[f] : 0ull;
+    const uint32_t room = fill ? (uint32_t)(em->cptr[f + 1] - at) : 0u;
+    uint32_t k = 0;
+    for (uint32_t c0 = 0; c0 < n; c0 += 64) {
+      const uint32_t i = c0 + lane;
+      uint32_t v = 0, d1 = kInf;
+      bool changed = false;
+      if (i < n) {
+        v = ldw<false>(&dlist[i]);
+        d1 = ldw<false>(&dnew[i]);
+        changed = entry_changed<false>(B, nhn, W, v, i, d1);
+      }
+      const uint64_t m = __ballot(changed);
+      if (fill && m) emit_entries<false>(*em, at, room, k, m, changed, v, i, d1, nhn, lane);
+      k += (uint32_t)__popcll(m);
+    }
+    if (!fill && lane == 0) em->cnt[f] = k;
+  }
   // ---- digest delta over D, scratch reset ----
   uint32_t nd_ = 0, nn_ = 0;
   uint64_t dh = 0;
@@ -1803,13 +1924,17 @@ __device__ __forceinline__ uint64_t* prof_row(unsigned long long* prof, size_t t
 // rows) -- 1: in registers, stored at team exit; 2: global read-modify-writes
 // per event -- so the production instance's registers, which set its
 // co-residency with the group teams (spf_whatif_plan_create), do not change
-// with diagnostics.
-template <int PROF>
+// with diagnostics.  EMIT (spf_whatif_changes; PROF 0 only): likewise separate
+// instances of the three repair kernels, with one more argument, the WiEmit,
+// as a trailing pack -- the production instances keep their argument list and
+// compile to what they did without it.
+template <int PROF, bool EMIT = false, class... EM>
 __global__ __launch_bounds__(256) void repair_wave_kernel(
     WiGraph g, WiBase B, const uint2* __restrict__ hot, const uint32_t* __restrict__ n_hot,
     uint32_t* cursor, uint2* big, uint32_t* n_big, unsigned long long* tab, uint32_t* dlist,
     uint32_t* dnew, uint32_t* nhn, uint32_t* lvl, uint32_t* ord, spf_whatif_digest* out, uint32_t cap,
-    uint32_t tab_log2, unsigned long long* prof, uint32_t prof_rows) {
+    uint32_t tab_log2, unsigned long long* prof, uint32_t prof_rows, EM... em) {
+  static_assert(sizeof...(EM) == (EMIT ? 1 : 0) && (!EMIT || PROF == 0), "EMIT: one WiEmit, PROF 0");
   __shared__ TeamCtl ctl[4];
   const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const size_t team = (size_t)blockIdx.x * 4 + w;
@@ -1828,8 +1953,9 @@ __global__ __launch_bounds__(256) void repair_wave_kernel(
     k = __builtin_amdgcn_readlane(k, 0);
     if (k >= total) break;
     const uint2 h = hot[k];
-    if (!repair_wave<PROF != 0, PROF == 2>(g, B, hs, dlist, dnew, nhn, ord, cap, &ctl[w], lane, h.y,
-                                          out + h.x, PROF == 1 ? ph : gph)) {
+    if (!repair_wave<PROF != 0, PROF == 2, EMIT>(g, B, hs, dlist, dnew, nhn, ord, cap, &ctl[w], lane,
+                                                h.y, out + h.x, PROF == 1 ? ph : gph,
+                                                emit_arg(em...), h.x)) {
       if (lane == 0) big[atomicAdd(n_big, 1u)] = h;
     }
   }
@@ -1838,11 +1964,12 @@ __global__ __launch_bounds__(256) void repair_wave_kernel(
       for (int q = 0; q < 12; ++q) r[q] = ph[q];
 }
 
-template <int PROF>
+template <int PROF, bool EMIT = false, class... EM>
 __global__ __launch_bounds__(1024) void repair_block_kernel(
     WiGraph g, WiBase B, const uint2* __restrict__ big, const uint32_t* __restrict__ n_big,
     uint32_t* mark, uint32_t* dlist, uint32_t* dnew, uint32_t* nhn, uint32_t* lvl, uint32_t* ord,
-    spf_whatif_digest* out, unsigned long long* prof, uint32_t prof_rows) {
+    spf_whatif_digest* out, unsigned long long* prof, uint32_t prof_rows, EM... em) {
+  static_assert(sizeof...(EM) == (EMIT ? 1 : 0) && (!EMIT || PROF == 0), "EMIT: one WiEmit, PROF 0");
   __shared__ TeamCtl ctl;
   // the largest repairs are the critical path of a batch and share their CU
   // with wave teams running concurrently: win the issue arbitration
@@ -1860,8 +1987,9 @@ __global__ __launch_bounds__(1024) void repair_block_kernel(
       PROF == 2 ? prof_row(prof, team, prof_rows, 2, threadIdx.x == 0 ? g.fault : nullptr) : nullptr;
   for (uint32_t k = blockIdx.x; k < total; k += gridDim.x) {
     const uint2 h = big[k];
-    repair<1024, false, false, PROF == 2>(g, B, mark, dlist, dnew, nhn, lvl, ord, g.N, &ctl,
-                                          threadIdx.x, h.y, out + h.x, PROF == 1 ? ph : gph);
+    repair<1024, false, false, PROF == 2, EMIT>(g, B, mark, dlist, dnew, nhn, lvl, ord, g.N, &ctl,
+                                                threadIdx.x, h.y, out + h.x, PROF == 1 ? ph : gph,
+                                                emit_arg(em...), h.x);
   }
   if (PROF == 1 && threadIdx.x == 0)
     if (uint64_t* r = prof_row(prof, team, prof_rows, 2, g.fault))
@@ -1899,12 +2027,13 @@ __global__ __launch_bounds__(1024) void sort_big_kernel(const uint2* __restrict_
 // both progress from the start.  Members of a team sit on one XCD (blocks x
 // and x + 8 share one); teams pull failures, largest first.
 constexpr int kGroupWg = 512;
-template <int G, int PROF>
+template <int G, int PROF, bool EMIT = false, class... EM>
 __global__ __launch_bounds__(kGroupWg) void repair_group_kernel(
     WiGraph g, WiBase B, const uint2* __restrict__ big, const uint32_t* __restrict__ n_big,
     uint32_t* cursor, TeamCtl* ctls, uint32_t* mark, uint32_t* dlist, uint32_t* dnew,
     uint32_t* nhn, uint32_t* lvl, uint32_t* ord, spf_whatif_digest* out,
-    unsigned long long* prof, uint32_t prof_rows) {
+    unsigned long long* prof, uint32_t prof_rows, EM... em) {
+  static_assert(sizeof...(EM) == (EMIT ? 1 : 0) && (!EMIT || PROF == 0), "EMIT: one WiEmit, PROF 0");
   constexpr int TEAM = kGroupWg * G;
   __builtin_amdgcn_s_setprio(3);
   const uint32_t idx = blockIdx.x >> 3;
@@ -1927,8 +2056,9 @@ __global__ __launch_bounds__(kGroupWg) void repair_group_kernel(
     const uint32_t k = ldw<true>(&ctl->next);
     if (k >= total) break;  // team-uniform
     const uint2 h = big[k];
-    repair<TEAM, true, false, PROF == 2>(g, B, mark, dlist, dnew, nhn, lvl, ord, g.N, ctl, tt, h.y,
-                                         out + h.x, PROF == 1 ? ph : gph);
+    repair<TEAM, true, false, PROF == 2, EMIT>(g, B, mark, dlist, dnew, nhn, lvl, ord, g.N, ctl, tt,
+                                               h.y, out + h.x, PROF == 1 ? ph : gph,
+                                               emit_arg(em...), h.x);
   }
   if (PROF == 1 && tt == 0)
     if (uint64_t* r = prof_row(prof, team, prof_rows, 3, g.fault))
@@ -1988,14 +2118,69 @@ const void* group_kernel(uint32_t G, int prof) {
   }
 }
 
+// the EMIT instances (change lists; PROF 0 only)
+const void* group_kernel_emit(uint32_t G) {
+  switch (G) {
+    case 2: return (const void*)repair_group_kernel<2, 0, true, WiEmit>;
+    case 4: return (const void*)repair_group_kernel<4, 0, true, WiEmit>;
+    case 8: return (const void*)repair_group_kernel<8, 0, true, WiEmit>;
+    case 16: return (const void*)repair_group_kernel<16, 0, true, WiEmit>;
+    default: return nullptr;
+  }
+}
+
 // one launch, a workgroup per CU (every member of every team resident at
-// once: the team barrier's precondition)
-hipError_t launch_group(uint32_t G, GroupArgs& a, uint32_t n_cu, int prof, hipStream_t s) {
-  const void* k = group_kernel(G, a.prof ? prof : 0);
+// once: the team barrier's precondition); with `em` the EMIT instance, the
+// occupancy check made with its own pointer
+hipError_t launch_group(uint32_t G, GroupArgs& a, uint32_t n_cu, int prof, hipStream_t s,
+                        const WiEmit* em = nullptr) {
+  const void* k = em ? group_kernel_emit(G) : group_kernel(G, a.prof ? prof : 0);
   if (!k) return hipErrorInvalidValue;
+  WiEmit e = em ? *em : WiEmit{};
   void* args[] = {&a.g, &a.B, &a.big, &a.n_big, &a.cursor, &a.ctls, &a.mark, &a.dlist, &a.dnew,
-                  &a.nhn, &a.lvl, &a.ord, &a.out, &a.prof, &a.prof_rows};
+                  &a.nhn, &a.lvl, &a.ord, &a.out, &a.prof, &a.prof_rows, &e};
   return launch_resident(k, n_cu, kGroupWg, args, n_cu, s);
+}
+
+// cptr[0 .. n] = exclusive scan of the failures' entry counts, cptr[n] the
+// total: one workgroup, 8 counts per thread and tile, the per-thread sums
+// scanned with the DPP wave scans (a sum < 2^35 as two words of 24 and 11
+// bits: 64 of either stay below 2^32), u64 offsets.
+constexpr uint32_t kListScanPer = 8;
+__global__ __launch_bounds__(1024) void whatif_scan_kernel(const uint32_t* __restrict__ cnt,
+                                                           uint32_t n,
+                                                           unsigned long long* __restrict__ cptr) {
+  __shared__ unsigned long long s_wave[16];
+  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  unsigned long long carry = 0;
+  for (uint64_t t0 = 0; t0 < n; t0 += 1024ull * kListScanPer) {  // block-uniform
+    const uint64_t b = t0 + (uint64_t)threadIdx.x * kListScanPer;
+    uint32_t x[kListScanPer];
+    unsigned long long sum = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kListScanPer; ++j) {
+      x[j] = b + j < n ? cnt[b + j] : 0u;
+      sum += x[j];
+    }
+    uint32_t tl = 0, th = 0;
+    const uint32_t el = wave_excl_scan((uint32_t)sum & 0xFFFFFFu, &tl);
+    const uint32_t eh = wave_excl_scan((uint32_t)(sum >> 24), &th);
+    if (lane == 0) s_wave[wv] = tl + ((unsigned long long)th << 24);
+    __syncthreads();
+    unsigned long long run = carry + el + ((unsigned long long)eh << 24);
+    for (uint32_t w = 0; w < 16; ++w) {
+      const unsigned long long t = s_wave[w];
+      if (w < wv) run += t;
+      carry += t;
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kListScanPer; ++j) {
+      if (b + j < n) cptr[b + j] = run;
+      run += x[j];
+    }
+    __syncthreads();  // s_wave is rewritten by the next tile
+  }
+  if (threadIdx.x == 0) cptr[n] = carry;
 }
 
 __global__ void base_digest_kernel(spf_whatif_digest* o, const unsigned long long* H) {
@@ -2037,8 +2222,20 @@ struct spf_whatif_plan {
   hipStream_t last = nullptr;  // stream of the last execute (spf_whatif_stats waits on it)
   // zero / negative metrics or u64 labels: every failure on the exact kernel
   std::unique_ptr<spfi::ExactWhatIf> exact;
+  // change lists of the last spf_whatif_changes: counts, scanned offsets and
+  // the exactly sized pools (kept while they are large enough), the digests
+  // when the caller passes none, events around count / scan / fill
+  DevBuf<uint32_t> l_cnt, l_node, l_nh;
+  DevBuf<unsigned long long> l_ptr, l_dist;
+  DevBuf<spf_whatif_digest> l_dig;
+  uint64_t l_total = 0;
+  bool has_lists = false;
+  hipEvent_t l_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  float l_ms[3] = {0, 0, 0};
   ~spf_whatif_plan() {
     for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    for (hipEvent_t e : l_ev)
+      if (e) (void)hipEventDestroy(e);
   }
 };
 
@@ -2115,6 +2312,140 @@ spf_status launch_big(spf_ctx* c, spf_plan* p, uint32_t* d_dist, uint32_t* d_nh,
 }
 
 }  // namespace spfi
+
+namespace {
+
+WiGraph wi_graph(const spf_whatif_plan* p) {
+  spf_ctx* c = p->ctx;
+  WiGraph g{c->d_row_ptr.p, c->d_col.p, c->d_wt.p, c->d_rev.p, c->d_link.p, c->d_ovl.p,
+            p->d_nbr_bit.p, c->N, p->src, p->W};
+  g.fault = c->d_fault.p;
+  g.ed = p->d_ed.p;
+  return g;
+}
+
+spf_status run_base(spf_whatif_plan* p, const WiGraph& g, hipStream_t s) {
+  spf_ctx* c = p->ctx;
+  const uint32_t N = c->N;
+  // 1. unfailed SPF, next hops, hash: one grid-resident launch
+  {
+    BaseArgs a{CoopSssp{c->d_row_ptr.p, c->d_col.p, c->d_wt.p, c->d_ovl.p, c->d_link.p, nullptr,
+                        N, p->src, 0u, p->d_dist.p, p->d_q.p, p->d_q2.p, p->d_bm.p, p->d_ctr.p},
+               g, p->d_nhb.p, p->d_lvl.p, p->d_order.p, p->d_misc.p, p->d_H.p,
+               p->d_prof.p ? p->d_prof.p + 16ull * p->big_teams : nullptr, p->d_parent.p,
+               p->d_sub.p};
+    a.sp.bar = p->d_bar.p;
+    a.sp.fault = c->d_fault.p;
+    if (p->d_prof.p) a.lprof = p->d_prof.p + 16ull * (p->big_teams + 1 + p->wave_teams);
+    HIP_TRY(c, hipMemsetAsync(p->d_bar.p, 0, 4 * kGridBarWords, s));
+    void* args[] = {&a};
+    if (const spf_status st = resident_order(c, s); st != SPF_OK) return st;
+    HIP_TRY(c, launch_resident((const void*)whatif_base_kernel,
+                               coop_blocks(c, (const void*)whatif_base_kernel, 1), kCoopThreads,
+                               args, c->n_cu, s));
+    if (const spf_status st = resident_done(c, s); st != SPF_OK) return st;
+  }
+  return SPF_OK;
+}
+
+// The failures of the plan's list on `s` and the context's side stream:
+// digests into d_out; with `em` the EMIT instances, which also count or fill
+// the change lists (one pass per call).
+spf_status run_failures(spf_whatif_plan* p, const WiGraph& g, spf_whatif_digest* d_out,
+                        hipStream_t s, const WiEmit* em) {
+  spf_ctx* c = p->ctx;
+  // 2. failures
+  HIP_TRY(c, hipMemsetAsync(p->d_cnt.p, 0, 32, s));
+  if (p->group) HIP_TRY(c, hipMemsetAsync(p->d_ctl.p, 0, sizeof(TeamCtl) * p->group_teams, s));
+  if (p->n_fail) {
+    hipLaunchKernelGGL(classify_kernel, dim3((p->n_fail + 255) / 256), dim3(256), 0, s, g,
+                       p->d_dist.p, p->d_H.p, p->d_fails.p, p->n_fail, p->d_link_edge.p,
+                       p->d_sub.p, p->classify_cap, d_out, p->d_hot.p, p->d_cnt.p, p->d_big0.p,
+                       p->d_cnt.p + 3);
+    HIP_TRY(c, hipGetLastError());
+    WiBase B{p->d_dist.p, p->d_nhb.p, p->d_H.p};
+    // failures classified big (parent subtree > kWaveCap) go to workgroup
+    // teams on a second stream right away, beside the wave teams; separate
+    // scratch, separate list, no dependence between the two grids
+    hipStream_t side = c->side ? c->side : s;
+    if (c->side) {
+      HIP_TRY(c, hipEventRecord(c->side_fork, s));
+      HIP_TRY(c, hipStreamWaitEvent(c->side, c->side_fork, 0));
+    }
+    bool grouped = false;
+    if (p->group) {
+      hipLaunchKernelGGL(sort_big_kernel, dim3(1), dim3(1024), 0, side, p->d_big0.p, p->d_cnt.p + 3,
+                         p->d_sub.p, c->d_col.p, p->d_big1.p);
+      HIP_TRY(c, hipGetLastError());
+      GroupArgs ga{g, B, p->d_big1.p, p->d_cnt.p + 3, p->d_cnt.p + 4,
+                   reinterpret_cast<TeamCtl*>(p->d_ctl.p), p->c_mark.p, p->c_dlist.p, p->c_dnew.p,
+                   p->c_nhn.p, p->c_lvl.p, p->c_ord.p, d_out, p->d_prof.p, p->big_teams};
+      if (const spf_status st = resident_order(c, side); st != SPF_OK) return st;
+      grouped = launch_group(p->group, ga, c->n_cu, p->prof_mode, side, em) == hipSuccess;
+      if (!grouped) (void)hipGetLastError();  // fall back to one-workgroup teams
+      else if (const spf_status st = resident_done(c, side); st != SPF_OK) return st;
+    }
+    if (!grouped) {
+      const uint32_t bt = p->big_teams;
+      if (em)
+        hipLaunchKernelGGL((repair_block_kernel<0, true, WiEmit>), dim3(bt), dim3(1024), 0, side, g, B,
+                           p->d_big0.p, p->d_cnt.p + 3, p->c_mark.p, p->c_dlist.p, p->c_dnew.p,
+                           p->c_nhn.p, p->c_lvl.p, p->c_ord.p, d_out, nullptr, 0u, *em);
+      else if (p->prof_mode == 2)
+        hipLaunchKernelGGL(repair_block_kernel<2>, dim3(bt), dim3(1024), 0, side, g, B, p->d_big0.p,
+                           p->d_cnt.p + 3, p->c_mark.p, p->c_dlist.p, p->c_dnew.p, p->c_nhn.p,
+                           p->c_lvl.p, p->c_ord.p, d_out, p->d_prof.p, bt);
+      else if (p->prof_mode == 1)
+        hipLaunchKernelGGL(repair_block_kernel<1>, dim3(bt), dim3(1024), 0, side, g, B, p->d_big0.p,
+                           p->d_cnt.p + 3, p->c_mark.p, p->c_dlist.p, p->c_dnew.p, p->c_nhn.p,
+                           p->c_lvl.p, p->c_ord.p, d_out, p->d_prof.p, bt);
+      else
+        hipLaunchKernelGGL(repair_block_kernel<0>, dim3(bt), dim3(1024), 0, side, g, B, p->d_big0.p,
+                           p->d_cnt.p + 3, p->c_mark.p, p->c_dlist.p, p->c_dnew.p, p->c_nhn.p,
+                           p->c_lvl.p, p->c_ord.p, d_out, nullptr, 0u);
+    }
+    HIP_TRY(c, hipGetLastError());
+    if (c->side) HIP_TRY(c, hipEventRecord(c->side_join, c->side));
+    {
+      unsigned long long* wp = p->d_prof.p ? p->d_prof.p + 16ull * (p->big_teams + 1) : nullptr;
+      const uint32_t wr = p->wave_teams;
+      if (em)
+        hipLaunchKernelGGL((repair_wave_kernel<0, true, WiEmit>), dim3(p->wave_teams / 4), dim3(256), 0,
+                           s, g, B, p->d_hot.p, p->d_cnt.p, p->d_cnt.p + 1, p->d_big.p, p->d_cnt.p + 2,
+                           p->w_tab.p, p->w_dlist.p, p->w_dnew.p, p->w_nhn.p, p->w_lvl.p,
+                           p->w_ord.p, d_out, p->wave_cap, p->tab_log2, nullptr, 0u, *em);
+      else if (p->prof_mode == 2)
+        hipLaunchKernelGGL(repair_wave_kernel<2>, dim3(p->wave_teams / 4), dim3(256), 0, s, g, B,
+                           p->d_hot.p, p->d_cnt.p, p->d_cnt.p + 1, p->d_big.p, p->d_cnt.p + 2,
+                           p->w_tab.p, p->w_dlist.p, p->w_dnew.p, p->w_nhn.p, p->w_lvl.p,
+                           p->w_ord.p, d_out, p->wave_cap, p->tab_log2, wp, wr);
+      else if (p->prof_mode == 1)
+        hipLaunchKernelGGL(repair_wave_kernel<1>, dim3(p->wave_teams / 4), dim3(256), 0, s, g, B,
+                           p->d_hot.p, p->d_cnt.p, p->d_cnt.p + 1, p->d_big.p, p->d_cnt.p + 2,
+                           p->w_tab.p, p->w_dlist.p, p->w_dnew.p, p->w_nhn.p, p->w_lvl.p,
+                           p->w_ord.p, d_out, p->wave_cap, p->tab_log2, wp, wr);
+      else
+        hipLaunchKernelGGL(repair_wave_kernel<0>, dim3(p->wave_teams / 4), dim3(256), 0, s, g, B,
+                           p->d_hot.p, p->d_cnt.p, p->d_cnt.p + 1, p->d_big.p, p->d_cnt.p + 2,
+                           p->w_tab.p, p->w_dlist.p, p->w_dnew.p, p->w_nhn.p, p->w_lvl.p,
+                           p->w_ord.p, d_out, p->wave_cap, p->tab_log2, nullptr, 0u);
+    }
+    HIP_TRY(c, hipGetLastError());
+    if (em)
+      hipLaunchKernelGGL((repair_block_kernel<0, true, WiEmit>), dim3(p->big_teams), dim3(1024), 0, s,
+                         g, B, p->d_big.p, p->d_cnt.p + 2, p->b_mark.p, p->b_dlist.p, p->b_dnew.p,
+                         p->b_nhn.p, p->b_lvl.p, p->b_ord.p, d_out, nullptr, 0u, *em);
+    else
+      hipLaunchKernelGGL(repair_block_kernel<0>, dim3(p->big_teams), dim3(1024), 0, s, g, B, p->d_big.p,
+                         p->d_cnt.p + 2, p->b_mark.p, p->b_dlist.p, p->b_dnew.p, p->b_nhn.p,
+                         p->b_lvl.p, p->b_ord.p, d_out, nullptr, 0u);
+    HIP_TRY(c, hipGetLastError());
+    if (c->side) HIP_TRY(c, hipStreamWaitEvent(s, c->side_join, 0));
+  }
+  return SPF_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -2310,7 +2641,6 @@ spf_status spf_whatif_execute(spf_whatif_plan* p, spf_whatif_digest* d_out,
     return fail(c, SPF_E_STATE, "graph changed since the plan was created: recreate it");
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   p->last = s;
-  const uint32_t N = c->N;
   hipEvent_t* ev = nullptr;
   if (p->timing_cap) {
     ev = &p->ev[3 * (p->timing_n % p->timing_cap)];
@@ -2324,103 +2654,10 @@ spf_status spf_whatif_execute(spf_whatif_plan* p, spf_whatif_digest* d_out,
     c->solves += 1ull + p->n_fail;
     return SPF_OK;
   }
-  WiGraph g{c->d_row_ptr.p, c->d_col.p, c->d_wt.p, c->d_rev.p, c->d_link.p, c->d_ovl.p,
-            p->d_nbr_bit.p, N, p->src, p->W};
-  g.fault = c->d_fault.p;
-  g.ed = p->d_ed.p;
-  // 1. unfailed SPF, next hops, hash: one grid-resident launch
-  {
-    BaseArgs a{CoopSssp{c->d_row_ptr.p, c->d_col.p, c->d_wt.p, c->d_ovl.p, c->d_link.p, nullptr,
-                        N, p->src, 0u, p->d_dist.p, p->d_q.p, p->d_q2.p, p->d_bm.p, p->d_ctr.p},
-               g, p->d_nhb.p, p->d_lvl.p, p->d_order.p, p->d_misc.p, p->d_H.p,
-               p->d_prof.p ? p->d_prof.p + 16ull * p->big_teams : nullptr, p->d_parent.p,
-               p->d_sub.p};
-    a.sp.bar = p->d_bar.p;
-    a.sp.fault = c->d_fault.p;
-    if (p->d_prof.p) a.lprof = p->d_prof.p + 16ull * (p->big_teams + 1 + p->wave_teams);
-    HIP_TRY(c, hipMemsetAsync(p->d_bar.p, 0, 4 * kGridBarWords, s));
-    void* args[] = {&a};
-    if (const spf_status st = resident_order(c, s); st != SPF_OK) return st;
-    HIP_TRY(c, launch_resident((const void*)whatif_base_kernel,
-                               coop_blocks(c, (const void*)whatif_base_kernel, 1), kCoopThreads,
-                               args, c->n_cu, s));
-    if (const spf_status st = resident_done(c, s); st != SPF_OK) return st;
-  }
+  const WiGraph g = wi_graph(p);
+  if (const spf_status st = run_base(p, g, s); st != SPF_OK) return st;
   if (ev) HIP_TRY(c, hipEventRecord(ev[1], s));
-  // 2. failures
-  HIP_TRY(c, hipMemsetAsync(p->d_cnt.p, 0, 32, s));
-  if (p->group) HIP_TRY(c, hipMemsetAsync(p->d_ctl.p, 0, sizeof(TeamCtl) * p->group_teams, s));
-  if (p->n_fail) {
-    hipLaunchKernelGGL(classify_kernel, dim3((p->n_fail + 255) / 256), dim3(256), 0, s, g,
-                       p->d_dist.p, p->d_H.p, p->d_fails.p, p->n_fail, p->d_link_edge.p,
-                       p->d_sub.p, p->classify_cap, d_out, p->d_hot.p, p->d_cnt.p, p->d_big0.p,
-                       p->d_cnt.p + 3);
-    HIP_TRY(c, hipGetLastError());
-    WiBase B{p->d_dist.p, p->d_nhb.p, p->d_H.p};
-    // failures classified big (parent subtree > kWaveCap) go to workgroup
-    // teams on a second stream right away, beside the wave teams; separate
-    // scratch, separate list, no dependence between the two grids
-    hipStream_t side = c->side ? c->side : s;
-    if (c->side) {
-      HIP_TRY(c, hipEventRecord(c->side_fork, s));
-      HIP_TRY(c, hipStreamWaitEvent(c->side, c->side_fork, 0));
-    }
-    bool grouped = false;
-    if (p->group) {
-      hipLaunchKernelGGL(sort_big_kernel, dim3(1), dim3(1024), 0, side, p->d_big0.p, p->d_cnt.p + 3,
-                         p->d_sub.p, c->d_col.p, p->d_big1.p);
-      HIP_TRY(c, hipGetLastError());
-      GroupArgs ga{g, B, p->d_big1.p, p->d_cnt.p + 3, p->d_cnt.p + 4,
-                   reinterpret_cast<TeamCtl*>(p->d_ctl.p), p->c_mark.p, p->c_dlist.p, p->c_dnew.p,
-                   p->c_nhn.p, p->c_lvl.p, p->c_ord.p, d_out, p->d_prof.p, p->big_teams};
-      if (const spf_status st = resident_order(c, side); st != SPF_OK) return st;
-      grouped = launch_group(p->group, ga, c->n_cu, p->prof_mode, side) == hipSuccess;
-      if (!grouped) (void)hipGetLastError();  // fall back to one-workgroup teams
-      else if (const spf_status st = resident_done(c, side); st != SPF_OK) return st;
-    }
-    if (!grouped) {
-      const uint32_t bt = p->big_teams;
-      if (p->prof_mode == 2)
-        hipLaunchKernelGGL(repair_block_kernel<2>, dim3(bt), dim3(1024), 0, side, g, B, p->d_big0.p,
-                           p->d_cnt.p + 3, p->c_mark.p, p->c_dlist.p, p->c_dnew.p, p->c_nhn.p,
-                           p->c_lvl.p, p->c_ord.p, d_out, p->d_prof.p, bt);
-      else if (p->prof_mode == 1)
-        hipLaunchKernelGGL(repair_block_kernel<1>, dim3(bt), dim3(1024), 0, side, g, B, p->d_big0.p,
-                           p->d_cnt.p + 3, p->c_mark.p, p->c_dlist.p, p->c_dnew.p, p->c_nhn.p,
-                           p->c_lvl.p, p->c_ord.p, d_out, p->d_prof.p, bt);
-      else
-        hipLaunchKernelGGL(repair_block_kernel<0>, dim3(bt), dim3(1024), 0, side, g, B, p->d_big0.p,
-                           p->d_cnt.p + 3, p->c_mark.p, p->c_dlist.p, p->c_dnew.p, p->c_nhn.p,
-                           p->c_lvl.p, p->c_ord.p, d_out, nullptr, 0u);
-    }
-    HIP_TRY(c, hipGetLastError());
-    if (c->side) HIP_TRY(c, hipEventRecord(c->side_join, c->side));
-    {
-      unsigned long long* wp = p->d_prof.p ? p->d_prof.p + 16ull * (p->big_teams + 1) : nullptr;
-      const uint32_t wr = p->wave_teams;
-      if (p->prof_mode == 2)
-        hipLaunchKernelGGL(repair_wave_kernel<2>, dim3(p->wave_teams / 4), dim3(256), 0, s, g, B,
-                           p->d_hot.p, p->d_cnt.p, p->d_cnt.p + 1, p->d_big.p, p->d_cnt.p + 2,
-                           p->w_tab.p, p->w_dlist.p, p->w_dnew.p, p->w_nhn.p, p->w_lvl.p,
-                           p->w_ord.p, d_out, p->wave_cap, p->tab_log2, wp, wr);
-      else if (p->prof_mode == 1)
-        hipLaunchKernelGGL(repair_wave_kernel<1>, dim3(p->wave_teams / 4), dim3(256), 0, s, g, B,
-                           p->d_hot.p, p->d_cnt.p, p->d_cnt.p + 1, p->d_big.p, p->d_cnt.p + 2,
-                           p->w_tab.p, p->w_dlist.p, p->w_dnew.p, p->w_nhn.p, p->w_lvl.p,
-                           p->w_ord.p, d_out, p->wave_cap, p->tab_log2, wp, wr);
-      else
-        hipLaunchKernelGGL(repair_wave_kernel<0>, dim3(p->wave_teams / 4), dim3(256), 0, s, g, B,
-                           p->d_hot.p, p->d_cnt.p, p->d_cnt.p + 1, p->d_big.p, p->d_cnt.p + 2,
-                           p->w_tab.p, p->w_dlist.p, p->w_dnew.p, p->w_nhn.p, p->w_lvl.p,
-                           p->w_ord.p, d_out, p->wave_cap, p->tab_log2, nullptr, 0u);
-    }
-    HIP_TRY(c, hipGetLastError());
-    hipLaunchKernelGGL(repair_block_kernel<0>, dim3(p->big_teams), dim3(1024), 0, s, g, B, p->d_big.p,
-                       p->d_cnt.p + 2, p->b_mark.p, p->b_dlist.p, p->b_dnew.p, p->b_nhn.p,
-                       p->b_lvl.p, p->b_ord.p, d_out, nullptr, 0u);
-    HIP_TRY(c, hipGetLastError());
-    if (c->side) HIP_TRY(c, hipStreamWaitEvent(s, c->side_join, 0));
-  }
+  if (const spf_status st = run_failures(p, g, d_out, s, nullptr); st != SPF_OK) return st;
   if (p->d_prof.p) {  // diagnostics: phase ticks (100 MHz) per team, accumulated over repairs
     const size_t bt = p->big_teams, wt = p->wave_teams;
     std::vector<unsigned long long> h(16ull * (bt + 1 + wt) + 128);
@@ -2469,6 +2706,184 @@ spf_status spf_whatif_execute(spf_whatif_plan* p, spf_whatif_digest* d_out,
   }
   if (ev) HIP_TRY(c, hipEventRecord(ev[2], s));
   c->solves += 1ull + p->n_fail;
+  return SPF_OK;
+}
+
+spf_status spf_whatif_changes(spf_whatif_plan* p, spf_whatif_digest* d_out, spf_whatif_digest* d_base,
+                              uint64_t* n_entries, uint64_t* pool_bytes, double* kernel_ms,
+                              void* stream) {
+  if (!p) return fail(nullptr, SPF_E_INVALID, "spf_whatif_changes: NULL plan");
+  spf_ctx* c = p->ctx;
+  p->has_lists = false;  // after a failed call the plan holds no lists
+  if (!c->loaded) return fail(c, SPF_E_STATE, "graph no longer loaded");
+  if (p->epoch != c->epoch)
+    return fail(c, SPF_E_STATE, "graph changed since the plan was created: recreate it");
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  const uint32_t nf = p->n_fail;
+  HIP_TRY(c, p->l_cnt.alloc(std::max<uint32_t>(1, nf)));
+  HIP_TRY(c, p->l_ptr.alloc((size_t)nf + 1));
+  if (!d_out) {
+    HIP_TRY(c, p->l_dig.alloc(std::max<uint32_t>(1, nf)));
+    d_out = p->l_dig.p;
+  }
+  for (hipEvent_t& e : p->l_ev)
+    if (!e) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
+  p->last = s;
+  WiEmit em;
+  em.cnt = p->l_cnt.p;
+  em.W = p->W;
+  em.fault = c->d_fault.p;
+  // one pass over the failures with the EMIT instances (count, then fill)
+  const WiGraph g = p->exact ? WiGraph{} : wi_graph(p);
+  auto pass = [&](bool first) -> spf_status {
+    if (p->exact)
+      return exact_whatif_launch(c, p->exact.get(), d_out, first ? d_base : nullptr, s, nullptr, &em,
+                                 first);
+    return run_failures(p, g, d_out, s, &em);
+  };
+  if (!p->exact)
+    if (const spf_status st = run_base(p, g, s); st != SPF_OK) return st;
+  // count: cnt[f] = failure f's entries (0 for cold ones: the memset)
+  HIP_TRY(c, hipMemsetAsync(p->l_cnt.p, 0, 4ull * std::max<uint32_t>(1, nf), s));
+  HIP_TRY(c, hipEventRecord(p->l_ev[0], s));
+  if (const spf_status st = pass(true); st != SPF_OK) return st;
+  HIP_TRY(c, hipEventRecord(p->l_ev[1], s));
+  hipLaunchKernelGGL(whatif_scan_kernel, dim3(1), dim3(1024), 0, s, p->l_cnt.p, nf, p->l_ptr.p);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipEventRecord(p->l_ev[2], s));
+  // the pools are sized from the scan's total
+  unsigned long long total = 0;
+  HIP_TRY(c, hipMemcpyAsync(&total, p->l_ptr.p + nf, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  if (const spf_status st = spf_device_check(c); st != SPF_OK) return st;
+  const size_t cap = std::max<size_t>(1, (size_t)total);
+  if (p->l_node.alloc(cap) != hipSuccess || p->l_dist.alloc(cap) != hipSuccess ||
+      p->l_nh.alloc(cap * p->W) != hipSuccess) {  // (kept while they are large enough)
+    (void)hipGetLastError();
+    p->l_node.reset();
+    p->l_dist.reset();
+    p->l_nh.reset();
+    return fail(c, SPF_E_NOMEM, "spf_whatif_changes: no memory for %llu entries of %u bytes", total,
+                12u + 4u * p->W);
+  }
+  // fill: the repairs again, entries to cptr[f] + k
+  em.cptr = p->l_ptr.p;
+  em.cnode = p->l_node.p;
+  em.cdist = p->l_dist.p;
+  em.cnh = p->l_nh.p;
+  if (const spf_status st = pass(false); st != SPF_OK) return st;
+  HIP_TRY(c, hipEventRecord(p->l_ev[3], s));
+  if (d_base && !p->exact) {
+    hipLaunchKernelGGL(base_digest_kernel, dim3(1), dim3(1), 0, s, d_base, p->d_H.p);
+    HIP_TRY(c, hipGetLastError());
+  }
+  HIP_TRY(c, hipStreamSynchronize(s));
+  if (const spf_status st = spf_device_check(c); st != SPF_OK) return st;
+  for (int k = 0; k < 3; ++k) HIP_TRY(c, hipEventElapsedTime(&p->l_ms[k], p->l_ev[k], p->l_ev[k + 1]));
+  p->l_total = total;
+  p->has_lists = true;
+  c->solves += 1ull + nf;
+  if (n_entries) *n_entries = total;
+  if (pool_bytes) *pool_bytes = 8ull * ((uint64_t)nf + 1) + total * (12ull + 4ull * p->W);
+  if (kernel_ms) *kernel_ms = (double)p->l_ms[0] + p->l_ms[1] + p->l_ms[2];
+  return SPF_OK;
+}
+
+spf_status spf_whatif_changes_timing(const spf_whatif_plan* p, double* ms) {
+  if (!p || !ms) return SPF_E_INVALID;
+  if (!p->has_lists) return fail(p->ctx, SPF_E_STATE, "spf_whatif_changes_timing: the plan holds no lists");
+  for (int k = 0; k < 3; ++k) ms[k] = p->l_ms[k];
+  return SPF_OK;
+}
+
+spf_status spf_whatif_changes_buffers(spf_whatif_plan* p, const uint64_t** d_ptr, const uint32_t** d_node,
+                                      const uint64_t** d_dist, const uint32_t** d_nh, uint32_t* W,
+                                      uint64_t* n_entries) {
+  if (!p) return fail(nullptr, SPF_E_INVALID, "spf_whatif_changes_buffers: NULL plan");
+  if (!p->has_lists) return fail(p->ctx, SPF_E_STATE, "spf_whatif_changes_buffers: the plan holds no lists");
+  if (d_ptr) *d_ptr = reinterpret_cast<const uint64_t*>(p->l_ptr.p);
+  if (d_node) *d_node = p->l_node.p;
+  if (d_dist) *d_dist = reinterpret_cast<const uint64_t*>(p->l_dist.p);
+  if (d_nh) *d_nh = p->l_nh.p;
+  if (W) *W = p->W;
+  if (n_entries) *n_entries = p->l_total;
+  return SPF_OK;
+}
+
+spf_status spf_whatif_changes_read(spf_whatif_plan* p, uint64_t* ptr, uint32_t* node, uint64_t* dist,
+                                   uint32_t* nh) {
+  if (!p) return fail(nullptr, SPF_E_INVALID, "spf_whatif_changes_read: NULL plan");
+  spf_ctx* c = p->ctx;
+  if (!p->has_lists) return fail(c, SPF_E_STATE, "spf_whatif_changes_read: the plan holds no lists");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t t = (size_t)p->l_total;
+  if (ptr) HIP_TRY(c, hipMemcpy(ptr, p->l_ptr.p, 8ull * ((size_t)p->n_fail + 1), hipMemcpyDeviceToHost));
+  if (node && t) HIP_TRY(c, hipMemcpy(node, p->l_node.p, 4ull * t, hipMemcpyDeviceToHost));
+  if (dist && t) HIP_TRY(c, hipMemcpy(dist, p->l_dist.p, 8ull * t, hipMemcpyDeviceToHost));
+  if (nh && t) HIP_TRY(c, hipMemcpy(nh, p->l_nh.p, 4ull * t * p->W, hipMemcpyDeviceToHost));
+  return SPF_OK;
+}
+
+spf_status spf_whatif_changes_db(spf_whatif_plan* p, uint32_t i, uint32_t* node, uint64_t* dist,
+                                 uint32_t* nh, uint64_t cap, uint64_t* n) {
+  if (!p) return fail(nullptr, SPF_E_INVALID, "spf_whatif_changes_db: NULL plan");
+  spf_ctx* c = p->ctx;
+  if (!p->has_lists) return fail(c, SPF_E_STATE, "spf_whatif_changes_db: the plan holds no lists");
+  if (i >= p->n_fail) return fail(c, SPF_E_INVALID, "spf_whatif_changes_db: failure %u of %u", i, p->n_fail);
+  HIP_TRY(c, hipSetDevice(c->device));
+  unsigned long long r[2] = {0, 0};
+  HIP_TRY(c, hipMemcpy(r, p->l_ptr.p + i, 16, hipMemcpyDeviceToHost));
+  if (r[1] < r[0] || r[1] > p->l_total) return fail(c, SPF_E_HIP, "spf_whatif_changes_db: offsets not monotone");
+  const size_t m = (size_t)(r[1] - r[0]), W = p->W;
+  if (n) *n = m;
+  if (!node && !dist && !nh) return SPF_OK;
+  if (cap < m) return fail(c, SPF_E_NOMEM, "spf_whatif_changes_db: %zu entries, room for %llu", m,
+                           (unsigned long long)cap);
+  if (!m) return SPF_OK;
+  std::vector<uint32_t> hn(m), hw(m * W);
+  std::vector<uint64_t> hd(m);
+  HIP_TRY(c, hipMemcpy(hn.data(), p->l_node.p + r[0], 4 * m, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(hd.data(), p->l_dist.p + r[0], 8 * m, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(hw.data(), p->l_nh.p + r[0] * W, 4 * m * W, hipMemcpyDeviceToHost));
+  std::vector<size_t> order(m);  // the device order is the teams' atomics': ascending by node here
+  for (size_t k = 0; k < m; ++k) order[k] = k;
+  std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return hn[a] < hn[b]; });
+  for (size_t k = 0; k < m; ++k) {
+    const size_t q = order[k];
+    if (node) node[k] = hn[q];
+    if (dist) dist[k] = hd[q];
+    if (nh) std::memcpy(nh + k * W, hw.data() + q * W, 4 * W);
+  }
+  return SPF_OK;
+}
+
+spf_status spf_whatif_base(spf_whatif_plan* p, uint64_t* dist, uint32_t* nh, uint32_t* W) {
+  if (!p) return fail(nullptr, SPF_E_INVALID, "spf_whatif_base: NULL plan");
+  spf_ctx* c = p->ctx;
+  if (!p->last) return fail(c, SPF_E_STATE, "spf_whatif_base: no execute yet");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(p->last));
+  const size_t N = c->N, Wp = p->W;
+  if (W) *W = p->W;
+  std::vector<uint64_t> d(N);
+  if (p->exact) {
+    HIP_TRY(c, hipMemcpy(d.data(), p->exact->base_d.p, 8 * N, hipMemcpyDeviceToHost));
+  } else {
+    std::vector<uint32_t> d32(N);
+    HIP_TRY(c, hipMemcpy(d32.data(), p->d_dist.p, 4 * N, hipMemcpyDeviceToHost));
+    for (size_t v = 0; v < N; ++v) d[v] = d32[v] == kInf ? ~0ull : d32[v];
+  }
+  if (dist) std::memcpy(dist, d.data(), 8 * N);
+  if (nh) {
+    // rows of W words in both plans (the exact plan's Wmax is its W); an
+    // unreachable node's row, and a source's without neighbours, is zero
+    const uint32_t* rows = p->exact ? p->exact->base_nh.p : p->d_nhb.p;
+    HIP_TRY(c, hipMemcpy(nh, rows, 4 * N * Wp, hipMemcpyDeviceToHost));
+    const bool no_nbr = c->nb_ptr[p->src + 1] == c->nb_ptr[p->src];
+    for (size_t v = 0; v < N; ++v)
+      if (d[v] == ~0ull || no_nbr) std::memset(nh + v * Wp, 0, 4 * Wp);
+  }
   return SPF_OK;
 }
 
@@ -2559,6 +2974,14 @@ spf_status spf_device_check(spf_ctx* c) {
   HIP_TRY(c, hipMemcpy(&flag, c->d_fault.p, sizeof flag, hipMemcpyDeviceToHost));
   if (!flag) return SPF_OK;
   HIP_TRY(c, hipMemset(c->d_fault.p, 0, sizeof flag));
+  if (flag & 64u) {
+    // a team's fill pass met more entries than its count pass allocated
+    // (spf_whatif_changes): the entry was dropped
+    return fail(c, SPF_E_HIP,
+                "what-if change lists on device %d: an entry past its failure's allocated count "
+                "(fault word 0x%08x); the results of this context's launches since the last check are "
+                "invalid", c->device, flag);
+  }
   if (flag & 56u) {
     // what-if repair diagnostics: a loop bound (bit 3, phase in bits 8-15), a
     // range check of the profiled instances (bit 4, site in bits 16-23) or a

@@ -398,6 +398,89 @@ class WhatIfPlan(NativeHandle):
         self._eng._err(N.lib.spf_whatif_timing(self._h, C.byref(a), C.byref(b), C.byref(n)))
         return a.value, b.value, n.value
 
+    def changes(self, stream: int = 0) -> "WhatIfChanges":
+        """Every failure's change list (``spf_whatif_changes``), read back."""
+        return WhatIfChanges(self, stream)
+
+    def base(self) -> Tuple[np.ndarray, np.ndarray, int]:
+        """The unfailed result the lists patch: (dist[N] u64, nh[N, W], W)."""
+        w = C.c_uint32()
+        self._eng._err(N.lib.spf_whatif_base(self._h, None, None, C.byref(w)))
+        n = self._eng.n_nodes
+        dist = np.zeros(n, np.uint64)
+        nh = np.zeros((n, w.value), np.uint32)
+        self._eng._err(N.lib.spf_whatif_base(self._h, N.ptr(dist, C.c_uint64), N.ptr(nh), None))
+        return dist, nh, int(w.value)
+
+
+class WhatIfChanges:
+    """The change lists of one ``spf_whatif_changes`` call on the host:
+    failure i owns entries ``ptr[i] .. ptr[i + 1]`` of ``node`` / ``dist``
+    (``SPF_UNREACHABLE64``: now unreachable) / ``nh[:, W]`` in device order;
+    ``of(i)`` returns them ascending by node.  The device arrays stay with
+    the plan until its next ``changes()``; ``close()`` closes the plan when
+    this object owns it (``SpfEngine.whatif_changes``)."""
+
+    def __init__(self, plan: WhatIfPlan, stream: int = 0, own_plan: bool = False) -> None:
+        from .hiprt import DeviceArray, set_device
+
+        self.plan, self._own = plan, own_plan
+        eng = plan._eng
+        set_device(eng.device)
+        self.n_fail = plan.n_fail
+        d_out = DeviceArray(max(1, self.n_fail), DIGEST_DTYPE)
+        d_base = DeviceArray(1, DIGEST_DTYPE)
+        try:
+            n, nbytes, ms = C.c_uint64(), C.c_uint64(), C.c_double()
+            eng._err(N.lib.spf_whatif_changes(plan._h, C.c_void_p(d_out.ptr), C.c_void_p(d_base.ptr),
+                                              C.byref(n), C.byref(nbytes), C.byref(ms),
+                                              C.c_void_p(stream) if stream else None))
+            self.digests = d_out.numpy()[: self.n_fail]
+            self.base_digest = d_base.numpy()[0]
+        finally:
+            d_out.free()
+            d_base.free()
+        self.n_entries, self.pool_bytes, self.kernel_ms = int(n.value), int(nbytes.value), ms.value
+        w = C.c_uint32()
+        eng._err(N.lib.spf_whatif_changes_buffers(plan._h, None, None, None, None, C.byref(w), None))
+        self.W = int(w.value)
+        self.ptr = np.zeros(self.n_fail + 1, np.uint64)
+        self.node = np.zeros(self.n_entries, np.uint32)
+        self.dist = np.zeros(self.n_entries, np.uint64)
+        self.nh = np.zeros((self.n_entries, self.W), np.uint32)
+        eng._err(N.lib.spf_whatif_changes_read(plan._h, N.ptr(self.ptr, C.c_uint64), N.ptr(self.node),
+                                               N.ptr(self.dist, C.c_uint64), N.ptr(self.nh)))
+
+    def timing(self) -> Tuple[float, float, float]:
+        """(count, scan, fill) ms of the call."""
+        ms = (C.c_double * 3)()
+        self.plan._eng._err(N.lib.spf_whatif_changes_timing(self.plan._h, ms))
+        return ms[0], ms[1], ms[2]
+
+    def of(self, i: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Failure i's (node[n], dist[n], nh[n, W]), ascending by node."""
+        n = C.c_uint64()
+        err = self.plan._eng._err
+        err(N.lib.spf_whatif_changes_db(self.plan._h, i, None, None, None, 0, C.byref(n)))
+        m = int(n.value)
+        node, dist = np.zeros(m, np.uint32), np.zeros(m, np.uint64)
+        nh = np.zeros((m, self.W), np.uint32)
+        if m:
+            err(N.lib.spf_whatif_changes_db(self.plan._h, i, N.ptr(node), N.ptr(dist, C.c_uint64),
+                                            N.ptr(nh), m, C.byref(n)))
+        return node, dist, nh
+
+    def close(self) -> None:
+        if self._own:
+            self.plan.close()
+            self._own = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
 
 class SpfEngine(NativeHandle):
     """An engine context with one graph loaded (``spf_ctx``).  ``close()``
@@ -631,6 +714,18 @@ class SpfEngine(NativeHandle):
         self._err(N.lib.spf_whatif_solve(self._h, src, N.ptr(arr), len(arr),
                                          out.ctypes.data, base.ctypes.data))
         return arr, out[: len(arr)], base[0]
+
+    def whatif_changes(self, src: int, links: Optional[Sequence[int]] = None) -> WhatIfChanges:
+        """What each failure changes: the nodes whose metric or next hops
+        move under runSpf(src, true, {l}), with their new values, for each
+        failed link l (every up link when `links` is None).  close() the
+        result (it owns its plan)."""
+        plan = self.whatif_plan(src, links)
+        try:
+            return WhatIfChanges(plan, own_plan=True)
+        except BaseException:
+            plan.close()
+            raise
 
     def sssp(self, src: int, hop: bool = False,
              ignore_links: Optional[Sequence[int]] = None) -> np.ndarray:
