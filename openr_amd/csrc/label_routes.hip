@@ -1,6 +1,6 @@
 // ============================================================================
 //  label_routes.hip -- every node's node-label MPLS routes from a RESIDENT
-//  all-sources pass (spf_mplan_label_routes, multi.cpp).
+//  all-sources pass (spf_mplan_label_routes, mplan_routes.cpp).
 //
 //  Reference: SpfSolver::SpfSolverImpl in openr/decision/Decision.cpp
 //    buildRouteDb           :586-674    one MPLS route per node segment label:

@@ -1,6 +1,6 @@
 // ============================================================================
 //  route_delta.hip -- every node's route-database delta between two passes
-//  (spf_mplan_route_delta, multi.cpp).
+//  (spf_mplan_route_delta, mplan_routes.cpp).
 //
 //  Reference: DecisionRouteDb::calculateUpdate in openr/decision/Decision.cpp
 //    :111-146   routes to update (new, or the entry differs) and routes to

@@ -1,6 +1,6 @@
 // ============================================================================
 //  route_update.hip -- the payload of every node's route-database delta
-//  (spf_mplan_route_update, multi.cpp).
+//  (spf_mplan_route_update, mplan_routes.cpp).
 //
 //  Reference: DecisionRouteDb::calculateUpdate in openr/decision/Decision.cpp
 //    :111-146   a DecisionRouteUpdate carries the updated ENTRIES -- a route's

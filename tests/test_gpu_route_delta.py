@@ -506,6 +506,11 @@ def test_contract():
         assert status(lambda: ls.allSourcesRouteDelta(snap)) == N.SPF_E_INVALID
         Gen(ls, sets, True)
         assert status(lambda: ls.allSourcesRouteDelta(snap)) == N.SPF_E_INVALID
+        # label routes of another me list than the route records': no snapshot, and nothing has moved
+        ls.allSourcesLabelRoutes(True, np.arange(n - 1, dtype=np.uint32))
+        assert status(ls.allSourcesRouteSnapshot) == N.SPF_E_INVALID
+        ls.allSourcesRouteDb(0)
+        ls.allSourcesLabelRouteDb(0)
         # a row patch drops the LinkState's plan; the snapshot is still good
         adj(dbs, "z0", "r05").isOverloaded = True
         push(ls, dbs, "z0")

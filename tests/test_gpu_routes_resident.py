@@ -244,7 +244,7 @@ def test_route_sums_u32_and_u64_paths_agree(lfa, monkeypatch):
 def test_route_lfa_u8_row_loads_match_oracle(members, monkeypatch):
     """With unit metrics and every member's BFS rows below depth 254, the
     many-me route kernel's LFA reads the members' u8 row copies (4 bytes per
-    4 destinations, multi.cpp route_prepare): every node's digests and
+    4 destinations, mplan_routes.cpp route_prepare): every node's digests and
     materialised databases equal the u32 loads' (SPF_ROUTE_U8=0) and the
     oracle's.  (Team plans keep no u8 rows: SPF_MSBFS_TEAM=0 gives every
     member the one-workgroup-per-batch BFS that writes them.)"""
