@@ -114,6 +114,24 @@ ClassRows plan_class_rows(const GraphHost& g, const std::vector<uint32_t>& closu
   return cr;
 }
 
+ExpandGrid plan_expand_grid(uint32_t rows, uint32_t span, uint32_t resident) {
+  ExpandGrid eg;
+  eg.groups = (rows + kExRows - 1) / kExRows;
+  eg.pieces = (span + kExPiece - 1) / kExPiece;
+  resident = std::max(1u, resident);
+  eg.pps = std::max(1u, eg.pieces);
+  if (eg.groups >= resident) {
+    eg.gper = (eg.groups + resident - 1) / resident;
+    eg.wgs = (eg.groups + eg.gper - 1) / eg.gper;
+  } else {
+    eg.wgs = std::max(1u, eg.groups);
+    const uint32_t want = std::min(eg.pps, resident / eg.wgs);
+    eg.pps = (eg.pps + want - 1) / want;
+    eg.splits = (std::max(1u, eg.pieces) + eg.pps - 1) / eg.pps;
+  }
+  return eg;
+}
+
 XcdLists plan_xcd_lists(const std::vector<uint32_t>& words, uint32_t runs) {
   XcdLists x;
   const uint32_t n_src = (uint32_t)words.size();

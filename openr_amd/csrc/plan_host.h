@@ -108,6 +108,25 @@ struct ClassRows {
 };
 ClassRows plan_class_rows(const GraphHost& g, const std::vector<uint32_t>& closure);
 
+// The expansion kernel's grid.  A workgroup owns whole groups of kExRows
+// closure rows and sweeps them in pieces of kExPiece nodes (a wave's store of
+// four nodes per lane).  resident = the workgroups the chip holds at once.
+//   groups >= resident: the full width per workgroup (splits == 1), gper =
+//     the rounds the chip needs, consecutive groups each, so every workgroup
+//     is resident from the start and all but the last own gper groups;
+//   fewer groups: one group per workgroup and the width split into `splits`
+//     ranges of pps pieces, as many as the chip holds.
+// Workgroup (x, y) owns groups [x * gper, min(groups, (x + 1) * gper)) over
+// pieces [y * pps, min(pieces, (y + 1) * pps)).
+constexpr uint32_t kExRows = 8;
+constexpr uint32_t kExPiece = 256;
+struct ExpandGrid {
+  uint32_t groups = 0, pieces = 0;  // row groups, pieces of the width
+  uint32_t wgs = 1, gper = 1;       // grid x, groups per workgroup
+  uint32_t splits = 1, pps = 1;     // grid y, pieces per split
+};
+ExpandGrid plan_expand_grid(uint32_t rows, uint32_t span, uint32_t resident);
+
 // What the two bounds below remember of the graph they were taken from.
 struct DepthCache {
   std::vector<uint32_t> ecc;  // per-node eccentricity estimates, for ecc_epoch

@@ -1343,13 +1343,16 @@ __global__ __launch_bounds__(kMsThreads) void class_bfs_kernel(
     Dc[(size_t)(row0 + t / pw) * cpitch + q_nc + t % pw] = 0xFFFFu;
 }
 
-// Node rows from class rows.  A workgroup owns kExNodes consecutive nodes
-// (four per thread: one 16-byte store per row) and walks a range of closure
-// rows, kExRows at a time: the classes of its nodes get local numbers once
-// (LDS map; local class 0 = the padding past N, always unreachable), per row
-// group the class rows' entries of those classes are staged transposed in
-// LDS (T[local class] = its kExRows distances), and a thread reads its four
-// nodes' distances of the whole group with four 16-byte LDS loads.
+// Node rows from class rows.  A workgroup owns whole groups of kExRows
+// closure rows over the row width (small plans: a range of the width,
+// plan_expand_grid).  Per group it stages the rows' class rows once -- thread
+// o reads classes 8o .. 8o + 7 of each row's Dc row with one 16-byte load and
+// writes them transposed, T[class] = its kExRows distances (u16), over all
+// q_nc classes (T[q_nc]: the padding past N, always unreachable) -- and then
+// its waves sweep the width in pieces of kExPiece nodes, four per lane: the
+// lane's class ids from q_cls (L2), four 16-byte LDS loads, one 16-byte store
+// per row.  T is double-buffered: the next group's Dc loads are issued before
+// the sweep and written to the other half behind it, one barrier per group.
 //   d(closure[r], v) = Dc[crow_of[r]][class of v]; the node closure[r] itself
 //   gets 0.
 //   D:  the u32 rows (pitch; unreachable and padding kInf), streaming stores.
@@ -1359,112 +1362,137 @@ __global__ __launch_bounds__(kMsThreads) void class_bfs_kernel(
 //       and lane 8q + b of a wave stores plane b of the wave's word q.
 //   Dn: the u8 rows (npitch; min(d, 254), 255 unreachable and padding).
 // Any of the three may be null.
-constexpr uint32_t kExThreads = 256;
-constexpr uint32_t kExNodes = 4 * kExThreads;
-constexpr uint32_t kExRows = 8;
+#ifndef SPF_EX_THREADS
+#define SPF_EX_THREADS 1024
+#endif
+constexpr uint32_t kExThreads = SPF_EX_THREADS;  // (build-time A/B)
+constexpr uint32_t kExWaves = kExThreads / 64;
+constexpr uint32_t kExMaxCls = 8 * kExThreads - 8;  // one class octet per thread, the padding's entry behind
+// entries of one half of T: q_nc classes and the padding's, whole octets
+__host__ __device__ constexpr uint32_t ex_entries(uint32_t q_nc) { return (q_nc + 8u) & ~7u; }
+
+// classes 8o .. 8o + 7 of the group's rows (a row past the plan's last, or an
+// octet past the class pitch: unreachable)
+__device__ __forceinline__ void ex_stage_load(uint4 (&x)[kExRows], const uint16_t* __restrict__ Dc,
+                                              uint32_t cpitch, const uint32_t* __restrict__ crow_of,
+                                              uint32_t r0, uint32_t rows, uint32_t o) {
+#pragma unroll
+  for (uint32_t j = 0; j < kExRows; ++j) {
+    x[j] = make_uint4(~0u, ~0u, ~0u, ~0u);
+    if (r0 + j < rows && 8u * o < cpitch)
+      x[j] = *reinterpret_cast<const uint4*>(Dc + (size_t)crow_of[r0 + j] * cpitch + 8u * o);
+  }
+}
+
+// ... transposed into T[8o .. 8o + 7]
+__device__ __forceinline__ void ex_stage_write(uint4* __restrict__ T, const uint4 (&x)[kExRows], uint32_t o) {
+#pragma unroll
+  for (uint32_t i = 0; i < 8; ++i) {
+    uint32_t h[kExRows];
+#pragma unroll
+    for (uint32_t j = 0; j < kExRows; ++j) {
+      const uint32_t w = i / 2 == 0 ? x[j].x : i / 2 == 1 ? x[j].y : i / 2 == 2 ? x[j].z : x[j].w;
+      h[j] = (i & 1u) ? w >> 16 : w & 0xFFFFu;
+    }
+    T[8u * o + i] = make_uint4(h[0] | h[1] << 16, h[2] | h[3] << 16, h[4] | h[5] << 16, h[6] | h[7] << 16);
+  }
+}
+
 __global__ __launch_bounds__(kExThreads) void expand_rows_kernel(
     const uint16_t* __restrict__ Dc, uint32_t cpitch, const uint32_t* __restrict__ crow_of,
-    const uint32_t* __restrict__ closure, uint32_t rows, uint32_t rows_per,
+    const uint32_t* __restrict__ closure, uint32_t rows, uint32_t gper, uint32_t pieces, uint32_t pps,
     const uint16_t* __restrict__ q_cls, uint32_t q_nc, uint32_t N, uint32_t pitch, uint32_t npitch,
     uint32_t* __restrict__ D, uint8_t* __restrict__ Dn, uint32_t* __restrict__ S,
     const uint32_t* __restrict__ maxd) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  uint4* const T = reinterpret_cast<uint4*>(smem);              // [kExNodes + 1]
-  uint32_t* const list = reinterpret_cast<uint32_t*>(T + kExNodes + 1);  // [kExNodes + 1]
-  uint32_t* const cnt = list + kExNodes + 1;                    // [1] (+ 2 unused)
-  uint32_t* const map = cnt + 3;                                // [q_nc]
-  constexpr uint32_t kEmpty = 0xFFFFFFFFu, kClaimed = 0xFFFFFFFEu;
+  const uint32_t nT = ex_entries(q_nc);
+  uint4* const T = reinterpret_cast<uint4*>(smem);  // [2][nT]
 
-  const uint32_t tid = threadIdx.x, lane = tid & 63;
-  const uint32_t cbase = blockIdx.x * kExNodes, v0 = cbase + tid * 4;
-  const uint32_t r_begin = blockIdx.y * rows_per, r_end = min(rows, r_begin + rows_per);
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t groups = (rows + kExRows - 1) / kExRows;
+  const uint32_t g_begin = blockIdx.x * gper, g_end = min(groups, g_begin + gper);
+  const uint32_t p_begin = blockIdx.y * pps, p_end = min(pieces, p_begin + pps);
   const uint32_t md = *maxd;
   const uint32_t P = (S && md < kSlSat) ? 32u - __clz(md + 1u) : 0u;
   const uint32_t wpm = pitch / 32;
+  const bool stager = tid < nT / 8;
+  // the plane the lane stores of its eight lanes' word (32 nodes)
+  const uint32_t pb = lane & 7u, nsh = 4u * pb;
 
-  for (uint32_t t = tid; t < q_nc; t += kExThreads) map[t] = kEmpty;
-  if (tid == 0) {
-    *cnt = 1;
-    T[0] = make_uint4(~0u, ~0u, ~0u, ~0u);
+  uint4 x[kExRows];
+  if (stager && g_begin < g_end) {
+    ex_stage_load(x, Dc, cpitch, crow_of, g_begin * kExRows, rows, tid);
+    ex_stage_write(T, x, tid);
   }
-  __syncthreads();
-  uint32_t cl[4];
+  for (uint32_t g = g_begin; g < g_end; ++g) {
+    const uint4* const cur = T + ((g - g_begin) & 1u) * nT;
+    __syncthreads();  // this group's half is written, the other half's readers are through
+    const bool more = stager && g + 1 < g_end;
+    if (more) ex_stage_load(x, Dc, cpitch, crow_of, (g + 1) * kExRows, rows, tid);
+    const uint32_t r0 = g * kExRows, nr = min(kExRows, rows - r0);
+    for (uint32_t pc = p_begin + wave; pc < p_end; pc += kExWaves) {
+      const uint32_t pbase = pc * kExPiece, v0 = pbase + lane * 4;
+      uint32_t cl[4];
+      if (v0 + 4 <= N) {
+        const uint2 c2 = *reinterpret_cast<const uint2*>(q_cls + v0);
+        cl[0] = c2.x & 0xFFFFu, cl[1] = c2.x >> 16, cl[2] = c2.y & 0xFFFFu, cl[3] = c2.y >> 16;
+      } else {
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    cl[k] = v0 + k < N ? q_cls[v0 + k] : kEmpty;
-    if (cl[k] != kEmpty && atomicCAS(&map[cl[k]], kEmpty, kClaimed) == kEmpty) {
-      const uint32_t id = atomicAdd(cnt, 1u);
-      list[id] = cl[k];
-      map[cl[k]] = id;
-    }
-  }
-  __syncthreads();
-  const uint32_t n_loc = *cnt;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) cl[k] = cl[k] != kEmpty ? map[cl[k]] : 0u;  // local numbers
-
-  // the lane's word of its wave (8 lanes = 32 nodes) and the plane it stores
-  const uint32_t w = v0 / 32, pb = lane & 7u, nsh = 4u * pb;
-  const bool d_live = D && v0 < pitch, n_live = Dn && v0 < npitch, s_live = pb < P && w < wpm;
-  for (uint32_t r0 = r_begin; r0 < r_end; r0 += kExRows) {
-    __syncthreads();  // the previous group's T is read
-    for (uint32_t lc = 1 + tid; lc < n_loc; lc += kExThreads) {
-      const uint32_t gc = list[lc];
-      uint32_t x[kExRows];
-#pragma unroll
-      for (uint32_t j = 0; j < kExRows; ++j)
-        x[j] = r0 + j < r_end ? Dc[(size_t)crow_of[r0 + j] * cpitch + gc] : 0xFFFFu;
-      T[lc] = make_uint4(x[0] | x[1] << 16, x[2] | x[3] << 16, x[4] | x[5] << 16, x[6] | x[7] << 16);
-    }
-    __syncthreads();
-    uint4 t[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) t[k] = T[cl[k]];
-#pragma unroll
-    for (uint32_t j = 0; j < kExRows; ++j) {
-      const uint32_t r = r0 + j;
-      if (r >= r_end) break;  // uniform
-      uint32_t d[4];  // 0xFFFF sign-extends to kInf; finite distances stay below 2^15
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const uint32_t pair = j / 2 == 0 ? t[k].x : j / 2 == 1 ? t[k].y : j / 2 == 2 ? t[k].z : t[k].w;
-        d[k] = (uint32_t)(int32_t)(int16_t)(pair >> (16 * (j & 1)));
+        for (int k = 0; k < 4; ++k) cl[k] = v0 + k < N ? q_cls[v0 + k] : q_nc;
       }
-      const uint32_t self = closure[r] - v0;  // the row's own node: distance 0
-      if (closure[r] - cbase < kExNodes) {    // uniform
+      uint4 t[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) d[k] = self == (uint32_t)k ? 0u : d[k];
-      }
-      if (d_live) {
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        const u32x4 o = {d[0], d[1], d[2], d[3]};
-        __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(D + (size_t)r * pitch + v0));
-      }
-      if (n_live) {
-        uint32_t b = 0;
+      for (int k = 0; k < 4; ++k) t[k] = cur[cl[k]];
+      const uint32_t w = v0 / 32;
+      const bool d_live = D && v0 < pitch, n_live = Dn && v0 < npitch, s_live = pb < P && w < wpm;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) b |= (d[k] == kInf ? 0xFFu : min(d[k], 254u)) << (8 * k);
-        __builtin_nontemporal_store(b, reinterpret_cast<uint32_t*>(Dn + (size_t)r * npitch + v0));
-      }
-      if (P) {  // uniform
-        uint32_t mine = 0;
-        for (uint32_t b = 0; b < P; ++b) {
-          uint32_t nib = ((d[0] >> b) & 1u) | ((d[1] >> b) & 1u) << 1 | ((d[2] >> b) & 1u) << 2 |
-                         ((d[3] >> b) & 1u) << 3;
-          nib <<= nsh;
-          // lanes ^ 1, ^ 2 (quad permutes), then the other quad of the eight
-          // lanes: row_shl 4 into quads 0 and 2, row_shr 4 into quads 1 and 3
-          nib |= (uint32_t)__builtin_amdgcn_update_dpp(0u, nib, 0xB1, 0xf, 0xf, true);
-          nib |= (uint32_t)__builtin_amdgcn_update_dpp(0u, nib, 0x4E, 0xf, 0xf, true);
-          nib |= (uint32_t)__builtin_amdgcn_update_dpp(0u, nib, 0x104, 0xf, 0x5, true) |
-                 (uint32_t)__builtin_amdgcn_update_dpp(0u, nib, 0x114, 0xf, 0xa, true);
-          mine = pb == b ? nib : mine;
+      for (uint32_t j = 0; j < kExRows; ++j) {
+        if (j >= nr) break;  // uniform
+        const uint32_t r = r0 + j;
+        uint32_t d[4];  // 0xFFFF sign-extends to kInf; finite distances stay below 2^15
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const uint32_t pair = j / 2 == 0 ? t[k].x : j / 2 == 1 ? t[k].y : j / 2 == 2 ? t[k].z : t[k].w;
+          d[k] = (uint32_t)(int32_t)(int16_t)(pair >> (16 * (j & 1)));
         }
-        // (plain stores: the next-hop pass reads the planes next, from L2;
-        // streaming ones cost it 12 us on fabric_full)
-        if (s_live) S[(size_t)r * kSlSlots * wpm + (size_t)w * P + pb] = mine;
+        const uint32_t own = closure[r];  // the row's own node: distance 0
+        if (own - pbase < kExPiece) {     // uniform
+          const uint32_t self = own - v0;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) d[k] = self == (uint32_t)k ? 0u : d[k];
+        }
+        if (d_live) {
+          typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+          const u32x4 o = {d[0], d[1], d[2], d[3]};
+          __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(D + (size_t)r * pitch + v0));
+        }
+        if (n_live) {
+          uint32_t b = 0;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) b |= (d[k] == kInf ? 0xFFu : min(d[k], 254u)) << (8 * k);
+          __builtin_nontemporal_store(b, reinterpret_cast<uint32_t*>(Dn + (size_t)r * npitch + v0));
+        }
+        if (P) {  // uniform
+          uint32_t mine = 0;
+          for (uint32_t b = 0; b < P; ++b) {
+            uint32_t nib = ((d[0] >> b) & 1u) | ((d[1] >> b) & 1u) << 1 | ((d[2] >> b) & 1u) << 2 |
+                           ((d[3] >> b) & 1u) << 3;
+            nib <<= nsh;
+            // lanes ^ 1, ^ 2 (quad permutes), then the other quad of the eight
+            // lanes: row_shl 4 into quads 0 and 2, row_shr 4 into quads 1 and 3
+            nib |= (uint32_t)__builtin_amdgcn_update_dpp(0u, nib, 0xB1, 0xf, 0xf, true);
+            nib |= (uint32_t)__builtin_amdgcn_update_dpp(0u, nib, 0x4E, 0xf, 0xf, true);
+            nib |= (uint32_t)__builtin_amdgcn_update_dpp(0u, nib, 0x104, 0xf, 0x5, true) |
+                   (uint32_t)__builtin_amdgcn_update_dpp(0u, nib, 0x114, 0xf, 0xa, true);
+            mine = pb == b ? nib : mine;
+          }
+          // (plain stores: the next-hop pass reads the planes next, from L2;
+          // streaming ones cost it 12 us on fabric_full)
+          if (s_live) S[(size_t)r * kSlSlots * wpm + (size_t)w * P + pb] = mine;
+        }
       }
     }
+    if (more) ex_stage_write(T + ((g + 1 - g_begin) & 1u) * nT, x, tid);
   }
 }
 
@@ -1979,12 +2007,12 @@ bool quotient_allowed(const spf_ctx* c) {
 
 // LDS of class_bfs_kernel (frontiers, row results and visited masks per class,
 // the quotient tables, the flags, the forwards bytes) and of expand_rows_kernel
-// (the staged class rows, the local class list, the class map)
+// (both halves of the staged class rows)
 size_t class_bfs_lds_bytes(uint32_t n_cls, uint32_t n_vrow) {
   const size_t nvp = (n_vrow + 7u) & ~7u, nc1 = (n_cls + 2u) & ~1u;
   return 40ull * nc1 + 2ull * (1 + kQChunk) * nvp + 16 + ((n_cls + 15u) & ~15u);
 }
-size_t expand_lds_bytes(uint32_t n_cls) { return 20ull * (kExNodes + 1) + 12 + 4ull * n_cls + 16; }
+size_t expand_lds_bytes(uint32_t n_cls) { return 2ull * 16 * ex_entries(n_cls); }
 
 // Sources per workgroup that spread `rows` over every CU: the fewest rounds
 // of `full`-source workgroups the chip needs, then those rounds filled evenly
@@ -2346,10 +2374,11 @@ spf_status launch_ecmp_sliced(spf_ctx* c, spf_plan* p, const uint32_t* D, bool h
   return SPF_OK;
 }
 
-// Class rows need the quotient sweep and both kernels' tables in LDS.
+// Class rows need the quotient sweep and both kernels' tables in LDS, and a
+// class octet per thread of the expansion's staging.
 bool class_rows_fit(const spf_ctx* c) {
   return use_quotient(c) && class_bfs_lds_bytes(c->qt.n_cls, c->qt.n_vrow) <= kMaxLds &&
-         expand_lds_bytes(c->qt.n_cls) <= kMaxLds;
+         c->qt.n_cls <= kExMaxCls && expand_lds_bytes(c->qt.n_cls) <= kMaxLds;
 }
 
 // The plan's class sources, spread over the CUs as ms_batch spreads rows.
@@ -2363,19 +2392,32 @@ spf_status launch_class_bfs(spf_ctx* c, spf_plan* p, hipStream_t s) {
   return SPF_OK;
 }
 
+// Workgroups of the expansion the chip holds at once: what its LDS and its
+// registers let a CU hold, by the runtime's own count, times CUs.
+uint32_t expand_resident(const spf_ctx* c) {
+  static size_t for_lds = 0;
+  static int per_cu = 0;
+  const size_t lds = expand_lds_bytes(c->qt.n_cls);
+  if (lds != for_lds) {
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, expand_rows_kernel, (int)kExThreads, lds) != hipSuccess)
+      n = 0;
+    per_cu = std::max(1, n);
+    for_lds = lds;
+  }
+  return c->n_cu * (uint32_t)per_cu;
+}
+
 // The closure rows from the class rows: u32 rows into D, bit planes into S,
-// u8 rows into Dn (each optional).  Node chunks x row ranges, about eight
-// workgroups per CU, ranges whole row groups.
+// u8 rows into Dn (each optional); the grid by plan_expand_grid.
 spf_status launch_expand(spf_ctx* c, spf_plan* p, uint32_t* D, uint8_t* Dn, uint32_t* S,
                          hipStream_t s) {
   const uint32_t rows = (uint32_t)p->closure.size();
-  const uint32_t span = std::max(D ? c->pitch : 0u, Dn ? c->npitch : 0u);
-  const uint32_t chunks = std::max(1u, (span + kExNodes - 1) / kExNodes);
-  const uint32_t ranges = std::max(1u, 8 * c->n_cu / chunks);
-  const uint32_t rows_per = ((rows + ranges - 1) / ranges + kExRows - 1) / kExRows * kExRows;
-  hipLaunchKernelGGL(expand_rows_kernel, dim3(chunks, (rows + rows_per - 1) / rows_per),
-                     dim3(kExThreads), expand_lds_bytes(c->qt.n_cls), s, p->d_Dc.p, p->cls_pitch,
-                     p->d_crow_of.p, p->d_closure.p, rows, rows_per, c->d_qcls.p, c->qt.n_cls, c->N,
+  const uint32_t span = std::max((D || S) ? c->pitch : 0u, Dn ? c->npitch : 0u);
+  const ExpandGrid eg = plan_expand_grid(rows, span, expand_resident(c));
+  hipLaunchKernelGGL(expand_rows_kernel, dim3(eg.wgs, eg.splits), dim3(kExThreads),
+                     expand_lds_bytes(c->qt.n_cls), s, p->d_Dc.p, p->cls_pitch, p->d_crow_of.p,
+                     p->d_closure.p, rows, eg.gper, eg.pieces, eg.pps, c->d_qcls.p, c->qt.n_cls, c->N,
                      c->pitch, c->npitch, D, Dn, S, p->d_maxd.p);
   HIP_TRY(c, hipGetLastError());
   return SPF_OK;
@@ -2863,10 +2905,15 @@ spf_status spf_plan_traffic_phases(const spf_plan* p, uint64_t* bytes) {
     bfs = rows * (4ull * (N + 1) + 8ull * E + N + 4ull * c->pitch + (p->narrow ? c->npitch : 0ull));
   }
   *bfs_bytes = bfs;
-  // expansion: Dc and the class ids read, the u32 rows (and kept u8 rows) written
-  const uint64_t cls_expand = p->cls ? 2ull * p->cls_k * p->cls_pitch + 2ull * N + rows * 4ull * c->pitch +
-                                           (p->keep_narrow ? rows * c->npitch : 0ull)
-                                     : 0ull;
+  // expansion: every closure row's class row read once per width split, the
+  // class ids once per row group; the u32 rows (and kept u8 rows) written
+  uint64_t cls_expand = 0;
+  if (p->cls) {
+    const ExpandGrid eg = plan_expand_grid((uint32_t)rows, std::max(c->pitch, p->keep_narrow ? c->npitch : 0u),
+                                           expand_resident(c));
+    cls_expand = eg.splits * rows * 2ull * p->cls_pitch + (uint64_t)eg.groups * 2ull * N +
+                 rows * 4ull * c->pitch + (p->keep_narrow ? rows * c->npitch : 0ull);
+  }
   bytes[1] = cls_expand;
   if (p->sliced && p->nh_total) {
     // planes in use: from the last execute's deepest level (one 4-byte read)
