@@ -503,6 +503,48 @@ spf_status spf_whatif_plan_create(spf_ctx* ctx, uint32_t src, const uint32_t* fa
 void spf_whatif_plan_destroy(spf_whatif_plan* plan);
 uint32_t spf_whatif_plan_failures(const spf_whatif_plan* plan);
 spf_status spf_whatif_plan_links(const spf_whatif_plan* plan, uint32_t* links /* [n_fail] */);
+/* ---- what-if batches for node failures and node drains.
+ * "Failure i" of the plan is a node x_i instead of a link:
+ *   SPF_WHATIF_NODE_DOWN   runSpf(src, true, linksFromNode(x)): every link of x
+ *                          ignored, the result of x's adjacency database being
+ *                          deleted;
+ *   SPF_WHATIF_NODE_DRAIN  runSpf(src) with x overloaded: x is recorded but not
+ *                          expanded (LinkState.cpp:831-838).
+ * The result is an ordinary spf_whatif_plan: spf_whatif_execute, _changes,
+ * _changes_db / _read / _buffers / _timing, _base, _stats, _enable_timing,
+ * _timing, _plan_failures and _plan_destroy work on it unchanged.  The digest
+ * and the list entry are the link plans': the next-hop bitset is over the
+ * distinct up neighbours of src in the UNFAILED graph, a failed neighbour's
+ * bit is simply never set.
+ *   DOWN x, x reachable in the unfailed run: x becomes unreachable -- it counts
+ *     in n_dist_changed and n_nh_changed and is listed with dist = UINT64_MAX
+ *     and zero words; only DAG descendants of x can change.
+ *   DOWN x, x unreachable: cold, digest {0, 0, hash}, no entries.
+ *   DRAIN x: x keeps its metric and next hops and is never listed or counted;
+ *     nothing is relaxed out of x; only the descendants of x's tight children
+ *     can change.  Cold when x is overloaded already, unreachable, or has no
+ *     tight out-edge.
+ * The repairs keep x in the affected set D as its root (D = x and its DAG
+ * descendants) for both kinds: down, x takes no distance; drained, x is a
+ * fixed node that settles at its unfailed metric and row and is neither a
+ * transit nor a predecessor (so it never differs from the base).
+ * fail_nodes: csr ids; NULL = every node except src, ascending (n_fail =
+ * n_nodes - 1).  The list's order is kept; a node may appear twice.
+ * SPF_E_INVALID: src in the list (failing the source is not a question this
+ * call answers), a node id >= n_nodes, an unknown kind.  SPF_E_UNSUPPORTED:
+ * graphs that take the exact path (a metric <= 0 or u64 labels) -- the exact
+ * replay would need a per-wave ignore bitmap.  SPF_WHATIF_PROF is ignored by
+ * node plans. */
+#define SPF_WHATIF_NODE_DOWN 1u  /* every link of the node ignored            */
+#define SPF_WHATIF_NODE_DRAIN 2u /* the node overloaded: reached, not transit */
+spf_status spf_whatif_plan_create_nodes(spf_ctx* ctx, uint32_t src, uint32_t kind,
+                                        const uint32_t* fail_nodes, uint32_t n_fail,
+                                        spf_whatif_plan** out);
+/* The plan's nodes; SPF_E_STATE on a link plan (as spf_whatif_plan_links is on
+ * a node plan). */
+spf_status spf_whatif_plan_nodes(const spf_whatif_plan* plan, uint32_t* nodes /* [n_fail] */);
+/* 0 = link plan, else SPF_WHATIF_NODE_* */
+spf_status spf_whatif_plan_kind(const spf_whatif_plan* plan, uint32_t* kind);
 /* d_out = [n_fail] digests, d_base = 1 digest (may be NULL).  Enqueued on
  * `stream` (a grid-resident launch for the unfailed solve); no host
  * synchronisation.  Failures with a large affected region are repaired on a

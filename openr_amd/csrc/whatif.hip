@@ -26,6 +26,20 @@
 //  Teams: a wave per hot failure while |D| fits its scratch (4096 nodes),
 //  the rest re-done by whole 1024-thread workgroups with room for all nodes.
 //
+//  Node failures (spf_whatif_plan_create_nodes) run the same repairs with the
+//  failure kind as a compile-time parameter (failed / drain_x below):
+//    * DOWN x = runSpf(src, true, linksFromNode(x)): D = the DAG descendants
+//      of x, x included (dlist[0] = x); every edge with an end at x is failed,
+//      so x gets no seed and no relaxation, stays at kInf and is counted and
+//      listed as unreachable.  Cold when x is unreachable in the unfailed run.
+//    * DRAIN x = runSpf(src) with x overloaded: D is the same set, and x sits
+//      in it (dlist[0] = x) as a node that is reached but never a transit: its
+//      tight predecessors are all outside D, so its seed is its unfailed
+//      distance and its row its unfailed row -- it contributes nothing to the
+//      digest and is never an entry -- while nothing is relaxed out of it and
+//      it is nobody's predecessor.  Cold when x is unreachable, drained
+//      already, or has no tight out-edge.
+//
 //  Digest of a result (same definition in oracle/spf_oracle.cpp):
 //    n_dist_changed, n_nh_changed (a node becoming unreachable counts in both)
 //    hash = sum over reachable v of mix(mix(v + 1) + d(v)) ^ fnv(nh(v) words)
@@ -49,6 +63,28 @@ constexpr uint32_t kWaveCap = 1024;            // |D| a wave team can hold
 constexpr size_t kBigScratch = 8ull << 30;     // HBM budget of the workgroup teams (both sets)
 constexpr size_t kWaveScratch = 8ull << 30;    // HBM budget of the wave teams
 constexpr uint32_t kDialLevels = 1024;         // distinct distances settled bucket by bucket
+
+// What a plan's failures are, a template parameter of the repairs: one link,
+// or a node down / drained (SPF_WHATIF_NODE_DOWN / SPF_WHATIF_NODE_DRAIN).
+constexpr int kLink = 0, kDown = 1, kDrain = 2;
+static_assert(kDown == SPF_WHATIF_NODE_DOWN && kDrain == SPF_WHATIF_NODE_DRAIN, "plan kinds");
+
+// Is the edge v -> u (link id `link`) unusable, in both directions, under
+// the failure: link l itself, or (node x down) any edge with an end at x.
+// `v_is_x`: the caller's row owner v is x (false where it cannot be).
+template <int KIND>
+__device__ __forceinline__ bool failed(uint32_t x, uint32_t l, bool v_is_x, uint32_t u,
+                                       uint32_t link) {
+  if constexpr (KIND == kLink) return link == l;
+  else if constexpr (KIND == kDown) return v_is_x || u == x;
+  else return false;
+}
+// Is v the node the failure drains (reached, never a transit or a predecessor).
+template <int KIND>
+__device__ __forceinline__ bool drain_x(uint32_t x, uint32_t v) {
+  if constexpr (KIND == kDrain) return v == x;
+  else return false;
+}
 
 __device__ __forceinline__ uint32_t ld(const uint32_t* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1135,10 +1171,12 @@ __device__ __forceinline__ void ph_max(uint64_t* ph, int k, uint64_t v, bool lea
 // (results then invalid, reported by spf_device_check).
 // EMIT (spf_whatif_changes): the repair also counts (em->cnode NULL) or
 // writes (fill pass) failure f's change list, before the digest loop.
-template <int TEAM, bool GROUP = false, bool CHK = false, bool GPH = false, bool EMIT = false>
+// KIND: `y` is the failed link's tight edge (kLink) or the failed node.
+template <int TEAM, bool GROUP = false, bool CHK = false, bool GPH = false, bool EMIT = false,
+          int KIND = kLink>
 __device__ bool repair(const WiGraph& g, const WiBase& B, uint32_t* mark, uint32_t* dlist,
                        uint32_t* dnew, uint32_t* nhn, uint32_t* lvl, uint32_t* ord, uint32_t cap,
-                       TeamCtl* ctl, uint32_t tt, uint32_t e_fail, spf_whatif_digest* out,
+                       TeamCtl* ctl, uint32_t tt, uint32_t y, spf_whatif_digest* out,
                        uint64_t* ph = nullptr, const WiEmit* em = nullptr, uint32_t f = 0) {
   // diagnostics (SPF_WHATIF_PROF): 12 counters, accumulated over the team's
   // failures (ph_add) -- [0] repairs, [1..5] 100 MHz ticks in D discovery,
@@ -1166,8 +1204,10 @@ __device__ bool repair(const WiGraph& g, const WiBase& B, uint32_t* mark, uint32
     return x;
   };
   const uint32_t lane = tt & 63, wv = tt >> 6;
-  const uint32_t l = g.link[e_fail];
-  const uint32_t b = g.col[e_fail];
+  // D's root b = dlist[0]: the failed link's head, or the failed node x
+  const uint32_t x = y;
+  const uint32_t l = KIND == kLink ? g.link[y] : 0u;
+  const uint32_t b = KIND == kLink ? g.col[y] : y;
   if (tt == 0) {
     stw<GROUP>(&ctl->n, 1u);
     stw<GROUP>(&ctl->ovf, 0u);
@@ -1268,7 +1308,8 @@ __device__ bool repair(const WiGraph& g, const WiBase& B, uint32_t* mark, uint32
     wave_edges(g.row_ptr, v, in, [&](uint32_t k, uint32_t e, bool act) {
       uint32_t s = kInf;
       const uint4 q = act ? g.ed[e] : make_uint4(0u, 0u, l, 0u);
-      if (act && q.z != l) {
+      // (the row owner is x exactly at D index 0)
+      if (act && !failed<KIND>(x, l, c0 + k == 0, q.x, q.z)) {
         const uint32_t u = q.x;
         if (ldw<GROUP>(&mark[u]) == kInf && !(g.ovl[u] && u != g.src)) {
           const uint32_t du = B.dist[u];
@@ -1291,9 +1332,9 @@ __device__ bool repair(const WiGraph& g, const WiBase& B, uint32_t* mark, uint32
     const uint32_t dv = ldw<GROUP>(&dnew[i]);
     uint32_t acc = 0;
     for (uint32_t e = g.row_ptr[v]; e < g.row_ptr[v + 1]; ++e) {
-      if (g.link[e] == l) continue;
+      if (failed<KIND>(x, l, false, g.col[e], g.link[e])) continue;  // (dnew[x] is kInf: v != x)
       const uint32_t u = g.col[e];
-      if (g.ovl[u] && u != g.src) continue;
+      if ((g.ovl[u] && u != g.src) || drain_x<KIND>(x, u)) continue;
       const uint32_t mu = chk(ldw<GROUP>(&mark[u]), n, true, 5, kInf);
       const uint32_t du = mu != kInf ? ldw<GROUP>(&dnew[mu]) : B.dist[u];
       if (du == kInf || du + in_w(g, e) != dv) continue;
@@ -1379,7 +1420,7 @@ __device__ bool repair(const WiGraph& g, const WiBase& B, uint32_t* mark, uint32
       const bool valid = lane < cs && q < K;
       const uint32_t i = valid ? chk(ldw<GROUP>(&ord[q]), n, false, 9, 0) : 0u;
       const uint32_t v = valid ? chk(dlist[i], g.N, false, 10, b) : 0u;
-      const uint32_t transit = valid && !g.ovl[v];  // drained: no transit
+      const uint32_t transit = valid && !g.ovl[v] && !drain_x<KIND>(x, v);  // drained: no transit
       const uint32_t jb = valid ? g.nbr_bit[v] : 0u;
       uint32_t cur = kInf, acc = 0;  // row_pairs' open row
       wave_edges(g.row_ptr, v, valid, [&](uint32_t k, uint32_t e, bool act) {
@@ -1387,10 +1428,11 @@ __device__ bool repair(const WiGraph& g, const WiBase& B, uint32_t* mark, uint32
         uint32_t u = 0, mu = kInf;
         bool tight = false, from_src = false;
         const uint4 q = act ? g.ed[e] : make_uint4(0u, 0u, l, 0u);
-        if (act && q.z != l) {
+        // (a level's nodes hold a distance: none is a downed x)
+        if (act && !failed<KIND>(x, l, false, q.x, q.z)) {
           u = q.x;
           mu = chk(ldw<GROUP>(&mark[u]), n, true, 13, kInf);
-          if (!(g.ovl[u] && u != g.src)) {
+          if (!(g.ovl[u] && u != g.src) && !drain_x<KIND>(x, u)) {
             const uint32_t du = mu != kInf ? ldw<GROUP>(&dnew[mu]) : B.dist[u];
             tight = du != kInf && du + (g.hop ? 1u : q.w) == t;
           }
@@ -1424,9 +1466,9 @@ __device__ bool repair(const WiGraph& g, const WiBase& B, uint32_t* mark, uint32
       for (uint32_t i = tt; i < n; i += TEAM) {
         const uint32_t v = dlist[i];
         const uint32_t dv = ldw<GROUP>(&dnew[i]);
-        if (dv == kInf || g.ovl[v]) continue;
+        if (dv == kInf || g.ovl[v] || drain_x<KIND>(x, v)) continue;
         for (uint32_t e = g.row_ptr[v]; e < g.row_ptr[v + 1]; ++e) {
-          if (g.link[e] == l) continue;
+          if (failed<KIND>(x, l, false, g.col[e], g.link[e])) continue;
           const uint32_t ic = chk(ldw<GROUP>(&mark[g.col[e]]), n, true, 14, kInf);
           if (ic == kInf) continue;
           const uint32_t nd = dv + g.wt[e];
@@ -1647,10 +1689,10 @@ __device__ __forceinline__ uint32_t ws_find(const WaveSet& s, uint32_t v) {
 // (ballot + mbcnt compaction instead of counter atomics); the level list of
 // a D of <= 64 nodes never leaves the registers (ds_permute).  |D| <= cap <=
 // kDialLevels distinct values, so Dial always settles (no fallback sweeps).
-template <bool CHK, bool GPH = false, bool EMIT = false>
+template <bool CHK, bool GPH = false, bool EMIT = false, int KIND = kLink>
 __device__ bool repair_wave(const WiGraph& g, const WiBase& B, const WaveSet& hs, uint32_t* dlist,
                             uint32_t* dnew, uint32_t* nhn, uint32_t* ord, uint32_t cap,
-                            TeamCtl* ctl, uint32_t lane, uint32_t e_fail, spf_whatif_digest* out,
+                            TeamCtl* ctl, uint32_t lane, uint32_t y, spf_whatif_digest* out,
                             uint64_t* ph, const WiEmit* em = nullptr, uint32_t f = 0) {
   uint64_t tprev = ph ? wall_clock64() : 0ull;
 #define WI_STAMP(k)                                \
@@ -1673,8 +1715,9 @@ __device__ bool repair_wave(const WiGraph& g, const WiBase& B, const WaveSet& hs
   };
   auto sync = [&]() { team_sync<64>(ctl, g.fault); };
   const uint32_t W = g.W;
-  const uint32_t l = g.link[e_fail];
-  const uint32_t b = g.col[e_fail];
+  const uint32_t x = y;  // (repair(): l, b)
+  const uint32_t l = KIND == kLink ? g.link[y] : 0u;
+  const uint32_t b = KIND == kLink ? g.col[y] : y;
   if (lane == 0) {
     dlist[0] = b;
     bool full = false;
@@ -1751,7 +1794,7 @@ __device__ bool repair_wave(const WiGraph& g, const WiBase& B, const WaveSet& hs
     wave_edges(g.row_ptr, v, i < n, [&](uint32_t k, uint32_t e, bool act) {
       uint32_t s = kInf;
       const uint4 q = act ? g.ed[e] : make_uint4(0u, 0u, l, 0u);
-      if (act && q.z != l) {
+      if (act && !failed<KIND>(x, l, c0 + k == 0, q.x, q.z)) {
         const uint32_t u = q.x;
         if (ws_find(hs, u) == kInf && !(g.ovl[u] && u != g.src)) {
           const uint32_t du = B.dist[u];
@@ -1816,7 +1859,7 @@ __device__ bool repair_wave(const WiGraph& g, const WiBase& B, const WaveSet& hs
         i = valid ? chk(ldw<false>(&ord[q]), n, false, 9, 0) : 0u;
         v = valid ? chk(ldw<false>(&dlist[i]), g.N, false, 10, b) : 0u;
       }
-      const uint32_t transit = valid && !g.ovl[v];  // drained: no transit
+      const uint32_t transit = valid && !g.ovl[v] && !drain_x<KIND>(x, v);  // drained: no transit
       const uint32_t jb = valid ? g.nbr_bit[v] : 0u;
       uint32_t cur = kInf, acc = 0;  // row_pairs' open row
       wave_edges(g.row_ptr, v, valid, [&](uint32_t k, uint32_t e, bool act) {
@@ -1824,10 +1867,10 @@ __device__ bool repair_wave(const WiGraph& g, const WiBase& B, const WaveSet& hs
         uint32_t u = 0, mu = kInf;
         bool tight = false, from_src = false;
         const uint4 q = act ? g.ed[e] : make_uint4(0u, 0u, l, 0u);
-        if (act && q.z != l) {
+        if (act && !failed<KIND>(x, l, false, q.x, q.z)) {
           u = q.x;
           mu = chk(ws_find(hs, u), n, true, 13, kInf);
-          if (!(g.ovl[u] && u != g.src)) {
+          if (!(g.ovl[u] && u != g.src) && !drain_x<KIND>(x, u)) {
             const uint32_t du = mu != kInf ? ldw<false>(&dnew[mu]) : B.dist[u];
             tight = du != kInf && du + (g.hop ? 1u : q.w) == t;
           }
@@ -1928,7 +1971,7 @@ __device__ __forceinline__ uint64_t* prof_row(unsigned long long* prof, size_t t
 // instances of the three repair kernels, with one more argument, the WiEmit,
 // as a trailing pack -- the production instances keep their argument list and
 // compile to what they did without it.
-template <int PROF, bool EMIT = false, class... EM>
+template <int PROF, bool EMIT = false, int KIND = kLink, class... EM>
 __global__ __launch_bounds__(256) void repair_wave_kernel(
     WiGraph g, WiBase B, const uint2* __restrict__ hot, const uint32_t* __restrict__ n_hot,
     uint32_t* cursor, uint2* big, uint32_t* n_big, unsigned long long* tab, uint32_t* dlist,
@@ -1953,9 +1996,9 @@ __global__ __launch_bounds__(256) void repair_wave_kernel(
     k = __builtin_amdgcn_readlane(k, 0);
     if (k >= total) break;
     const uint2 h = hot[k];
-    if (!repair_wave<PROF != 0, PROF == 2, EMIT>(g, B, hs, dlist, dnew, nhn, ord, cap, &ctl[w], lane,
-                                                h.y, out + h.x, PROF == 1 ? ph : gph,
-                                                emit_arg(em...), h.x)) {
+    if (!repair_wave<PROF != 0, PROF == 2, EMIT, KIND>(g, B, hs, dlist, dnew, nhn, ord, cap, &ctl[w],
+                                                      lane, h.y, out + h.x, PROF == 1 ? ph : gph,
+                                                      emit_arg(em...), h.x)) {
       if (lane == 0) big[atomicAdd(n_big, 1u)] = h;
     }
   }
@@ -1964,7 +2007,7 @@ __global__ __launch_bounds__(256) void repair_wave_kernel(
       for (int q = 0; q < 12; ++q) r[q] = ph[q];
 }
 
-template <int PROF, bool EMIT = false, class... EM>
+template <int PROF, bool EMIT = false, int KIND = kLink, class... EM>
 __global__ __launch_bounds__(1024) void repair_block_kernel(
     WiGraph g, WiBase B, const uint2* __restrict__ big, const uint32_t* __restrict__ n_big,
     uint32_t* mark, uint32_t* dlist, uint32_t* dnew, uint32_t* nhn, uint32_t* lvl, uint32_t* ord,
@@ -1987,9 +2030,9 @@ __global__ __launch_bounds__(1024) void repair_block_kernel(
       PROF == 2 ? prof_row(prof, team, prof_rows, 2, threadIdx.x == 0 ? g.fault : nullptr) : nullptr;
   for (uint32_t k = blockIdx.x; k < total; k += gridDim.x) {
     const uint2 h = big[k];
-    repair<1024, false, false, PROF == 2, EMIT>(g, B, mark, dlist, dnew, nhn, lvl, ord, g.N, &ctl,
-                                                threadIdx.x, h.y, out + h.x, PROF == 1 ? ph : gph,
-                                                emit_arg(em...), h.x);
+    repair<1024, false, false, PROF == 2, EMIT, KIND>(g, B, mark, dlist, dnew, nhn, lvl, ord, g.N,
+                                                      &ctl, threadIdx.x, h.y, out + h.x,
+                                                      PROF == 1 ? ph : gph, emit_arg(em...), h.x);
   }
   if (PROF == 1 && threadIdx.x == 0)
     if (uint64_t* r = prof_row(prof, team, prof_rows, 2, g.fault))
@@ -2027,7 +2070,7 @@ __global__ __launch_bounds__(1024) void sort_big_kernel(const uint2* __restrict_
 // both progress from the start.  Members of a team sit on one XCD (blocks x
 // and x + 8 share one); teams pull failures, largest first.
 constexpr int kGroupWg = 512;
-template <int G, int PROF, bool EMIT = false, class... EM>
+template <int G, int PROF, bool EMIT = false, int KIND = kLink, class... EM>
 __global__ __launch_bounds__(kGroupWg) void repair_group_kernel(
     WiGraph g, WiBase B, const uint2* __restrict__ big, const uint32_t* __restrict__ n_big,
     uint32_t* cursor, TeamCtl* ctls, uint32_t* mark, uint32_t* dlist, uint32_t* dnew,
@@ -2056,9 +2099,9 @@ __global__ __launch_bounds__(kGroupWg) void repair_group_kernel(
     const uint32_t k = ldw<true>(&ctl->next);
     if (k >= total) break;  // team-uniform
     const uint2 h = big[k];
-    repair<TEAM, true, false, PROF == 2, EMIT>(g, B, mark, dlist, dnew, nhn, lvl, ord, g.N, ctl, tt,
-                                               h.y, out + h.x, PROF == 1 ? ph : gph,
-                                               emit_arg(em...), h.x);
+    repair<TEAM, true, false, PROF == 2, EMIT, KIND>(g, B, mark, dlist, dnew, nhn, lvl, ord, g.N, ctl,
+                                                     tt, h.y, out + h.x, PROF == 1 ? ph : gph,
+                                                     emit_arg(em...), h.x);
   }
   if (PROF == 1 && tt == 0)
     if (uint64_t* r = prof_row(prof, team, prof_rows, 3, g.fault))
@@ -2121,20 +2164,26 @@ const void* group_kernel(uint32_t G, int prof) {
 // the EMIT instances (change lists; PROF 0 only)
 const void* group_kernel_emit(uint32_t G) {
   switch (G) {
-    case 2: return (const void*)repair_group_kernel<2, 0, true, WiEmit>;
-    case 4: return (const void*)repair_group_kernel<4, 0, true, WiEmit>;
-    case 8: return (const void*)repair_group_kernel<8, 0, true, WiEmit>;
-    case 16: return (const void*)repair_group_kernel<16, 0, true, WiEmit>;
+    case 2: return (const void*)repair_group_kernel<2, 0, true, kLink, WiEmit>;
+    case 4: return (const void*)repair_group_kernel<4, 0, true, kLink, WiEmit>;
+    case 8: return (const void*)repair_group_kernel<8, 0, true, kLink, WiEmit>;
+    case 16: return (const void*)repair_group_kernel<16, 0, true, kLink, WiEmit>;
     default: return nullptr;
   }
 }
+
+// the node plans' instances (defined, and so instantiated, after every link
+// instance: the link kernels keep their places in the code object)
+const void* group_kernel_nodes(int kind, uint32_t G, bool emit);
+const void* wave_kernel_nodes(int kind, bool emit);
 
 // one launch, a workgroup per CU (every member of every team resident at
 // once: the team barrier's precondition); with `em` the EMIT instance, the
 // occupancy check made with its own pointer
 hipError_t launch_group(uint32_t G, GroupArgs& a, uint32_t n_cu, int prof, hipStream_t s,
-                        const WiEmit* em = nullptr) {
-  const void* k = em ? group_kernel_emit(G) : group_kernel(G, a.prof ? prof : 0);
+                        const WiEmit* em = nullptr, int kind = kLink) {
+  const void* k = kind != kLink ? group_kernel_nodes(kind, G, em != nullptr)
+                  : em ? group_kernel_emit(G) : group_kernel(G, a.prof ? prof : 0);
   if (!k) return hipErrorInvalidValue;
   WiEmit e = em ? *em : WiEmit{};
   void* args[] = {&a.g, &a.B, &a.big, &a.n_big, &a.cursor, &a.ctls, &a.mark, &a.dlist, &a.dnew,
@@ -2192,6 +2241,7 @@ __global__ void base_digest_kernel(spf_whatif_digest* o, const unsigned long lon
 struct spf_whatif_plan {
   spf_ctx* ctx = nullptr;
   uint32_t src = 0, n_fail = 0, W = 0, wave_teams = 0;
+  uint32_t kind = 0;   // 0: d_fails holds link ids, else SPF_WHATIF_NODE_*: node ids
   uint64_t epoch = 0;  // graph state the plan was derived from
   DevBuf<uint32_t> d_fails, d_link_edge, d_nbr_bit, d_dist, d_q, d_q2, d_bm, d_nhb, d_ctr;
   DevBuf<uint32_t> d_bar;  // the base kernel's grid-barrier counters
@@ -2348,11 +2398,15 @@ spf_status run_base(spf_whatif_plan* p, const WiGraph& g, hipStream_t s) {
   return SPF_OK;
 }
 
+spf_status run_failures_nodes(spf_whatif_plan* p, const WiGraph& g, spf_whatif_digest* d_out,
+                              hipStream_t s, const WiEmit* em);  // (below)
+
 // The failures of the plan's list on `s` and the context's side stream:
 // digests into d_out; with `em` the EMIT instances, which also count or fill
 // the change lists (one pass per call).
 spf_status run_failures(spf_whatif_plan* p, const WiGraph& g, spf_whatif_digest* d_out,
                         hipStream_t s, const WiEmit* em) {
+  if (p->kind) return run_failures_nodes(p, g, d_out, s, em);
   spf_ctx* c = p->ctx;
   // 2. failures
   HIP_TRY(c, hipMemsetAsync(p->d_cnt.p, 0, 32, s));
@@ -2388,7 +2442,7 @@ spf_status run_failures(spf_whatif_plan* p, const WiGraph& g, spf_whatif_digest*
     if (!grouped) {
       const uint32_t bt = p->big_teams;
       if (em)
-        hipLaunchKernelGGL((repair_block_kernel<0, true, WiEmit>), dim3(bt), dim3(1024), 0, side, g, B,
+        hipLaunchKernelGGL((repair_block_kernel<0, true, kLink, WiEmit>), dim3(bt), dim3(1024), 0, side, g, B,
                            p->d_big0.p, p->d_cnt.p + 3, p->c_mark.p, p->c_dlist.p, p->c_dnew.p,
                            p->c_nhn.p, p->c_lvl.p, p->c_ord.p, d_out, nullptr, 0u, *em);
       else if (p->prof_mode == 2)
@@ -2410,7 +2464,7 @@ spf_status run_failures(spf_whatif_plan* p, const WiGraph& g, spf_whatif_digest*
       unsigned long long* wp = p->d_prof.p ? p->d_prof.p + 16ull * (p->big_teams + 1) : nullptr;
       const uint32_t wr = p->wave_teams;
       if (em)
-        hipLaunchKernelGGL((repair_wave_kernel<0, true, WiEmit>), dim3(p->wave_teams / 4), dim3(256), 0,
+        hipLaunchKernelGGL((repair_wave_kernel<0, true, kLink, WiEmit>), dim3(p->wave_teams / 4), dim3(256), 0,
                            s, g, B, p->d_hot.p, p->d_cnt.p, p->d_cnt.p + 1, p->d_big.p, p->d_cnt.p + 2,
                            p->w_tab.p, p->w_dlist.p, p->w_dnew.p, p->w_nhn.p, p->w_lvl.p,
                            p->w_ord.p, d_out, p->wave_cap, p->tab_log2, nullptr, 0u, *em);
@@ -2432,7 +2486,7 @@ spf_status run_failures(spf_whatif_plan* p, const WiGraph& g, spf_whatif_digest*
     }
     HIP_TRY(c, hipGetLastError());
     if (em)
-      hipLaunchKernelGGL((repair_block_kernel<0, true, WiEmit>), dim3(p->big_teams), dim3(1024), 0, s,
+      hipLaunchKernelGGL((repair_block_kernel<0, true, kLink, WiEmit>), dim3(p->big_teams), dim3(1024), 0, s,
                          g, B, p->d_big.p, p->d_cnt.p + 2, p->b_mark.p, p->b_dlist.p, p->b_dnew.p,
                          p->b_nhn.p, p->b_lvl.p, p->b_ord.p, d_out, nullptr, 0u, *em);
     else
@@ -2445,50 +2499,172 @@ spf_status run_failures(spf_whatif_plan* p, const WiGraph& g, spf_whatif_digest*
   return SPF_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-spf_status spf_whatif_plan_create(spf_ctx* c, uint32_t src, const uint32_t* fail_links,
-                                  uint32_t n_fail, spf_whatif_plan** out) {
-  if (!c || !out) return fail(c, SPF_E_INVALID, "spf_whatif_plan_create: NULL argument");
-  *out = nullptr;
-  if (!c->loaded) return fail(c, SPF_E_STATE, "no graph loaded");
-  if (src >= c->N) return fail(c, SPF_E_INVALID, "source %u out of range", src);
-  auto p = std::make_unique<spf_whatif_plan>();
-  p->ctx = c;
-  p->src = src;
-  const uint32_t N = c->N, E = c->E;
-  // link -> one of its directed edges (up links only: a dead slot is a self-loop)
-  std::vector<uint32_t> link_edge((size_t)c->max_link + 1, kInf);
-  for (uint32_t u = 0; u < N; ++u)
-    for (uint32_t e = c->row_ptr[u]; e < c->row_ptr[u + 1]; ++e)
-      if (c->col[e] != u && link_edge[c->link[e]] == kInf) link_edge[c->link[e]] = e;
-  std::vector<uint32_t> fails;
-  if (fail_links) {
-    fails.assign(fail_links, fail_links + n_fail);
-    for (uint32_t l : fails)
-      if (l > c->max_link || link_edge[l] == kInf)
-        return fail(c, SPF_E_INVALID, "link %u is not an up link of the graph", l);
-  } else {  // every up link, ascending id
-    for (uint32_t l = 0; l <= c->max_link && E; ++l)
-      if (link_edge[l] != kInf) fails.push_back(l);
+// ---------------------------------------------------------------------------
+//  node plans: their kernels and launches.  Kept below every use of a link
+//  instance: templates are emitted in the order they are first named, so the
+//  link kernels sit in the code object where they sat without node plans.
+// ---------------------------------------------------------------------------
+// Node failures: cold -> digest now, hot -> work item (failure, node x), to
+// the workgroup teams when x's parent subtree exceeds wave_cap.  DOWN is hot
+// whenever x is reachable (x itself changes); DRAIN when x is reachable, not
+// drained already and the tail of a tight edge (the scan stops at the first).
+template <int KIND>
+__global__ void classify_nodes_kernel(WiGraph g, const uint32_t* __restrict__ dist,
+                                      const unsigned long long* __restrict__ H,
+                                      const uint32_t* __restrict__ fails, uint32_t n_fail,
+                                      const uint32_t* __restrict__ sub, uint32_t wave_cap,
+                                      spf_whatif_digest* out, uint2* hot, uint32_t* n_hot,
+                                      uint2* big, uint32_t* n_big) {
+  const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= n_fail) return;
+  const uint32_t x = fails[f];  // < N, != src (checked at plan creation)
+  const uint32_t dx = dist[x];
+  bool is_hot = dx != kInf;
+  if (is_hot && KIND == kDrain) {
+    is_hot = false;
+    if (!g.ovl[x])
+      for (uint32_t e = g.row_ptr[x]; e < g.row_ptr[x + 1] && !is_hot; ++e)
+        is_hot = g.col[e] != x && dx + g.wt[e] == dist[g.col[e]];
   }
-  p->n_fail = (uint32_t)fails.size();
-  if (c->nonpos || c->needs64) {
-    // zero / negative metrics, u64 labels: the exact kernel replays
-    // runSpf(src, true, {l}) for every failure touching a pathLink
-    HIP_TRY(c, hipSetDevice(c->device));
-    p->exact = std::make_unique<spfi::ExactWhatIf>();
-    const spf_status st = exact_whatif_prepare(c, p->exact.get(), src, fails, link_edge);
-    if (st != SPF_OK) return st;
-    if (!fails.empty()) HIP_TRY(c, p->d_fails.upload(fails.data(), fails.size(), c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    p->W = p->exact->W;
-    p->epoch = c->epoch;
-    *out = p.release();
-    return SPF_OK;
+  if (!is_hot) {
+    out[f] = spf_whatif_digest{0u, 0u, (uint64_t)*H};
+  } else if (sub[x] > wave_cap) {  // |D| >= subtree: a workgroup's repair
+    big[atomicAdd(n_big, 1u)] = make_uint2(f, x);
+  } else {
+    hot[atomicAdd(n_hot, 1u)] = make_uint2(f, x);
   }
+}
+
+// sort_big_kernel for node plans: an item's y is the failed node itself, the
+// root of its subtree.
+template <int KIND>
+__global__ __launch_bounds__(1024) void sort_big_nodes_kernel(const uint2* __restrict__ in,
+                                                              const uint32_t* __restrict__ n_in,
+                                                              const uint32_t* __restrict__ sub,
+                                                              uint2* __restrict__ out) {
+  const uint32_t n = *n_in;
+  for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
+    if (n > kSortCap) {
+      out[i] = in[i];
+      continue;
+    }
+    const uint32_t ki = sub[in[i].y];
+    uint32_t r = 0;
+    for (uint32_t j = 0; j < n; ++j) {
+      const uint32_t kj = sub[in[j].y];
+      r += kj > ki || (kj == ki && j < i);
+    }
+    out[r] = in[i];
+  }
+}
+
+// the node plans' instances (no profiled ones)
+template <int KIND>
+const void* group_kernel_nodes(uint32_t G, bool emit) {
+  switch (G) {
+    case 2: return emit ? (const void*)repair_group_kernel<2, 0, true, KIND, WiEmit>
+                        : (const void*)repair_group_kernel<2, 0, false, KIND>;
+    case 4: return emit ? (const void*)repair_group_kernel<4, 0, true, KIND, WiEmit>
+                        : (const void*)repair_group_kernel<4, 0, false, KIND>;
+    case 8: return emit ? (const void*)repair_group_kernel<8, 0, true, KIND, WiEmit>
+                        : (const void*)repair_group_kernel<8, 0, false, KIND>;
+    case 16: return emit ? (const void*)repair_group_kernel<16, 0, true, KIND, WiEmit>
+                         : (const void*)repair_group_kernel<16, 0, false, KIND>;
+    default: return nullptr;
+  }
+}
+const void* group_kernel_nodes(int kind, uint32_t G, bool emit) {
+  return kind == kDown ? group_kernel_nodes<kDown>(G, emit) : group_kernel_nodes<kDrain>(G, emit);
+}
+const void* wave_kernel_nodes(int kind, bool emit) {
+  if (kind == kDown)
+    return emit ? (const void*)repair_wave_kernel<0, true, kDown, WiEmit>
+                : (const void*)repair_wave_kernel<0, false, kDown>;
+  return emit ? (const void*)repair_wave_kernel<0, true, kDrain, WiEmit>
+              : (const void*)repair_wave_kernel<0, false, kDrain>;
+}
+
+// run_failures of a node plan: the same launches on the same streams and
+// scratch, the KIND instances of the repairs, work items (failure, node).
+template <int KIND>
+spf_status run_failures_nodes_k(spf_whatif_plan* p, const WiGraph& g, spf_whatif_digest* d_out,
+                              hipStream_t s, const WiEmit* em) {
+  spf_ctx* c = p->ctx;
+  HIP_TRY(c, hipMemsetAsync(p->d_cnt.p, 0, 32, s));
+  if (p->group) HIP_TRY(c, hipMemsetAsync(p->d_ctl.p, 0, sizeof(TeamCtl) * p->group_teams, s));
+  if (!p->n_fail) return SPF_OK;
+  hipLaunchKernelGGL(classify_nodes_kernel<KIND>, dim3((p->n_fail + 255) / 256), dim3(256), 0, s, g,
+                     p->d_dist.p, p->d_H.p, p->d_fails.p, p->n_fail, p->d_sub.p, p->classify_cap, d_out, p->d_hot.p, p->d_cnt.p, p->d_big0.p, p->d_cnt.p + 3);
+  HIP_TRY(c, hipGetLastError());
+  WiBase B{p->d_dist.p, p->d_nhb.p, p->d_H.p};
+  hipStream_t side = c->side ? c->side : s;
+  if (c->side) {
+    HIP_TRY(c, hipEventRecord(c->side_fork, s));
+    HIP_TRY(c, hipStreamWaitEvent(c->side, c->side_fork, 0));
+  }
+  bool grouped = false;
+  if (p->group) {
+    hipLaunchKernelGGL(sort_big_nodes_kernel<KIND>, dim3(1), dim3(1024), 0, side, p->d_big0.p,
+                       p->d_cnt.p + 3, p->d_sub.p, p->d_big1.p);
+    HIP_TRY(c, hipGetLastError());
+    GroupArgs ga{g, B, p->d_big1.p, p->d_cnt.p + 3, p->d_cnt.p + 4,
+                 reinterpret_cast<TeamCtl*>(p->d_ctl.p), p->c_mark.p, p->c_dlist.p, p->c_dnew.p,
+                 p->c_nhn.p, p->c_lvl.p, p->c_ord.p, d_out, nullptr, 0u};
+    if (const spf_status st = resident_order(c, side); st != SPF_OK) return st;
+    grouped = launch_group(p->group, ga, c->n_cu, 0, side, em, KIND) == hipSuccess;
+    if (!grouped) (void)hipGetLastError();  // fall back to one-workgroup teams
+    else if (const spf_status st = resident_done(c, side); st != SPF_OK) return st;
+  }
+  if (!grouped) {
+    if (em)
+      hipLaunchKernelGGL((repair_block_kernel<0, true, KIND, WiEmit>), dim3(p->big_teams), dim3(1024), 0,
+                         side, g, B, p->d_big0.p, p->d_cnt.p + 3, p->c_mark.p, p->c_dlist.p,
+                         p->c_dnew.p, p->c_nhn.p, p->c_lvl.p, p->c_ord.p, d_out, nullptr, 0u, *em);
+    else
+      hipLaunchKernelGGL((repair_block_kernel<0, false, KIND>), dim3(p->big_teams), dim3(1024), 0, side,
+                         g, B, p->d_big0.p, p->d_cnt.p + 3, p->c_mark.p, p->c_dlist.p, p->c_dnew.p,
+                         p->c_nhn.p, p->c_lvl.p, p->c_ord.p, d_out, nullptr, 0u);
+  }
+  HIP_TRY(c, hipGetLastError());
+  if (c->side) HIP_TRY(c, hipEventRecord(c->side_join, c->side));
+  if (em)
+    hipLaunchKernelGGL((repair_wave_kernel<0, true, KIND, WiEmit>), dim3(p->wave_teams / 4), dim3(256), 0,
+                       s, g, B, p->d_hot.p, p->d_cnt.p, p->d_cnt.p + 1, p->d_big.p, p->d_cnt.p + 2,
+                       p->w_tab.p, p->w_dlist.p, p->w_dnew.p, p->w_nhn.p, p->w_lvl.p, p->w_ord.p,
+                       d_out, p->wave_cap, p->tab_log2, nullptr, 0u, *em);
+  else
+    hipLaunchKernelGGL((repair_wave_kernel<0, false, KIND>), dim3(p->wave_teams / 4), dim3(256), 0, s, g,
+                       B, p->d_hot.p, p->d_cnt.p, p->d_cnt.p + 1, p->d_big.p, p->d_cnt.p + 2,
+                       p->w_tab.p, p->w_dlist.p, p->w_dnew.p, p->w_nhn.p, p->w_lvl.p, p->w_ord.p,
+                       d_out, p->wave_cap, p->tab_log2, nullptr, 0u);
+  HIP_TRY(c, hipGetLastError());
+  // the wave teams' overflow (|D| > wave_cap), after them on `s`
+  if (em)
+    hipLaunchKernelGGL((repair_block_kernel<0, true, KIND, WiEmit>), dim3(p->big_teams), dim3(1024), 0, s,
+                       g, B, p->d_big.p, p->d_cnt.p + 2, p->b_mark.p, p->b_dlist.p, p->b_dnew.p,
+                       p->b_nhn.p, p->b_lvl.p, p->b_ord.p, d_out, nullptr, 0u, *em);
+  else
+    hipLaunchKernelGGL((repair_block_kernel<0, false, KIND>), dim3(p->big_teams), dim3(1024), 0, s, g, B,
+                       p->d_big.p, p->d_cnt.p + 2, p->b_mark.p, p->b_dlist.p, p->b_dnew.p, p->b_nhn.p,
+                       p->b_lvl.p, p->b_ord.p, d_out, nullptr, 0u);
+  HIP_TRY(c, hipGetLastError());
+  if (c->side) HIP_TRY(c, hipStreamWaitEvent(s, c->side_join, 0));
+  return SPF_OK;
+}
+
+spf_status run_failures_nodes(spf_whatif_plan* p, const WiGraph& g, spf_whatif_digest* d_out,
+                              hipStream_t s, const WiEmit* em) {
+  return p->kind == (uint32_t)kDown ? run_failures_nodes_k<kDown>(p, g, d_out, s, em)
+                                    : run_failures_nodes_k<kDrain>(p, g, d_out, s, em);
+}
+
+// The part of plan creation that link and node plans share, from the source's
+// neighbour bits to the teams' scratch: p holds ctx, src, kind and n_fail,
+// `fails` its list (link ids with `link_edge`, node ids without).
+spf_status plan_build(spf_ctx* c, std::unique_ptr<spf_whatif_plan>& p,
+                      const std::vector<uint32_t>& fails, const std::vector<uint32_t>* link_edge,
+                      spf_whatif_plan** out) {
+  const uint32_t N = c->N, src = p->src;
   // bit of each distinct up neighbour of src
   std::vector<uint32_t> nbr_bit(N, kInf);
   const uint32_t k = c->nb_ptr[src + 1] - c->nb_ptr[src];
@@ -2510,7 +2686,7 @@ spf_status spf_whatif_plan_create(spf_ctx* c, uint32_t src, const uint32_t* fail
   }
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, p->d_fails.upload(fails.data(), fails.size(), c->stream));
-  HIP_TRY(c, p->d_link_edge.upload(link_edge.data(), link_edge.size(), c->stream));
+  if (link_edge) HIP_TRY(c, p->d_link_edge.upload(link_edge->data(), link_edge->size(), c->stream));
   HIP_TRY(c, p->d_nbr_bit.upload(nbr_bit.data(), N, c->stream));
   HIP_TRY(c, p->d_dist.alloc(N));
   HIP_TRY(c, p->d_q.alloc(N));
@@ -2564,21 +2740,37 @@ spf_status spf_whatif_plan_create(spf_ctx* c, uint32_t src, const uint32_t* fail
     // workgroup's 2 waves share 512 VGPRs (granule 8).  Fewer wave teams per
     // CU until both fit.  (Round 4's stamp pointer in the wave kernel --
     // 75 -> 80+ VGPRs at 4 waves per SIMD beside 2 x 88 -- broke this sum.)
-    hipFuncAttributes fw{}, fg{};
+    // A node plan launches its own instances: the sum is made with their
+    // registers (the larger of the digest and the list instance of each).
     const int pm = whatif_prof_mode();
-    const void* wk = pm == 2 ? (const void*)repair_wave_kernel<2>
-                             : pm == 1 ? (const void*)repair_wave_kernel<1> : (const void*)repair_wave_kernel<0>;
-    HIP_TRY(c, hipFuncGetAttributes(&fw, wk));
-    HIP_TRY(c, hipFuncGetAttributes(&fg, group_kernel(p->group, pm)));
+    int rw = 0, rg = 0;
+    const auto regs = [](const void* k, int& most) {
+      hipFuncAttributes a{};
+      const hipError_t e = k ? hipFuncGetAttributes(&a, k) : hipErrorInvalidDeviceFunction;
+      most = std::max(most, a.numRegs);
+      return e;
+    };
+    if (p->kind) {
+      for (const bool emit : {false, true}) {
+        HIP_TRY(c, regs(wave_kernel_nodes((int)p->kind, emit), rw));
+        HIP_TRY(c, regs(group_kernel_nodes((int)p->kind, p->group, emit), rg));
+      }
+    } else {
+      const void* wk = pm == 2 ? (const void*)repair_wave_kernel<2>
+                               : pm == 1 ? (const void*)repair_wave_kernel<1> : (const void*)repair_wave_kernel<0>;
+      HIP_TRY(c, regs(wk, rw));
+      HIP_TRY(c, regs(group_kernel(p->group, pm), rg));
+    }
     const auto gran = [](int r) { return (uint32_t)((std::max(r, 1) + 7) & ~7); };
     const uint32_t per_simd_group = kGroupWg / 64 / 4;
-    const uint32_t vw = gran(fw.numRegs), vg = gran(fg.numRegs);
+    const uint32_t vw = gran(rw), vg = gran(rg);
     uint32_t per_simd_wave = (p->wave_teams + 4 * c->n_cu - 1) / (4 * c->n_cu);
     while (per_simd_wave > 1 && per_simd_wave * vw + per_simd_group * vg > 512) --per_simd_wave;
     p->wave_teams = std::min(p->wave_teams, per_simd_wave * 4 * c->n_cu);
     if (std::getenv("SPF_WHATIF_DEBUG"))
-      std::fprintf(stderr, "whatif: wave kernel %d VGPRs, group<%u> %d VGPRs: %u wave teams (%u per SIMD)\n",
-                   fw.numRegs, p->group, fg.numRegs, p->wave_teams, per_simd_wave);
+      std::fprintf(stderr, "whatif%s: wave kernel %d VGPRs, group<%u> %d VGPRs: %u wave teams (%u per SIMD)\n",
+                   p->kind == (uint32_t)kDown ? " (node down)" : p->kind == (uint32_t)kDrain ? " (node drain)" : "",
+                   rw, p->group, rg, p->wave_teams, per_simd_wave);
   }
   const size_t wt = p->wave_teams;
   while ((1u << p->tab_log2) < 4 * p->wave_cap) ++p->tab_log2;
@@ -2610,7 +2802,7 @@ spf_status spf_whatif_plan_create(spf_ctx* c, uint32_t src, const uint32_t* fail
   // marks start (and are always left) at kInf
   HIP_TRY(c, hipMemsetAsync(p->w_tab.p, 0xFF, (wt << p->tab_log2) * 8, c->stream));
   HIP_TRY(c, hipMemsetAsync(p->b_mark.p, 0xFF, bt * N * 4, c->stream));
-  p->prof_mode = whatif_prof_mode();
+  p->prof_mode = p->kind ? 0 : whatif_prof_mode();  // node plans have no profiled instances
   if (p->prof_mode) {  // [bt teams][base][wave teams] x 16 (row bounds checked in the kernels)
     const size_t slots = 16 * (bt + 1 + p->wave_teams) + 128;  // + the base's per-level clocks
     HIP_TRY(c, p->d_prof.alloc(slots));
@@ -2622,13 +2814,107 @@ spf_status spf_whatif_plan_create(spf_ctx* c, uint32_t src, const uint32_t* fail
   return SPF_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+spf_status spf_whatif_plan_create(spf_ctx* c, uint32_t src, const uint32_t* fail_links,
+                                  uint32_t n_fail, spf_whatif_plan** out) {
+  if (!c || !out) return fail(c, SPF_E_INVALID, "spf_whatif_plan_create: NULL argument");
+  *out = nullptr;
+  if (!c->loaded) return fail(c, SPF_E_STATE, "no graph loaded");
+  if (src >= c->N) return fail(c, SPF_E_INVALID, "source %u out of range", src);
+  auto p = std::make_unique<spf_whatif_plan>();
+  p->ctx = c;
+  p->src = src;
+  const uint32_t N = c->N, E = c->E;
+  // link -> one of its directed edges (up links only: a dead slot is a self-loop)
+  std::vector<uint32_t> link_edge((size_t)c->max_link + 1, kInf);
+  for (uint32_t u = 0; u < N; ++u)
+    for (uint32_t e = c->row_ptr[u]; e < c->row_ptr[u + 1]; ++e)
+      if (c->col[e] != u && link_edge[c->link[e]] == kInf) link_edge[c->link[e]] = e;
+  std::vector<uint32_t> fails;
+  if (fail_links) {
+    fails.assign(fail_links, fail_links + n_fail);
+    for (uint32_t l : fails)
+      if (l > c->max_link || link_edge[l] == kInf)
+        return fail(c, SPF_E_INVALID, "link %u is not an up link of the graph", l);
+  } else {  // every up link, ascending id
+    for (uint32_t l = 0; l <= c->max_link && E; ++l)
+      if (link_edge[l] != kInf) fails.push_back(l);
+  }
+  p->n_fail = (uint32_t)fails.size();
+  if (c->nonpos || c->needs64) {
+    // zero / negative metrics, u64 labels: the exact kernel replays
+    // runSpf(src, true, {l}) for every failure touching a pathLink
+    HIP_TRY(c, hipSetDevice(c->device));
+    p->exact = std::make_unique<spfi::ExactWhatIf>();
+    const spf_status st = exact_whatif_prepare(c, p->exact.get(), src, fails, link_edge);
+    if (st != SPF_OK) return st;
+    if (!fails.empty()) HIP_TRY(c, p->d_fails.upload(fails.data(), fails.size(), c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    p->W = p->exact->W;
+    p->epoch = c->epoch;
+    *out = p.release();
+    return SPF_OK;
+  }
+  return plan_build(c, p, fails, &link_edge, out);
+}
+
 void spf_whatif_plan_destroy(spf_whatif_plan* p) { delete p; }
 uint32_t spf_whatif_plan_failures(const spf_whatif_plan* p) { return p ? p->n_fail : 0; }
 
 spf_status spf_whatif_plan_links(const spf_whatif_plan* p, uint32_t* links) {
   if (!p || !links) return SPF_E_INVALID;
   spf_ctx* c = p->ctx;
+  if (p->kind) return fail(c, SPF_E_STATE, "spf_whatif_plan_links: a node plan (spf_whatif_plan_nodes)");
   HIP_TRY(c, hipMemcpy(links, p->d_fails.p, 4ull * p->n_fail, hipMemcpyDeviceToHost));
+  return SPF_OK;
+}
+
+spf_status spf_whatif_plan_create_nodes(spf_ctx* c, uint32_t src, uint32_t kind,
+                                        const uint32_t* fail_nodes, uint32_t n_fail,
+                                        spf_whatif_plan** out) {
+  if (!c || !out) return fail(c, SPF_E_INVALID, "spf_whatif_plan_create_nodes: NULL argument");
+  *out = nullptr;
+  if (!c->loaded) return fail(c, SPF_E_STATE, "no graph loaded");
+  if (src >= c->N) return fail(c, SPF_E_INVALID, "source %u out of range", src);
+  if (kind != SPF_WHATIF_NODE_DOWN && kind != SPF_WHATIF_NODE_DRAIN)
+    return fail(c, SPF_E_INVALID, "spf_whatif_plan_create_nodes: unknown kind %u", kind);
+  std::vector<uint32_t> fails;
+  if (fail_nodes) {
+    fails.assign(fail_nodes, fail_nodes + n_fail);
+    for (uint32_t x : fails) {
+      if (x >= c->N) return fail(c, SPF_E_INVALID, "node %u out of range", x);
+      if (x == src) return fail(c, SPF_E_INVALID, "node %u is the source: not a failure of this call", x);
+    }
+  } else {  // every node except the source, ascending id
+    for (uint32_t x = 0; x < c->N; ++x)
+      if (x != src) fails.push_back(x);
+  }
+  if (c->nonpos || c->needs64)
+    return fail(c, SPF_E_UNSUPPORTED,
+                "spf_whatif_plan_create_nodes: node failures are not supported on graphs that take the "
+                "exact path (a metric <= 0 or u64 labels)");
+  auto p = std::make_unique<spf_whatif_plan>();
+  p->ctx = c;
+  p->src = src;
+  p->kind = kind;
+  p->n_fail = (uint32_t)fails.size();
+  return plan_build(c, p, fails, nullptr, out);
+}
+
+spf_status spf_whatif_plan_nodes(const spf_whatif_plan* p, uint32_t* nodes) {
+  if (!p || !nodes) return SPF_E_INVALID;
+  spf_ctx* c = p->ctx;
+  if (!p->kind) return fail(c, SPF_E_STATE, "spf_whatif_plan_nodes: a link plan (spf_whatif_plan_links)");
+  HIP_TRY(c, hipMemcpy(nodes, p->d_fails.p, 4ull * p->n_fail, hipMemcpyDeviceToHost));
+  return SPF_OK;
+}
+
+spf_status spf_whatif_plan_kind(const spf_whatif_plan* p, uint32_t* kind) {
+  if (!p || !kind) return SPF_E_INVALID;
+  *kind = p->kind;
   return SPF_OK;
 }
 

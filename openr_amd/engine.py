@@ -363,22 +363,39 @@ DIGEST_DTYPE =np.dtype([("n_dist_changed", "<u4"), ("n_nh_changed", "<u4"),
                          ("hash", "<u8")])  # spf_whatif_digest
 
 
+WHATIF_KINDS = {"link": 0, "down": N.SPF_WHATIF_NODE_DOWN, "drain": N.SPF_WHATIF_NODE_DRAIN}
+
+
 class WhatIfPlan(NativeHandle):
-    """One source, a list of single-link failures (``spf_whatif_plan``)."""
+    """One source and a list of failures (``spf_whatif_plan``): single links
+    (``kind == "link"``, ``links``), or nodes down / drained (``"down"`` /
+    ``"drain"``, ``nodes``; ``links`` is then empty, as ``nodes`` is for a
+    link plan)."""
 
     _destroy = "spf_whatif_plan_destroy"
 
-    def __init__(self, eng: "SpfEngine", src: int, links: Optional[Sequence[int]]) -> None:
+    def __init__(self, eng: "SpfEngine", src: int, links: Optional[Sequence[int]],
+                 kind: str = "link") -> None:
+        if kind not in WHATIF_KINDS:
+            raise ValueError(f"what-if kind {kind!r}: one of {sorted(WHATIF_KINDS)}")
         self._eng = eng
+        self.kind = kind
         h = C.c_void_p()
         arr = None if links is None else np.ascontiguousarray(links, np.uint32)
-        eng._err(N.lib.spf_whatif_plan_create(eng._h, src, None if arr is None else N.ptr(arr),
-                                              0 if arr is None else len(arr), C.byref(h)))
+        a, n = (None if arr is None else N.ptr(arr)), (0 if arr is None else len(arr))
+        if kind == "link":
+            eng._err(N.lib.spf_whatif_plan_create(eng._h, src, a, n, C.byref(h)))
+        else:
+            eng._err(N.lib.spf_whatif_plan_create_nodes(eng._h, src, WHATIF_KINDS[kind], a, n,
+                                                        C.byref(h)))
         self._adopt(h)
         self.n_fail = int(N.lib.spf_whatif_plan_failures(h))
-        self.links = np.zeros(max(1, self.n_fail), np.uint32)
-        eng._err(N.lib.spf_whatif_plan_links(h, N.ptr(self.links)))
-        self.links = self.links[: self.n_fail]
+        ids = np.zeros(max(1, self.n_fail), np.uint32)
+        read = N.lib.spf_whatif_plan_links if kind == "link" else N.lib.spf_whatif_plan_nodes
+        eng._err(read(h, N.ptr(ids)))
+        none = np.zeros(0, np.uint32)
+        self.links = ids[: self.n_fail] if kind == "link" else none
+        self.nodes = none if kind == "link" else ids[: self.n_fail]
 
     def execute(self, d_out: int, d_base: int = 0, stream: int = 0) -> None:
         self._eng._err(N.lib.spf_whatif_execute(self._h, C.c_void_p(d_out),
@@ -721,6 +738,46 @@ class SpfEngine(NativeHandle):
         failed link l (every up link when `links` is None).  close() the
         result (it owns its plan)."""
         plan = self.whatif_plan(src, links)
+        try:
+            return WhatIfChanges(plan, own_plan=True)
+        except BaseException:
+            plan.close()
+            raise
+
+    def whatif_node_plan(self, src: int, nodes: Optional[Sequence[int]] = None,
+                         kind: str = "down") -> WhatIfPlan:
+        """A what-if plan whose failures are nodes: ``kind="down"`` (every
+        link of the node ignored) or ``"drain"`` (the node overloaded); every
+        node except `src` when `nodes` is None."""
+        if kind not in ("down", "drain"):
+            raise ValueError(f"node what-if kind {kind!r}: 'down' or 'drain'")
+        return self._track(WhatIfPlan(self, src, nodes, kind))
+
+    def whatif_nodes(self, src: int, nodes: Optional[Sequence[int]] = None, kind: str = "down"):
+        """Digests of the SPF of `src` with each node of the list down or
+        drained: (nodes, digests[n], base digest)."""
+        from .hiprt import DeviceArray, set_device
+
+        plan = self.whatif_node_plan(src, nodes, kind)
+        try:
+            set_device(self.device)
+            d_out = DeviceArray(max(1, plan.n_fail), DIGEST_DTYPE)
+            d_base = DeviceArray(1, DIGEST_DTYPE)
+            try:
+                plan.execute(d_out.ptr, d_base.ptr)
+                plan.stats()  # waits for the execute, checks the device's fault word
+                return plan.nodes, d_out.numpy()[: plan.n_fail], d_base.numpy()[0]
+            finally:
+                d_out.free()
+                d_base.free()
+        finally:
+            plan.close()
+
+    def whatif_node_changes(self, src: int, nodes: Optional[Sequence[int]] = None,
+                            kind: str = "down") -> WhatIfChanges:
+        """What each node failure changes (``whatif_changes`` for nodes down
+        or drained).  close() the result (it owns its plan)."""
+        plan = self.whatif_node_plan(src, nodes, kind)
         try:
             return WhatIfChanges(plan, own_plan=True)
         except BaseException:
