@@ -543,7 +543,49 @@ spf_status spf_whatif_plan_create_nodes(spf_ctx* ctx, uint32_t src, uint32_t kin
 /* The plan's nodes; SPF_E_STATE on a link plan (as spf_whatif_plan_links is on
  * a node plan). */
 spf_status spf_whatif_plan_nodes(const spf_whatif_plan* plan, uint32_t* nodes /* [n_fail] */);
-/* 0 = link plan, else SPF_WHATIF_NODE_* */
+/* ---- what-if batches for link-set failures (shared-risk link groups: a fibre
+ * bundle, a line card, both links of a LAG, a conduit).
+ * "Failure i" of the plan is a set of links, all ignored at once:
+ *   runSpf(src, true, {set_links[set_ptr[i] .. set_ptr[i + 1])})
+ * against the unfailed runSpf(src) -- the reference's own primitive with more
+ * than one link in linksToIgnore (LinkState.cpp:808-882).  The result is an
+ * ordinary spf_whatif_plan: spf_whatif_execute, _changes, _changes_db / _read /
+ * _buffers / _timing, _base, _stats, _enable_timing, _timing, _plan_failures
+ * and _plan_destroy work on it unchanged, and spf_whatif_plan_kind returns
+ * SPF_WHATIF_LINK_SET.  The digest and the list entry are the link plans': the
+ * next-hop bitset is over the distinct up neighbours of src in the UNFAILED
+ * graph.
+ *   A set is a set: the plan sorts each one and drops duplicates
+ *     (spf_whatif_plan_sets returns them so).  The order of the sets is kept,
+ *     and the same set may appear twice.
+ *   The empty set is allowed and cold: digest {0, 0, hash}, no entries.
+ *   A member that is down, or not tight in the unfailed shortest-path DAG, has
+ *     no effect; a set none of whose members is tight is cold.
+ *   Links of src are allowed, all of them included: every other node then
+ *     becomes unreachable.  Unlike node plans, nothing about src is refused.
+ *   A single link is a set of one (digests and lists equal the link plan's);
+ *     linksFromNode(x) as a set equals SPF_WHATIF_NODE_DOWN of x.
+ * The repairs take the heads of the set's tight members as the roots of the
+ * affected set D (D = the roots and their DAG descendants; two members with
+ * one head give one root), and test "is this edge failed" by membership of
+ * its link id in the sorted set: compares against registers up to 4 members,
+ * a binary search of the set in memory beyond.
+ * SPF_E_INVALID: set_ptr[0] != 0, set_ptr not non-decreasing, a link id that is
+ * not a link id of the graph (> the largest link id loaded), NULL arrays with
+ * n_sets > 0 (set_links may be NULL when every set is empty).
+ * SPF_E_UNSUPPORTED: graphs that take the exact path (a metric <= 0 or u64
+ * labels), as for node plans.  SPF_WHATIF_PROF is ignored by set plans. */
+#define SPF_WHATIF_LINK_SET 3u   /* failure i = a set of links, all ignored */
+spf_status spf_whatif_plan_create_sets(spf_ctx* ctx, uint32_t src,
+                                       const uint32_t* set_ptr /* [n_sets + 1] */,
+                                       const uint32_t* set_links /* [set_ptr[n_sets]] */,
+                                       uint32_t n_sets, spf_whatif_plan** out);
+/* The plan's sets as it holds them: each ascending, duplicates removed.
+ * set_ptr [n_fail + 1]; set_links [set_ptr[n_fail]], NULL to read set_ptr
+ * alone.  SPF_E_STATE on a link or node plan (as spf_whatif_plan_links and
+ * _plan_nodes are on a set plan). */
+spf_status spf_whatif_plan_sets(const spf_whatif_plan* plan, uint32_t* set_ptr, uint32_t* set_links);
+/* 0 = link plan, SPF_WHATIF_NODE_* or SPF_WHATIF_LINK_SET */
 spf_status spf_whatif_plan_kind(const spf_whatif_plan* plan, uint32_t* kind);
 /* d_out = [n_fail] digests, d_base = 1 digest (may be NULL).  Enqueued on
  * `stream` (a grid-resident launch for the unfailed solve); no host

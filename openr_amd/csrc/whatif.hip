@@ -40,6 +40,16 @@
 //      it is nobody's predecessor.  Cold when x is unreachable, drained
 //      already, or has no tight out-edge.
 //
+//  Link sets (spf_whatif_plan_create_sets, shared-risk groups) are the fourth
+//  kind: failure i = runSpf(src, true, S_i) for a set S_i of links.  An edge is
+//  failed when its link id is a member of S_i, and D = the DAG descendants of
+//  several roots, the heads of every tight member (two members with one head
+//  claim it once; a root below another root is found marked by the level
+//  loop).  The argument above carries over: a node outside D has no tight path
+//  through any failed link.  Cold when no member is tight (an empty set, down
+//  or non-tight members only).  A single link is a set of one, DOWN x the set
+//  linksFromNode(x).
+//
 //  Digest of a result (same definition in oracle/spf_oracle.cpp):
 //    n_dist_changed, n_nh_changed (a node becoming unreachable counts in both)
 //    hash = sum over reachable v of mix(mix(v + 1) + d(v)) ^ fnv(nh(v) words)
@@ -66,8 +76,9 @@ constexpr uint32_t kDialLevels = 1024;         // distinct distances settled buc
 
 // What a plan's failures are, a template parameter of the repairs: one link,
 // or a node down / drained (SPF_WHATIF_NODE_DOWN / SPF_WHATIF_NODE_DRAIN).
-constexpr int kLink = 0, kDown = 1, kDrain = 2;
-static_assert(kDown == SPF_WHATIF_NODE_DOWN && kDrain == SPF_WHATIF_NODE_DRAIN, "plan kinds");
+constexpr int kLink = 0, kDown = 1, kDrain = 2, kSet = 3;
+static_assert(kDown == SPF_WHATIF_NODE_DOWN && kDrain == SPF_WHATIF_NODE_DRAIN &&
+                  kSet == SPF_WHATIF_LINK_SET, "plan kinds");
 
 // Is the edge v -> u (link id `link`) unusable, in both directions, under
 // the failure: link l itself, or (node x down) any edge with an end at x.
@@ -84,6 +95,62 @@ template <int KIND>
 __device__ __forceinline__ bool drain_x(uint32_t x, uint32_t v) {
   if constexpr (KIND == kDrain) return v == x;
   else return false;
+}
+
+
+// A set plan's canonical sets on the device (each ascending, no duplicates):
+// failure f owns links[ptr[f] .. ptr[f + 1]); link_edge[l] = one directed edge
+// of link l, kInf when l is down.  The set kernels' trailing argument.
+struct WiSets {
+  const uint32_t* ptr;
+  const uint32_t* links;
+  const uint32_t* link_edge;
+};
+// The failed set of one repair (KIND == kSet; empty, and so no argument at
+// all, for the other kinds): the sorted run in global memory, its length and
+// -- team-uniform, in scalar registers -- its first four members, padded with
+// kInf (no link id).  Shared-risk groups are mostly two to four links (both
+// links of a LAG, a bundle): those never touch memory for the membership test.
+constexpr uint32_t kSetRegs = 4;
+template <int KIND>
+struct SetRef {};
+template <>
+struct SetRef<kSet> {
+  const uint32_t* mem;
+  const uint32_t* link_edge;
+  uint32_t n, m0, m1, m2, m3;
+};
+__device__ __forceinline__ SetRef<kSet> set_of(const WiSets& s, uint32_t f) {
+  const uint32_t b0 = __builtin_amdgcn_readfirstlane(s.ptr[f]);
+  const uint32_t n = __builtin_amdgcn_readfirstlane(s.ptr[f + 1]) - b0;
+  const uint32_t* mem = s.links + b0;
+  SetRef<kSet> r{mem, s.link_edge, n, kInf, kInf, kInf, kInf};
+  if (n > 0) r.m0 = __builtin_amdgcn_readfirstlane(mem[0]);
+  if (n > 1) r.m1 = __builtin_amdgcn_readfirstlane(mem[1]);
+  if (n > 2) r.m2 = __builtin_amdgcn_readfirstlane(mem[2]);
+  if (n > 3) r.m3 = __builtin_amdgcn_readfirstlane(mem[3]);
+  return r;
+}
+// Is `link` a member: up to kSetRegs members by compares against registers,
+// longer sets by a binary search of the sorted run (ceil(log2 n) + 1 loads,
+// all within the run's few cache lines; a linear scan of a 167-link hub set
+// would be 167 per edge).
+__device__ __forceinline__ bool set_has(const SetRef<kSet>& r, uint32_t link) {
+  if (r.n <= kSetRegs) return link == r.m0 || link == r.m1 || link == r.m2 || link == r.m3;
+  uint32_t lo = 0, hi = r.n;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (r.mem[mid] < link) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < r.n && r.mem[lo] == link;
+}
+// failed() of every kind: a set plan asks the set, the others as above
+template <int KIND>
+__device__ __forceinline__ bool failed(const SetRef<KIND>& sr, uint32_t x, uint32_t l, bool v_is_x,
+                                       uint32_t u, uint32_t link) {
+  if constexpr (KIND == kSet) return set_has(sr, link);
+  else return failed<KIND>(x, l, v_is_x, u, link);
 }
 
 __device__ __forceinline__ uint32_t ld(const uint32_t* p) {
@@ -991,6 +1058,34 @@ __device__ __forceinline__ void stq(unsigned long long* p, unsigned long long v)
 // keep their argument list).
 __device__ __forceinline__ const WiEmit* emit_arg() { return nullptr; }
 __device__ __forceinline__ const WiEmit* emit_arg(const WiEmit& e) { return &e; }
+// (set plans: the pack ends with the WiSets)
+__device__ __forceinline__ const WiEmit* emit_arg(const WiSets&) { return nullptr; }
+__device__ __forceinline__ const WiEmit* emit_arg(const WiEmit& e, const WiSets&) { return &e; }
+__device__ __forceinline__ const WiSets& sets_arg(const WiSets& s) { return s; }
+__device__ __forceinline__ const WiSets& sets_arg(const WiEmit&, const WiSets& s) { return s; }
+// failure f's set (set plans), nothing for the other kinds
+template <int KIND, class... EM>
+__device__ __forceinline__ SetRef<KIND> set_arg(uint32_t f, const EM&... em) {
+  if constexpr (KIND == kSet) return set_of(sets_arg(em...), f);
+  else return SetRef<KIND>{};
+}
+
+// The head of link edge e0's tight direction in the unfailed DAG, kInf when
+// neither is tight (or e0 = kInf, a down link): classify_kernel's test --
+// tail reachable, tail not drained unless it is src, dist[a] + w == dist[b].
+// Metrics are positive, so at most one direction is tight.
+__device__ __forceinline__ uint32_t tight_head(const WiGraph& g, const uint32_t* dist, uint32_t e0) {
+  uint32_t head = kInf;
+  if (e0 != kInf) {
+    for (uint32_t k = 0; k < 2; ++k) {
+      const uint32_t e = k ? g.rev[e0] : e0;
+      const uint32_t a = g.col[g.rev[e]], b = g.col[e];  // a -> b
+      if (g.ovl[a] && a != g.src) continue;
+      if (dist[a] != kInf && dist[a] + g.wt[e] == dist[b]) head = b;
+    }
+  }
+  return head;
+}
 
 // Is D node i (graph node v, new distance d1) an entry of its failure's list:
 // its metric or its next-hop row differs from the unfailed result.  (A node
@@ -1171,13 +1266,15 @@ __device__ __forceinline__ void ph_max(uint64_t* ph, int k, uint64_t v, bool lea
 // (results then invalid, reported by spf_device_check).
 // EMIT (spf_whatif_changes): the repair also counts (em->cnode NULL) or
 // writes (fill pass) failure f's change list, before the digest loop.
-// KIND: `y` is the failed link's tight edge (kLink) or the failed node.
+// KIND: `y` is the failed link's tight edge (kLink) or the failed node; a set
+// plan's failure is `sr` (y is its size estimate, not used here).
 template <int TEAM, bool GROUP = false, bool CHK = false, bool GPH = false, bool EMIT = false,
           int KIND = kLink>
 __device__ bool repair(const WiGraph& g, const WiBase& B, uint32_t* mark, uint32_t* dlist,
                        uint32_t* dnew, uint32_t* nhn, uint32_t* lvl, uint32_t* ord, uint32_t cap,
                        TeamCtl* ctl, uint32_t tt, uint32_t y, spf_whatif_digest* out,
-                       uint64_t* ph = nullptr, const WiEmit* em = nullptr, uint32_t f = 0) {
+                       uint64_t* ph = nullptr, const WiEmit* em = nullptr, uint32_t f = 0,
+                       SetRef<KIND> sr = SetRef<KIND>{}) {
   // diagnostics (SPF_WHATIF_PROF): 12 counters, accumulated over the team's
   // failures (ph_add) -- [0] repairs, [1..5] 100 MHz ticks in D discovery,
   // seeds, Dial, fallback sweeps, digest; [8] sum |D|, [9] sum Dial levels,
@@ -1209,17 +1306,48 @@ __device__ bool repair(const WiGraph& g, const WiBase& B, uint32_t* mark, uint32
   const uint32_t l = KIND == kLink ? g.link[y] : 0u;
   const uint32_t b = KIND == kLink ? g.col[y] : y;
   if (tt == 0) {
-    stw<GROUP>(&ctl->n, 1u);
+    stw<GROUP>(&ctl->n, KIND == kSet ? 0u : 1u);
     stw<GROUP>(&ctl->ovf, 0u);
     stw<GROUP>(&ctl->hub, 0u);
     for (int q = 0; q < 3; ++q) stw<GROUP>(&ctl->flag[q], 0u);
     stq<GROUP>(&ctl->ndist, 0ull);
     stq<GROUP>(&ctl->nnh, 0ull);
     stq<GROUP>(&ctl->dh, 0ull);
-    dlist[0] = b;
-    stw<GROUP>(&mark[b], 0);
+    if constexpr (KIND != kSet) {
+      dlist[0] = b;
+      stw<GROUP>(&mark[b], 0);
+    }
   }
   team_sync<TEAM, GROUP>(ctl, g.fault);
+  if constexpr (KIND == kSet) {
+    // D's roots: the heads of the set's tight members.  The team's lanes walk
+    // the members, 64 per wave at a time; a head is claimed once (the mark
+    // CAS: two members may share it) and the claimed heads of a chunk take
+    // the next D indices by ballot compaction, one counter atomic per wave --
+    // the level loop's append.  A root below another root is met marked there.
+    for (uint32_t c0 = wv * 64; c0 < sr.n; c0 += TEAM) {  // wave-uniform
+      const uint32_t i = c0 + lane;
+      const uint32_t c = i < sr.n ? tight_head(g, B.dist, sr.link_edge[sr.mem[i]]) : kInf;
+      const bool won = c != kInf && atomicCAS(&mark[c], kInf, kBusy) == kInf;
+      const uint64_t wm = __ballot(won);
+      if (wm) {
+        uint32_t base = 0;
+        if (lane == 0) base = atomicAdd(&ctl->n, (uint32_t)__popcll(wm));
+        base = __builtin_amdgcn_readlane(base, 0);
+        if (won) {
+          const uint32_t idx = base + lanes_below(wm);
+          if (idx < cap) {
+            dlist[idx] = c;
+            stw<GROUP>(&mark[c], idx);
+          } else {
+            stw<GROUP>(&mark[c], kInf);
+            stw<GROUP>(&ctl->ovf, 1u);
+          }
+        }
+      }
+    }
+    team_sync<TEAM, GROUP>(ctl, g.fault);
+  }
   // ---- D = descendants of b in the unfailed DAG (level by level) ----
   // Control words (ctl->n / ovf / hub / flag / nxt / lc) are written by
   // atomics and plain stores of other lanes, waves or CUs: every read of one
@@ -1309,7 +1437,7 @@ __device__ bool repair(const WiGraph& g, const WiBase& B, uint32_t* mark, uint32
       uint32_t s = kInf;
       const uint4 q = act ? g.ed[e] : make_uint4(0u, 0u, l, 0u);
       // (the row owner is x exactly at D index 0)
-      if (act && !failed<KIND>(x, l, c0 + k == 0, q.x, q.z)) {
+      if (act && !failed<KIND>(sr, x, l, c0 + k == 0, q.x, q.z)) {
         const uint32_t u = q.x;
         if (ldw<GROUP>(&mark[u]) == kInf && !(g.ovl[u] && u != g.src)) {
           const uint32_t du = B.dist[u];
@@ -1332,7 +1460,7 @@ __device__ bool repair(const WiGraph& g, const WiBase& B, uint32_t* mark, uint32
     const uint32_t dv = ldw<GROUP>(&dnew[i]);
     uint32_t acc = 0;
     for (uint32_t e = g.row_ptr[v]; e < g.row_ptr[v + 1]; ++e) {
-      if (failed<KIND>(x, l, false, g.col[e], g.link[e])) continue;  // (dnew[x] is kInf: v != x)
+      if (failed<KIND>(sr, x, l, false, g.col[e], g.link[e])) continue;  // (dnew[x] is kInf: v != x)
       const uint32_t u = g.col[e];
       if ((g.ovl[u] && u != g.src) || drain_x<KIND>(x, u)) continue;
       const uint32_t mu = chk(ldw<GROUP>(&mark[u]), n, true, 5, kInf);
@@ -1429,7 +1557,7 @@ __device__ bool repair(const WiGraph& g, const WiBase& B, uint32_t* mark, uint32
         bool tight = false, from_src = false;
         const uint4 q = act ? g.ed[e] : make_uint4(0u, 0u, l, 0u);
         // (a level's nodes hold a distance: none is a downed x)
-        if (act && !failed<KIND>(x, l, false, q.x, q.z)) {
+        if (act && !failed<KIND>(sr, x, l, false, q.x, q.z)) {
           u = q.x;
           mu = chk(ldw<GROUP>(&mark[u]), n, true, 13, kInf);
           if (!(g.ovl[u] && u != g.src) && !drain_x<KIND>(x, u)) {
@@ -1468,7 +1596,7 @@ __device__ bool repair(const WiGraph& g, const WiBase& B, uint32_t* mark, uint32
         const uint32_t dv = ldw<GROUP>(&dnew[i]);
         if (dv == kInf || g.ovl[v] || drain_x<KIND>(x, v)) continue;
         for (uint32_t e = g.row_ptr[v]; e < g.row_ptr[v + 1]; ++e) {
-          if (failed<KIND>(x, l, false, g.col[e], g.link[e])) continue;
+          if (failed<KIND>(sr, x, l, false, g.col[e], g.link[e])) continue;
           const uint32_t ic = chk(ldw<GROUP>(&mark[g.col[e]]), n, true, 14, kInf);
           if (ic == kInf) continue;
           const uint32_t nd = dv + g.wt[e];
@@ -1693,7 +1821,8 @@ template <bool CHK, bool GPH = false, bool EMIT = false, int KIND = kLink>
 __device__ bool repair_wave(const WiGraph& g, const WiBase& B, const WaveSet& hs, uint32_t* dlist,
                             uint32_t* dnew, uint32_t* nhn, uint32_t* ord, uint32_t cap,
                             TeamCtl* ctl, uint32_t lane, uint32_t y, spf_whatif_digest* out,
-                            uint64_t* ph, const WiEmit* em = nullptr, uint32_t f = 0) {
+                            uint64_t* ph, const WiEmit* em = nullptr, uint32_t f = 0,
+                            SetRef<KIND> sr = SetRef<KIND>{}) {
   uint64_t tprev = ph ? wall_clock64() : 0ull;
 #define WI_STAMP(k)                                \
   do {                                             \
@@ -1719,18 +1848,47 @@ __device__ bool repair_wave(const WiGraph& g, const WiBase& B, const WaveSet& hs
   const uint32_t l = KIND == kLink ? g.link[y] : 0u;
   const uint32_t b = KIND == kLink ? g.col[y] : y;
   if (lane == 0) {
-    dlist[0] = b;
-    bool full = false;
-    const uint32_t s0 = ws_claim(hs, b, full);  // (the table is empty)
-    ws_st(&hs.tab[s0], b);                      // value 0: D index 0
+    if constexpr (KIND != kSet) {
+      dlist[0] = b;
+      bool full = false;
+      const uint32_t s0 = ws_claim(hs, b, full);  // (the table is empty)
+      ws_st(&hs.tab[s0], b);                      // value 0: D index 0
+    }
     stq<false>(&ctl->ndist, 0ull);
     stq<false>(&ctl->nnh, 0ull);
     stq<false>(&ctl->dh, 0ull);
   }
   sync();
   // ---- D = descendants of b in the unfailed DAG, frontier by frontier ----
-  uint32_t n = 1, lo = 0;
+  uint32_t n = KIND == kSet ? 0u : 1u, lo = 0;
   bool bad = false;
+  if constexpr (KIND == kSet) {
+    // D's roots: the heads of the set's tight members, the lanes over the
+    // members 64 at a time; a head is claimed once (ws_claim: two members may
+    // share it), the claimed heads of a chunk take D indices n, n + 1, ... by
+    // ballot compaction -- the frontier loop's append.  More roots than cap,
+    // or a full table, is the overflow below.
+    bool full = false;
+    for (uint32_t c0 = 0; c0 < sr.n && n <= cap; c0 += 64) {
+      const uint32_t i = c0 + lane;
+      const uint32_t c = i < sr.n ? tight_head(g, B.dist, sr.link_edge[sr.mem[i]]) : kInf;
+      uint32_t slot = ~0u;
+      if (c != kInf) slot = ws_claim(hs, c, full);
+      const bool won = slot != ~0u;
+      const uint64_t wm = __ballot(won);
+      if (won) {
+        const uint32_t idx = n + lanes_below(wm);
+        ws_st(&hs.tab[slot], ((unsigned long long)(idx < cap ? idx : kInf) << 32) | c);
+        if (idx < cap) dlist[idx] = c;
+      }
+      n += (uint32_t)__popcll(wm);
+    }
+    if (__ballot(full)) {
+      bad = true;
+      lo = n;  // (no frontier pass)
+    }
+    sync();
+  }
   for (uint32_t iter = 0; lo < n && n <= cap; ++iter) {
     if (iter > cap + 2) {  // wave-uniform
       bad = true;
@@ -1794,7 +1952,7 @@ __device__ bool repair_wave(const WiGraph& g, const WiBase& B, const WaveSet& hs
     wave_edges(g.row_ptr, v, i < n, [&](uint32_t k, uint32_t e, bool act) {
       uint32_t s = kInf;
       const uint4 q = act ? g.ed[e] : make_uint4(0u, 0u, l, 0u);
-      if (act && !failed<KIND>(x, l, c0 + k == 0, q.x, q.z)) {
+      if (act && !failed<KIND>(sr, x, l, c0 + k == 0, q.x, q.z)) {
         const uint32_t u = q.x;
         if (ws_find(hs, u) == kInf && !(g.ovl[u] && u != g.src)) {
           const uint32_t du = B.dist[u];
@@ -1867,7 +2025,7 @@ __device__ bool repair_wave(const WiGraph& g, const WiBase& B, const WaveSet& hs
         uint32_t u = 0, mu = kInf;
         bool tight = false, from_src = false;
         const uint4 q = act ? g.ed[e] : make_uint4(0u, 0u, l, 0u);
-        if (act && !failed<KIND>(x, l, false, q.x, q.z)) {
+        if (act && !failed<KIND>(sr, x, l, false, q.x, q.z)) {
           u = q.x;
           mu = chk(ws_find(hs, u), n, true, 13, kInf);
           if (!(g.ovl[u] && u != g.src) && !drain_x<KIND>(x, u)) {
@@ -1970,14 +2128,17 @@ __device__ __forceinline__ uint64_t* prof_row(unsigned long long* prof, size_t t
 // with diagnostics.  EMIT (spf_whatif_changes; PROF 0 only): likewise separate
 // instances of the three repair kernels, with one more argument, the WiEmit,
 // as a trailing pack -- the production instances keep their argument list and
-// compile to what they did without it.
+// compile to what they did without it.  A set plan's instances (KIND kSet)
+// end the pack with the WiSets; the work item's failure index h.x selects the
+// set (set_arg).
 template <int PROF, bool EMIT = false, int KIND = kLink, class... EM>
 __global__ __launch_bounds__(256) void repair_wave_kernel(
     WiGraph g, WiBase B, const uint2* __restrict__ hot, const uint32_t* __restrict__ n_hot,
     uint32_t* cursor, uint2* big, uint32_t* n_big, unsigned long long* tab, uint32_t* dlist,
     uint32_t* dnew, uint32_t* nhn, uint32_t* lvl, uint32_t* ord, spf_whatif_digest* out, uint32_t cap,
     uint32_t tab_log2, unsigned long long* prof, uint32_t prof_rows, EM... em) {
-  static_assert(sizeof...(EM) == (EMIT ? 1 : 0) && (!EMIT || PROF == 0), "EMIT: one WiEmit, PROF 0");
+  static_assert(sizeof...(EM) == (EMIT ? 1 : 0) + (KIND == kSet ? 1 : 0) && (!EMIT || PROF == 0),
+                "EMIT: a WiEmit, PROF 0; set plans: a WiSets last");
   __shared__ TeamCtl ctl[4];
   const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const size_t team = (size_t)blockIdx.x * 4 + w;
@@ -1998,7 +2159,7 @@ __global__ __launch_bounds__(256) void repair_wave_kernel(
     const uint2 h = hot[k];
     if (!repair_wave<PROF != 0, PROF == 2, EMIT, KIND>(g, B, hs, dlist, dnew, nhn, ord, cap, &ctl[w],
                                                       lane, h.y, out + h.x, PROF == 1 ? ph : gph,
-                                                      emit_arg(em...), h.x)) {
+                                                      emit_arg(em...), h.x, set_arg<KIND>(h.x, em...))) {
       if (lane == 0) big[atomicAdd(n_big, 1u)] = h;
     }
   }
@@ -2012,7 +2173,8 @@ __global__ __launch_bounds__(1024) void repair_block_kernel(
     WiGraph g, WiBase B, const uint2* __restrict__ big, const uint32_t* __restrict__ n_big,
     uint32_t* mark, uint32_t* dlist, uint32_t* dnew, uint32_t* nhn, uint32_t* lvl, uint32_t* ord,
     spf_whatif_digest* out, unsigned long long* prof, uint32_t prof_rows, EM... em) {
-  static_assert(sizeof...(EM) == (EMIT ? 1 : 0) && (!EMIT || PROF == 0), "EMIT: one WiEmit, PROF 0");
+  static_assert(sizeof...(EM) == (EMIT ? 1 : 0) + (KIND == kSet ? 1 : 0) && (!EMIT || PROF == 0),
+                "EMIT: a WiEmit, PROF 0; set plans: a WiSets last");
   __shared__ TeamCtl ctl;
   // the largest repairs are the critical path of a batch and share their CU
   // with wave teams running concurrently: win the issue arbitration
@@ -2032,7 +2194,8 @@ __global__ __launch_bounds__(1024) void repair_block_kernel(
     const uint2 h = big[k];
     repair<1024, false, false, PROF == 2, EMIT, KIND>(g, B, mark, dlist, dnew, nhn, lvl, ord, g.N,
                                                       &ctl, threadIdx.x, h.y, out + h.x,
-                                                      PROF == 1 ? ph : gph, emit_arg(em...), h.x);
+                                                      PROF == 1 ? ph : gph, emit_arg(em...), h.x,
+                                                      set_arg<KIND>(h.x, em...));
   }
   if (PROF == 1 && threadIdx.x == 0)
     if (uint64_t* r = prof_row(prof, team, prof_rows, 2, g.fault))
@@ -2076,7 +2239,8 @@ __global__ __launch_bounds__(kGroupWg) void repair_group_kernel(
     uint32_t* cursor, TeamCtl* ctls, uint32_t* mark, uint32_t* dlist, uint32_t* dnew,
     uint32_t* nhn, uint32_t* lvl, uint32_t* ord, spf_whatif_digest* out,
     unsigned long long* prof, uint32_t prof_rows, EM... em) {
-  static_assert(sizeof...(EM) == (EMIT ? 1 : 0) && (!EMIT || PROF == 0), "EMIT: one WiEmit, PROF 0");
+  static_assert(sizeof...(EM) == (EMIT ? 1 : 0) + (KIND == kSet ? 1 : 0) && (!EMIT || PROF == 0),
+                "EMIT: a WiEmit, PROF 0; set plans: a WiSets last");
   constexpr int TEAM = kGroupWg * G;
   __builtin_amdgcn_s_setprio(3);
   const uint32_t idx = blockIdx.x >> 3;
@@ -2101,7 +2265,7 @@ __global__ __launch_bounds__(kGroupWg) void repair_group_kernel(
     const uint2 h = big[k];
     repair<TEAM, true, false, PROF == 2, EMIT, KIND>(g, B, mark, dlist, dnew, nhn, lvl, ord, g.N, ctl,
                                                      tt, h.y, out + h.x, PROF == 1 ? ph : gph,
-                                                     emit_arg(em...), h.x);
+                                                     emit_arg(em...), h.x, set_arg<KIND>(h.x, em...));
   }
   if (PROF == 1 && tt == 0)
     if (uint64_t* r = prof_row(prof, team, prof_rows, 3, g.fault))
@@ -2176,18 +2340,25 @@ const void* group_kernel_emit(uint32_t G) {
 // instance: the link kernels keep their places in the code object)
 const void* group_kernel_nodes(int kind, uint32_t G, bool emit);
 const void* wave_kernel_nodes(int kind, bool emit);
+// and the set plans', after those
+const void* group_kernel_sets(uint32_t G, bool emit);
+const void* wave_kernel_sets(bool emit);
 
 // one launch, a workgroup per CU (every member of every team resident at
 // once: the team barrier's precondition); with `em` the EMIT instance, the
 // occupancy check made with its own pointer
 hipError_t launch_group(uint32_t G, GroupArgs& a, uint32_t n_cu, int prof, hipStream_t s,
-                        const WiEmit* em = nullptr, int kind = kLink) {
-  const void* k = kind != kLink ? group_kernel_nodes(kind, G, em != nullptr)
+                        const WiEmit* em = nullptr, int kind = kLink, const WiSets* ss = nullptr) {
+  const void* k = kind == kSet ? group_kernel_sets(G, em != nullptr)
+                  : kind != kLink ? group_kernel_nodes(kind, G, em != nullptr)
                   : em ? group_kernel_emit(G) : group_kernel(G, a.prof ? prof : 0);
-  if (!k) return hipErrorInvalidValue;
+  if (!k || (kind == kSet) != (ss != nullptr)) return hipErrorInvalidValue;
   WiEmit e = em ? *em : WiEmit{};
+  WiSets w = ss ? *ss : WiSets{};
+  // the trailing pack: the WiEmit (EMIT instances), then the WiSets (set plans)
   void* args[] = {&a.g, &a.B, &a.big, &a.n_big, &a.cursor, &a.ctls, &a.mark, &a.dlist, &a.dnew,
-                  &a.nhn, &a.lvl, &a.ord, &a.out, &a.prof, &a.prof_rows, &e};
+                  &a.nhn, &a.lvl, &a.ord, &a.out, &a.prof, &a.prof_rows,
+                  em || !ss ? (void*)&e : (void*)&w, &w};
   return launch_resident(k, n_cu, kGroupWg, args, n_cu, s);
 }
 
@@ -2241,7 +2412,11 @@ __global__ void base_digest_kernel(spf_whatif_digest* o, const unsigned long lon
 struct spf_whatif_plan {
   spf_ctx* ctx = nullptr;
   uint32_t src = 0, n_fail = 0, W = 0, wave_teams = 0;
-  uint32_t kind = 0;   // 0: d_fails holds link ids, else SPF_WHATIF_NODE_*: node ids
+  // 0: d_fails holds link ids; SPF_WHATIF_NODE_*: node ids; SPF_WHATIF_LINK_SET:
+  // set_ptr [n_fail + 1], the members in d_set_links (canonical: each set
+  // ascending, duplicates removed) and d_link_edge for every link id
+  uint32_t kind = 0;
+  DevBuf<uint32_t> d_set_links;
   uint64_t epoch = 0;  // graph state the plan was derived from
   DevBuf<uint32_t> d_fails, d_link_edge, d_nbr_bit, d_dist, d_q, d_q2, d_bm, d_nhb, d_ctr;
   DevBuf<uint32_t> d_bar;  // the base kernel's grid-barrier counters
@@ -2400,12 +2575,15 @@ spf_status run_base(spf_whatif_plan* p, const WiGraph& g, hipStream_t s) {
 
 spf_status run_failures_nodes(spf_whatif_plan* p, const WiGraph& g, spf_whatif_digest* d_out,
                               hipStream_t s, const WiEmit* em);  // (below)
+spf_status run_failures_sets(spf_whatif_plan* p, const WiGraph& g, spf_whatif_digest* d_out,
+                             hipStream_t s, const WiEmit* em);  // (below)
 
 // The failures of the plan's list on `s` and the context's side stream:
 // digests into d_out; with `em` the EMIT instances, which also count or fill
 // the change lists (one pass per call).
 spf_status run_failures(spf_whatif_plan* p, const WiGraph& g, spf_whatif_digest* d_out,
                         hipStream_t s, const WiEmit* em) {
+  if (p->kind == (uint32_t)kSet) return run_failures_sets(p, g, d_out, s, em);
   if (p->kind) return run_failures_nodes(p, g, d_out, s, em);
   spf_ctx* c = p->ctx;
   // 2. failures
@@ -2658,9 +2836,160 @@ spf_status run_failures_nodes(spf_whatif_plan* p, const WiGraph& g, spf_whatif_d
                                     : run_failures_nodes_k<kDrain>(p, g, d_out, s, em);
 }
 
-// The part of plan creation that link and node plans share, from the source's
-// neighbour bits to the teams' scratch: p holds ctx, src, kind and n_fail,
-// `fails` its list (link ids with `link_edge`, node ids without).
+// ---------------------------------------------------------------------------
+//  set plans: their kernels and launches, below the node plans' for the same
+//  reason.
+// ---------------------------------------------------------------------------
+// Link sets: a wave per set, its lanes over the members 64 at a time (a hub's
+// 167 links, a conduit's 200, do not serialise on one thread).  Cold (no tight
+// member: the empty set too) -> digest now.  Hot -> work item (failure, size
+// estimate): the saturating sum of sub[] over the tight members' heads.  The
+// sum counts a shared head and a root nested in another root's subtree twice,
+// so it can exceed |D|'s lower bound; it is right for the common case, roots
+// with disjoint subtrees, where the maximum would keep a repair of several
+// near-cap subtrees on a wave team only for it to overflow and be re-queued.
+// Either way the result is the same: an estimate above wave_cap goes to the
+// workgroup teams, a wave team that overflows hands its failure to them.
+__global__ __launch_bounds__(256) void classify_sets_kernel(
+    WiGraph g, const uint32_t* __restrict__ dist, const unsigned long long* __restrict__ H, WiSets ss,
+    uint32_t n_fail, const uint32_t* __restrict__ sub, uint32_t wave_cap, spf_whatif_digest* out,
+    uint2* hot, uint32_t* n_hot, uint2* big, uint32_t* n_big) {
+  const uint32_t f = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+  if (f >= n_fail) return;  // wave-uniform
+  const uint32_t b0 = ss.ptr[f], n = ss.ptr[f + 1] - b0;
+  const auto sat_add = [](uint32_t a, uint32_t b) { return a + b < a ? ~0u : a + b; };
+  uint32_t est = 0;
+  bool any = false;
+  for (uint32_t c0 = 0; c0 < n; c0 += 64) {  // wave-uniform
+    const uint32_t i = c0 + lane;
+    const uint32_t head = i < n ? tight_head(g, dist, ss.link_edge[ss.links[b0 + i]]) : kInf;
+    if (head != kInf) {
+      any = true;
+      est = sat_add(est, sub[head]);
+    }
+  }
+  for (int d = 32; d >= 1; d >>= 1) est = sat_add(est, (uint32_t)__shfl_xor(est, d, 64));
+  const bool is_hot = __ballot(any) != 0;
+  if (lane != 0) return;
+  if (!is_hot) {
+    out[f] = spf_whatif_digest{0u, 0u, (uint64_t)*H};
+  } else if (est > wave_cap) {  // a workgroup's repair
+    big[atomicAdd(n_big, 1u)] = make_uint2(f, est);
+  } else {
+    hot[atomicAdd(n_hot, 1u)] = make_uint2(f, est);
+  }
+}
+
+// sort_big_kernel for set plans: an item's y is its size estimate itself.
+__global__ __launch_bounds__(1024) void sort_big_sets_kernel(const uint2* __restrict__ in,
+                                                             const uint32_t* __restrict__ n_in,
+                                                             uint2* __restrict__ out) {
+  const uint32_t n = *n_in;
+  for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
+    if (n > kSortCap) {
+      out[i] = in[i];
+      continue;
+    }
+    const uint32_t ki = in[i].y;
+    uint32_t r = 0;
+    for (uint32_t j = 0; j < n; ++j) {
+      const uint32_t kj = in[j].y;
+      r += kj > ki || (kj == ki && j < i);
+    }
+    out[r] = in[i];
+  }
+}
+
+// the set plans' instances (no profiled ones)
+const void* group_kernel_sets(uint32_t G, bool emit) {
+  switch (G) {
+    case 2: return emit ? (const void*)repair_group_kernel<2, 0, true, kSet, WiEmit, WiSets>
+                        : (const void*)repair_group_kernel<2, 0, false, kSet, WiSets>;
+    case 4: return emit ? (const void*)repair_group_kernel<4, 0, true, kSet, WiEmit, WiSets>
+                        : (const void*)repair_group_kernel<4, 0, false, kSet, WiSets>;
+    case 8: return emit ? (const void*)repair_group_kernel<8, 0, true, kSet, WiEmit, WiSets>
+                        : (const void*)repair_group_kernel<8, 0, false, kSet, WiSets>;
+    case 16: return emit ? (const void*)repair_group_kernel<16, 0, true, kSet, WiEmit, WiSets>
+                         : (const void*)repair_group_kernel<16, 0, false, kSet, WiSets>;
+    default: return nullptr;
+  }
+}
+const void* wave_kernel_sets(bool emit) {
+  return emit ? (const void*)repair_wave_kernel<0, true, kSet, WiEmit, WiSets>
+              : (const void*)repair_wave_kernel<0, false, kSet, WiSets>;
+}
+
+// run_failures of a set plan: the same launches on the same streams and
+// scratch, the kSet instances of the repairs, work items (failure, estimate).
+spf_status run_failures_sets(spf_whatif_plan* p, const WiGraph& g, spf_whatif_digest* d_out,
+                             hipStream_t s, const WiEmit* em) {
+  spf_ctx* c = p->ctx;
+  HIP_TRY(c, hipMemsetAsync(p->d_cnt.p, 0, 32, s));
+  if (p->group) HIP_TRY(c, hipMemsetAsync(p->d_ctl.p, 0, sizeof(TeamCtl) * p->group_teams, s));
+  if (!p->n_fail) return SPF_OK;
+  const WiSets ss{p->d_fails.p, p->d_set_links.p, p->d_link_edge.p};
+  hipLaunchKernelGGL(classify_sets_kernel, dim3((p->n_fail + 3) / 4), dim3(256), 0, s, g, p->d_dist.p,
+                     p->d_H.p, ss, p->n_fail, p->d_sub.p, p->classify_cap, d_out, p->d_hot.p,
+                     p->d_cnt.p, p->d_big0.p, p->d_cnt.p + 3);
+  HIP_TRY(c, hipGetLastError());
+  WiBase B{p->d_dist.p, p->d_nhb.p, p->d_H.p};
+  hipStream_t side = c->side ? c->side : s;
+  if (c->side) {
+    HIP_TRY(c, hipEventRecord(c->side_fork, s));
+    HIP_TRY(c, hipStreamWaitEvent(c->side, c->side_fork, 0));
+  }
+  bool grouped = false;
+  if (p->group) {
+    hipLaunchKernelGGL(sort_big_sets_kernel, dim3(1), dim3(1024), 0, side, p->d_big0.p, p->d_cnt.p + 3,
+                       p->d_big1.p);
+    HIP_TRY(c, hipGetLastError());
+    GroupArgs ga{g, B, p->d_big1.p, p->d_cnt.p + 3, p->d_cnt.p + 4,
+                 reinterpret_cast<TeamCtl*>(p->d_ctl.p), p->c_mark.p, p->c_dlist.p, p->c_dnew.p,
+                 p->c_nhn.p, p->c_lvl.p, p->c_ord.p, d_out, nullptr, 0u};
+    if (const spf_status st = resident_order(c, side); st != SPF_OK) return st;
+    grouped = launch_group(p->group, ga, c->n_cu, 0, side, em, kSet, &ss) == hipSuccess;
+    if (!grouped) (void)hipGetLastError();  // fall back to one-workgroup teams
+    else if (const spf_status st = resident_done(c, side); st != SPF_OK) return st;
+  }
+  // a block-team launch over `list` (n_list items) with scratch set b_* or c_*
+  const auto blocks = [&](hipStream_t on, const uint2* list, const uint32_t* n_list, bool conc) {
+    uint32_t *mark = conc ? p->c_mark.p : p->b_mark.p, *dlist = conc ? p->c_dlist.p : p->b_dlist.p;
+    uint32_t *dnew = conc ? p->c_dnew.p : p->b_dnew.p, *nhn = conc ? p->c_nhn.p : p->b_nhn.p;
+    uint32_t *lvl = conc ? p->c_lvl.p : p->b_lvl.p, *ord = conc ? p->c_ord.p : p->b_ord.p;
+    if (em)
+      hipLaunchKernelGGL((repair_block_kernel<0, true, kSet, WiEmit, WiSets>), dim3(p->big_teams),
+                         dim3(1024), 0, on, g, B, list, n_list, mark, dlist, dnew, nhn, lvl, ord, d_out,
+                         nullptr, 0u, *em, ss);
+    else
+      hipLaunchKernelGGL((repair_block_kernel<0, false, kSet, WiSets>), dim3(p->big_teams), dim3(1024),
+                         0, on, g, B, list, n_list, mark, dlist, dnew, nhn, lvl, ord, d_out, nullptr, 0u,
+                         ss);
+  };
+  if (!grouped) blocks(side, p->d_big0.p, p->d_cnt.p + 3, true);
+  HIP_TRY(c, hipGetLastError());
+  if (c->side) HIP_TRY(c, hipEventRecord(c->side_join, c->side));
+  if (em)
+    hipLaunchKernelGGL((repair_wave_kernel<0, true, kSet, WiEmit, WiSets>), dim3(p->wave_teams / 4),
+                       dim3(256), 0, s, g, B, p->d_hot.p, p->d_cnt.p, p->d_cnt.p + 1, p->d_big.p,
+                       p->d_cnt.p + 2, p->w_tab.p, p->w_dlist.p, p->w_dnew.p, p->w_nhn.p, p->w_lvl.p,
+                       p->w_ord.p, d_out, p->wave_cap, p->tab_log2, nullptr, 0u, *em, ss);
+  else
+    hipLaunchKernelGGL((repair_wave_kernel<0, false, kSet, WiSets>), dim3(p->wave_teams / 4), dim3(256),
+                       0, s, g, B, p->d_hot.p, p->d_cnt.p, p->d_cnt.p + 1, p->d_big.p, p->d_cnt.p + 2,
+                       p->w_tab.p, p->w_dlist.p, p->w_dnew.p, p->w_nhn.p, p->w_lvl.p, p->w_ord.p,
+                       d_out, p->wave_cap, p->tab_log2, nullptr, 0u, ss);
+  HIP_TRY(c, hipGetLastError());
+  // the wave teams' overflow (|D| or the roots > wave_cap), after them on `s`
+  blocks(s, p->d_big.p, p->d_cnt.p + 2, false);
+  HIP_TRY(c, hipGetLastError());
+  if (c->side) HIP_TRY(c, hipStreamWaitEvent(s, c->side_join, 0));
+  return SPF_OK;
+}
+
+// The part of plan creation that link, node and set plans share, from the
+// source's neighbour bits to the teams' scratch: p holds ctx, src, kind and
+// n_fail, `fails` its list (link ids with `link_edge`, node ids without; a set
+// plan's set_ptr with `link_edge`, its members uploaded by the caller).
 spf_status plan_build(spf_ctx* c, std::unique_ptr<spf_whatif_plan>& p,
                       const std::vector<uint32_t>& fails, const std::vector<uint32_t>* link_edge,
                       spf_whatif_plan** out) {
@@ -2750,7 +3079,12 @@ spf_status plan_build(spf_ctx* c, std::unique_ptr<spf_whatif_plan>& p,
       most = std::max(most, a.numRegs);
       return e;
     };
-    if (p->kind) {
+    if (p->kind == (uint32_t)kSet) {
+      for (const bool emit : {false, true}) {
+        HIP_TRY(c, regs(wave_kernel_sets(emit), rw));
+        HIP_TRY(c, regs(group_kernel_sets(p->group, emit), rg));
+      }
+    } else if (p->kind) {
       for (const bool emit : {false, true}) {
         HIP_TRY(c, regs(wave_kernel_nodes((int)p->kind, emit), rw));
         HIP_TRY(c, regs(group_kernel_nodes((int)p->kind, p->group, emit), rg));
@@ -2769,7 +3103,9 @@ spf_status plan_build(spf_ctx* c, std::unique_ptr<spf_whatif_plan>& p,
     p->wave_teams = std::min(p->wave_teams, per_simd_wave * 4 * c->n_cu);
     if (std::getenv("SPF_WHATIF_DEBUG"))
       std::fprintf(stderr, "whatif%s: wave kernel %d VGPRs, group<%u> %d VGPRs: %u wave teams (%u per SIMD)\n",
-                   p->kind == (uint32_t)kDown ? " (node down)" : p->kind == (uint32_t)kDrain ? " (node drain)" : "",
+                   p->kind == (uint32_t)kDown ? " (node down)"
+                   : p->kind == (uint32_t)kDrain ? " (node drain)"
+                   : p->kind == (uint32_t)kSet ? " (link sets)" : "",
                    rw, p->group, rg, p->wave_teams, per_simd_wave);
   }
   const size_t wt = p->wave_teams;
@@ -2867,6 +3203,8 @@ uint32_t spf_whatif_plan_failures(const spf_whatif_plan* p) { return p ? p->n_fa
 spf_status spf_whatif_plan_links(const spf_whatif_plan* p, uint32_t* links) {
   if (!p || !links) return SPF_E_INVALID;
   spf_ctx* c = p->ctx;
+  if (p->kind == (uint32_t)kSet)
+    return fail(c, SPF_E_STATE, "spf_whatif_plan_links: a set plan (spf_whatif_plan_sets)");
   if (p->kind) return fail(c, SPF_E_STATE, "spf_whatif_plan_links: a node plan (spf_whatif_plan_nodes)");
   HIP_TRY(c, hipMemcpy(links, p->d_fails.p, 4ull * p->n_fail, hipMemcpyDeviceToHost));
   return SPF_OK;
@@ -2908,7 +3246,69 @@ spf_status spf_whatif_plan_nodes(const spf_whatif_plan* p, uint32_t* nodes) {
   if (!p || !nodes) return SPF_E_INVALID;
   spf_ctx* c = p->ctx;
   if (!p->kind) return fail(c, SPF_E_STATE, "spf_whatif_plan_nodes: a link plan (spf_whatif_plan_links)");
+  if (p->kind == (uint32_t)kSet)
+    return fail(c, SPF_E_STATE, "spf_whatif_plan_nodes: a set plan (spf_whatif_plan_sets)");
   HIP_TRY(c, hipMemcpy(nodes, p->d_fails.p, 4ull * p->n_fail, hipMemcpyDeviceToHost));
+  return SPF_OK;
+}
+
+spf_status spf_whatif_plan_create_sets(spf_ctx* c, uint32_t src, const uint32_t* set_ptr,
+                                       const uint32_t* set_links, uint32_t n_sets,
+                                       spf_whatif_plan** out) {
+  if (!c || !out) return fail(c, SPF_E_INVALID, "spf_whatif_plan_create_sets: NULL argument");
+  *out = nullptr;
+  if (!c->loaded) return fail(c, SPF_E_STATE, "no graph loaded");
+  if (src >= c->N) return fail(c, SPF_E_INVALID, "source %u out of range", src);
+  if (n_sets && !set_ptr) return fail(c, SPF_E_INVALID, "spf_whatif_plan_create_sets: NULL set_ptr");
+  if (n_sets && set_ptr[0] != 0)
+    return fail(c, SPF_E_INVALID, "spf_whatif_plan_create_sets: set_ptr[0] = %u, not 0", set_ptr[0]);
+  for (uint32_t i = 0; i < n_sets; ++i)
+    if (set_ptr[i + 1] < set_ptr[i])
+      return fail(c, SPF_E_INVALID, "spf_whatif_plan_create_sets: set_ptr decreases at set %u", i);
+  const uint32_t total = n_sets ? set_ptr[n_sets] : 0u;
+  if (total && !set_links) return fail(c, SPF_E_INVALID, "spf_whatif_plan_create_sets: NULL set_links");
+  for (uint32_t k = 0; k < total; ++k)
+    if (!c->E || set_links[k] > c->max_link)
+      return fail(c, SPF_E_INVALID, "link %u is not a link id of the graph", set_links[k]);
+  if (c->nonpos || c->needs64)
+    return fail(c, SPF_E_UNSUPPORTED,
+                "spf_whatif_plan_create_sets: link sets are not supported on graphs that take the "
+                "exact path (a metric <= 0 or u64 labels)");
+  // canonical sets: each ascending, duplicates removed; the order of the sets kept
+  std::vector<uint32_t> ptr(1, 0u), links;
+  links.reserve(total);
+  for (uint32_t i = 0; i < n_sets; ++i) {
+    const size_t b0 = links.size();
+    links.insert(links.end(), set_links + set_ptr[i], set_links + set_ptr[i + 1]);
+    std::sort(links.begin() + b0, links.end());
+    links.erase(std::unique(links.begin() + b0, links.end()), links.end());
+    ptr.push_back((uint32_t)links.size());
+  }
+  // link -> one of its directed edges; kInf: a down link (a dead slot is a self-loop)
+  std::vector<uint32_t> link_edge((size_t)c->max_link + 1, kInf);
+  for (uint32_t u = 0; u < c->N; ++u)
+    for (uint32_t e = c->row_ptr[u]; e < c->row_ptr[u + 1]; ++e)
+      if (c->col[e] != u && link_edge[c->link[e]] == kInf) link_edge[c->link[e]] = e;
+  auto p = std::make_unique<spf_whatif_plan>();
+  p->ctx = c;
+  p->src = src;
+  p->kind = (uint32_t)kSet;
+  p->n_fail = n_sets;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (links.empty()) links.push_back(0u);  // (never read: every set is empty)
+  HIP_TRY(c, p->d_set_links.upload(links.data(), links.size(), c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // (links is freed on return)
+  return plan_build(c, p, ptr, &link_edge, out);
+}
+
+spf_status spf_whatif_plan_sets(const spf_whatif_plan* p, uint32_t* set_ptr, uint32_t* set_links) {
+  if (!p || !set_ptr) return SPF_E_INVALID;
+  spf_ctx* c = p->ctx;
+  if (p->kind != (uint32_t)kSet)
+    return fail(c, SPF_E_STATE, "spf_whatif_plan_sets: not a set plan (spf_whatif_plan_links / _nodes)");
+  HIP_TRY(c, hipMemcpy(set_ptr, p->d_fails.p, 4ull * ((size_t)p->n_fail + 1), hipMemcpyDeviceToHost));
+  const uint32_t total = set_ptr[p->n_fail];
+  if (total && set_links) HIP_TRY(c, hipMemcpy(set_links, p->d_set_links.p, 4ull * total, hipMemcpyDeviceToHost));
   return SPF_OK;
 }
 

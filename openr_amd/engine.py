@@ -363,14 +363,18 @@ DIGEST_DTYPE =np.dtype([("n_dist_changed", "<u4"), ("n_nh_changed", "<u4"),
                          ("hash", "<u8")])  # spf_whatif_digest
 
 
-WHATIF_KINDS = {"link": 0, "down": N.SPF_WHATIF_NODE_DOWN, "drain": N.SPF_WHATIF_NODE_DRAIN}
+WHATIF_KINDS = {"link": 0, "down": N.SPF_WHATIF_NODE_DOWN, "drain": N.SPF_WHATIF_NODE_DRAIN,
+                "sets": N.SPF_WHATIF_LINK_SET}
 
 
 class WhatIfPlan(NativeHandle):
     """One source and a list of failures (``spf_whatif_plan``): single links
     (``kind == "link"``, ``links``), or nodes down / drained (``"down"`` /
     ``"drain"``, ``nodes``; ``links`` is then empty, as ``nodes`` is for a
-    link plan)."""
+    link plan), or sets of links failing together (``"sets"``: `links` is a
+    sequence of sequences of link ids; ``set_ptr`` / ``set_links`` / ``sets``
+    hold them as the plan does, each ascending without duplicates, and
+    ``links`` and ``nodes`` are empty)."""
 
     _destroy = "spf_whatif_plan_destroy"
 
@@ -381,6 +385,11 @@ class WhatIfPlan(NativeHandle):
         self._eng = eng
         self.kind = kind
         h = C.c_void_p()
+        none = np.zeros(0, np.uint32)
+        self.set_ptr, self.set_links, self.sets = np.zeros(1, np.uint32), none, []
+        if kind == "sets":
+            self._init_sets(eng, src, links)
+            return
         arr = None if links is None else np.ascontiguousarray(links, np.uint32)
         a, n = (None if arr is None else N.ptr(arr)), (0 if arr is None else len(arr))
         if kind == "link":
@@ -393,9 +402,36 @@ class WhatIfPlan(NativeHandle):
         ids = np.zeros(max(1, self.n_fail), np.uint32)
         read = N.lib.spf_whatif_plan_links if kind == "link" else N.lib.spf_whatif_plan_nodes
         eng._err(read(h, N.ptr(ids)))
-        none = np.zeros(0, np.uint32)
         self.links = ids[: self.n_fail] if kind == "link" else none
         self.nodes = none if kind == "link" else ids[: self.n_fail]
+
+    def _init_sets(self, eng: "SpfEngine", src: int, sets) -> None:
+        if sets is None:
+            raise ValueError("a set plan needs its sets")
+        if isinstance(sets, np.ndarray) and sets.ndim == 2:  # equal sizes: one row per set
+            members = sets
+            ptr = (np.arange(len(sets) + 1, dtype=np.uint64) * sets.shape[1]).astype(np.uint32)
+            flat = np.ascontiguousarray(sets, np.uint32).reshape(-1)
+        else:
+            members = [np.ascontiguousarray(s, np.uint32).reshape(-1) for s in sets]
+            ptr = np.zeros(len(members) + 1, np.uint32)
+            ptr[1:] = np.cumsum([len(m) for m in members])
+            flat = np.concatenate(members) if members else np.zeros(0, np.uint32)
+            flat = np.ascontiguousarray(flat, np.uint32)
+        h = C.c_void_p()
+        eng._err(N.lib.spf_whatif_plan_create_sets(eng._h, src, N.ptr(ptr),
+                                                   N.ptr(flat) if len(flat) else None,
+                                                   len(members), C.byref(h)))
+        self._adopt(h)
+        self.n_fail = int(N.lib.spf_whatif_plan_failures(h))
+        self.links = self.nodes = np.zeros(0, np.uint32)
+        self.set_ptr = np.zeros(self.n_fail + 1, np.uint32)
+        eng._err(N.lib.spf_whatif_plan_sets(h, N.ptr(self.set_ptr), None))
+        self.set_links = np.zeros(int(self.set_ptr[-1]), np.uint32)
+        if len(self.set_links):
+            eng._err(N.lib.spf_whatif_plan_sets(h, N.ptr(self.set_ptr), N.ptr(self.set_links)))
+        self.sets = [self.set_links[int(a): int(b)]
+                     for a, b in zip(self.set_ptr[:-1], self.set_ptr[1:])]
 
     def execute(self, d_out: int, d_base: int = 0, stream: int = 0) -> None:
         self._eng._err(N.lib.spf_whatif_execute(self._h, C.c_void_p(d_out),
@@ -778,6 +814,41 @@ class SpfEngine(NativeHandle):
         """What each node failure changes (``whatif_changes`` for nodes down
         or drained).  close() the result (it owns its plan)."""
         plan = self.whatif_node_plan(src, nodes, kind)
+        try:
+            return WhatIfChanges(plan, own_plan=True)
+        except BaseException:
+            plan.close()
+            raise
+
+    def whatif_set_plan(self, src: int, sets: Sequence[Sequence[int]]) -> WhatIfPlan:
+        """A what-if plan whose failures are sets of links that fail together
+        (shared-risk groups): failure i ignores every link of ``sets[i]``."""
+        return self._track(WhatIfPlan(self, src, sets, "sets"))
+
+    def whatif_sets(self, src: int, sets: Sequence[Sequence[int]]):
+        """Digests of runSpf(src, true, set) for each set of links:
+        (digests[n], base digest)."""
+        from .hiprt import DeviceArray, set_device
+
+        plan = self.whatif_set_plan(src, sets)
+        try:
+            set_device(self.device)
+            d_out = DeviceArray(max(1, plan.n_fail), DIGEST_DTYPE)
+            d_base = DeviceArray(1, DIGEST_DTYPE)
+            try:
+                plan.execute(d_out.ptr, d_base.ptr)
+                plan.stats()  # waits for the execute, checks the device's fault word
+                return d_out.numpy()[: plan.n_fail], d_base.numpy()[0]
+            finally:
+                d_out.free()
+                d_base.free()
+        finally:
+            plan.close()
+
+    def whatif_set_changes(self, src: int, sets: Sequence[Sequence[int]]) -> WhatIfChanges:
+        """What each link-set failure changes (``whatif_changes`` for sets).
+        close() the result (it owns its plan)."""
+        plan = self.whatif_set_plan(src, sets)
         try:
             return WhatIfChanges(plan, own_plan=True)
         except BaseException:
