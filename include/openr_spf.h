@@ -585,7 +585,55 @@ spf_status spf_whatif_plan_create_sets(spf_ctx* ctx, uint32_t src,
  * alone.  SPF_E_STATE on a link or node plan (as spf_whatif_plan_links and
  * _plan_nodes are on a set plan). */
 spf_status spf_whatif_plan_sets(const spf_whatif_plan* plan, uint32_t* set_ptr, uint32_t* set_links);
-/* 0 = link plan, SPF_WHATIF_NODE_* or SPF_WHATIF_LINK_SET */
+/* ---- what-if batches for link metric changes (cost-out and undrain: the
+ * reference's LinkMonitor setLinkMetric / setAdjacencyMetric, `breeze lm
+ * set-link-metric`).
+ * "Failure i" of the plan is a change (links[i], m_lo[i], m_hi[i]): runSpf(src)
+ * on the graph in which that link's direction from its endpoint with the
+ * smaller csr id to the larger weighs m_lo[i] and the opposite direction
+ * m_hi[i], against the unchanged runSpf(src).  SPF_WHATIF_METRIC_KEEP (0, no
+ * metric of the positive envelope) keeps a direction's metric.  The link stays
+ * usable: no failure of the other kinds expresses this, nor the way back
+ * (lowering a metric to put traffic back on a link).  The result is an
+ * ordinary spf_whatif_plan: spf_whatif_execute, _changes, _changes_db / _read /
+ * _buffers / _timing, _base, _stats, _enable_timing, _timing, _plan_failures
+ * and _plan_destroy work on it unchanged, and spf_whatif_plan_kind returns
+ * SPF_WHATIF_LINK_METRIC.  The digest and the list entry are the link plans':
+ * the next-hop bitset is over the distinct up neighbours of src in the
+ * unchanged graph.  A metric change never alters that neighbour set or anyone's
+ * reachability, so no entry carries dist == UINT64_MAX.
+ *   One direction at most can matter, because metrics are positive: if u -> v
+ *     is tight, or becomes useful (d(u) + w' <= d(v)), then d(u) < d(v), and the
+ *     reverse direction cannot reach u at or below d(u) whatever it weighs.
+ *   Cold (digest {0, 0, hash}, no entries): the link is down; both directions
+ *     kept or equal to the current metric; a raised direction that is not
+ *     tight; a lowered u -> v with d(u) + w' > d(v), or u unreachable, or u not
+ *     expanded (overloaded and not src).
+ *   Hot: a raise of a tight u -> v repairs the DAG descendants of v, the link
+ *     plan's affected set, with the edge kept at its new weight; a lower with
+ *     delta = d(v) - d(u) - w' >= 0 repairs the nodes reached from v over
+ *     edges of slack <= delta, a superset of what can change (delta = 0: a new
+ *     equal-cost tie, distances stay and next hops grow).
+ * The order of the list is kept, and a link may appear several times with
+ * different metrics (one link swept over ten metrics is one plan).
+ * SPF_E_INVALID: a link id that is not a link id of the graph (> the largest
+ * link id loaded), NULL arrays with n > 0, a metric so large that metric x
+ * n_nodes >= 2^32 - 1 (the bound past which a loaded graph leaves 32-bit
+ * distances).  SPF_E_UNSUPPORTED: graphs that take the exact path (a metric <= 0
+ * or u64 labels), as for node and set plans.  SPF_WHATIF_PROF is ignored by
+ * metric plans. */
+#define SPF_WHATIF_LINK_METRIC 4u /* failure i = one link's metrics changed */
+#define SPF_WHATIF_METRIC_KEEP 0u /* m_lo / m_hi: keep this direction's metric */
+spf_status spf_whatif_plan_create_metrics(spf_ctx* ctx, uint32_t src, const uint32_t* links /* [n] */,
+                                          const uint32_t* m_lo /* [n] */,
+                                          const uint32_t* m_hi /* [n] */, uint32_t n,
+                                          spf_whatif_plan** out);
+/* The plan's changes as given, [n_fail] each; any output may be NULL.
+ * SPF_E_STATE on a link, node or set plan (as spf_whatif_plan_links, _plan_nodes
+ * and _plan_sets are on a metric plan). */
+spf_status spf_whatif_plan_metrics(const spf_whatif_plan* plan, uint32_t* links, uint32_t* m_lo,
+                                   uint32_t* m_hi);
+/* 0 = link plan, SPF_WHATIF_NODE_*, SPF_WHATIF_LINK_SET or SPF_WHATIF_LINK_METRIC */
 spf_status spf_whatif_plan_kind(const spf_whatif_plan* plan, uint32_t* kind);
 /* d_out = [n_fail] digests, d_base = 1 digest (may be NULL).  Enqueued on
  * `stream` (a grid-resident launch for the unfailed solve); no host

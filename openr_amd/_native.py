@@ -34,6 +34,8 @@ SPF_KSP2_NONE = 0xFFFFFFFF
 SPF_WHATIF_NODE_DOWN = 1
 SPF_WHATIF_NODE_DRAIN = 2
 SPF_WHATIF_LINK_SET = 3
+SPF_WHATIF_LINK_METRIC = 4
+SPF_WHATIF_METRIC_KEEP = 0
 KSP2_KIND_NAMES = ("EXACT", "HBM", "LDS_U32", "LDS_U16")  # spf_ksp2_kind
 SPF_ROUTE_LFA = 0x1
 SPF_ROUTE_COMPACT = 0x2
@@ -260,6 +262,9 @@ PROTOTYPES = {
     "spf_whatif_plan_create_sets": (C.c_int, [_vp, C.c_uint32, _u32p, _u32p, C.c_uint32,
                                               C.POINTER(_vp)]),
     "spf_whatif_plan_sets": (C.c_int, [_vp, _u32p, _u32p]),
+    "spf_whatif_plan_create_metrics": (C.c_int, [_vp, C.c_uint32, _u32p, _u32p, _u32p, C.c_uint32,
+                                                 C.POINTER(_vp)]),
+    "spf_whatif_plan_metrics": (C.c_int, [_vp, _u32p, _u32p, _u32p]),
     "spf_whatif_plan_kind": (C.c_int, [_vp, _u32p]),
     "spf_whatif_execute": (C.c_int, [_vp, _vp, _vp, _vp]),
     "spf_whatif_stats": (C.c_int, [_vp, _u32p, _u32p]),

@@ -35,7 +35,7 @@ void metric_flags(GraphHost& g) {
   // compare it, and that sum must neither wrap nor reach kInf (a 50-node
   // chain at 87,652,393 per link has d = 2^32 - 39 at its far end, and the
   // relaxation back from there wrapped to a "shorter" distance)
-  g.needs64 = g.n_neg > 0 || (uint64_t)g.max_metric * (uint64_t)g.N >= (uint64_t)kInf;
+  g.needs64 = g.n_neg > 0 || metric_past_u32(g.max_metric, g.N);
   g.unit = !g.nonpos && g.max_metric <= 1;
 }
 // the counts gain / lose the live edges of u's row

@@ -31,6 +31,12 @@ inline uint32_t ms_own(uint32_t N) {
   return own <= 1 ? 1 : own <= 2 ? 2 : own <= 4 ? 4 : own <= 8 ? 8 : own <= 10 ? 10 : own <= 12 ? 12 : 16;
 }
 
+// Does a largest metric `m` on an N-node graph leave 32-bit distances (the
+// bound argued at metric_flags; what-if metric changes are held to it too)
+inline bool metric_past_u32(uint32_t m, uint32_t N) {
+  return (uint64_t)m * (uint64_t)N >= (uint64_t)kInf;
+}
+
 struct GraphHost {
   bool loaded = false;
   uint32_t N = 0, E = 0, pitch = 0;

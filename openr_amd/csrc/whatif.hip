@@ -50,6 +50,33 @@
 //  or non-tight members only).  A single link is a set of one, DOWN x the set
 //  linksFromNode(x).
 //
+//  Link metric changes (spf_whatif_plan_create_metrics: cost-out, undrain) are
+//  the fifth kind: change i = (link l, m_lo, m_hi) is runSpf(src) on the graph
+//  in which l's two directions weigh m_lo (smaller CSR id -> larger) and m_hi
+//  (0 keeps a direction).  Nothing is failed: what changes is what an edge
+//  WEIGHS (w_fwd / w_rev below substitute the two new weights wherever a weight
+//  of l's two directed edges is read).  One direction at most can matter,
+//  because metrics are positive: if u -> v is tight, or becomes useful
+//  (d(u) + w' <= d(v)), then d(u) < d(v), and v -> u cannot reach u at or below
+//  d(u) whatever it weighs.
+//    * cold: l is down; both directions kept or equal to the current metric; a
+//      raised direction that is not tight; a lowered u -> v with
+//      d(u) + w' > d(v), or u unreachable, or u not expanded (drained, not src).
+//    * raise of a tight u -> v: D = the DAG descendants of v, the link plan's D,
+//      but the edge stays: it seeds v from u at w'.
+//    * lower with d(u) + w' <= d(v): delta = d(v) - d(u) - w' >= 0 (0: a new
+//      ECMP tie, distances stay, next hops grow).  No node improves by more
+//      than delta.  D grows from v over edges x -> c with
+//      d(x) + w(x, c) <= d(c) + delta (unfailed distances on both sides; c
+//      reachable and not src, which never changes): a shortest new path from v
+//      to a changed node runs through changed nodes only, and each of its edges
+//      has slack <= delta.  The set is closed -- a node outside it keeps its
+//      distance and its tight predecessors -- and the repair is exact for any
+//      D whose complement is unchanged; unchanged nodes of D add nothing to
+//      the digest and are no entries.  With delta = 0 the test is the tight
+//      test: raises and lowers share one loop, delta a team-uniform scalar.
+//  No change alters src's neighbour set or anyone's reachability.
+//
 //  Digest of a result (same definition in oracle/spf_oracle.cpp):
 //    n_dist_changed, n_nh_changed (a node becoming unreachable counts in both)
 //    hash = sum over reachable v of mix(mix(v + 1) + d(v)) ^ fnv(nh(v) words)
@@ -76,9 +103,9 @@ constexpr uint32_t kDialLevels = 1024;         // distinct distances settled buc
 
 // What a plan's failures are, a template parameter of the repairs: one link,
 // or a node down / drained (SPF_WHATIF_NODE_DOWN / SPF_WHATIF_NODE_DRAIN).
-constexpr int kLink = 0, kDown = 1, kDrain = 2, kSet = 3;
+constexpr int kLink = 0, kDown = 1, kDrain = 2, kSet = 3, kMetric = 4;
 static_assert(kDown == SPF_WHATIF_NODE_DOWN && kDrain == SPF_WHATIF_NODE_DRAIN &&
-                  kSet == SPF_WHATIF_LINK_SET, "plan kinds");
+                  kSet == SPF_WHATIF_LINK_SET && kMetric == SPF_WHATIF_LINK_METRIC, "plan kinds");
 
 // Is the edge v -> u (link id `link`) unusable, in both directions, under
 // the failure: link l itself, or (node x down) any edge with an end at x.
@@ -151,6 +178,53 @@ __device__ __forceinline__ bool failed(const SetRef<KIND>& sr, uint32_t x, uint3
                                        uint32_t u, uint32_t link) {
   if constexpr (KIND == kSet) return set_has(sr, link);
   else return failed<KIND>(x, l, v_is_x, u, link);
+}
+
+// A metric plan's changes on the device: change f is chg[f] = {e_lo, e_hi,
+// w_lo, w_hi} -- the changed link's directed edge out of its endpoint with the
+// smaller CSR id, the reverse edge, and what each weighs under the change (a
+// kept direction: its current metric); e_lo = kInf for a down link.
+// delta[f] is written by classify_metrics_kernel.  The metric kernels'
+// trailing argument.
+struct WiMet {
+  const uint4* chg;
+  const uint32_t* delta;
+};
+// The change of one repair (KIND == kMetric), team-uniform and in scalar
+// registers: SetRef's place in the repairs' argument lists.
+template <>
+struct SetRef<kMetric> {
+  uint32_t e_lo, e_hi, w_lo, w_hi, delta;
+};
+__device__ __forceinline__ SetRef<kMetric> met_of(const WiMet& m, uint32_t f) {
+  const uint4 q = m.chg[f];
+  const auto uni = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane(x); };
+  return SetRef<kMetric>{uni(q.x), uni(q.y), uni(q.z), uni(q.w), uni(m.delta[f])};
+}
+// What CSR edge e weighs (w_fwd; `w` as read from the graph) and what the edge
+// reverse to e weighs (w_rev) under the failure: the graph's weights, except
+// for the two directed edges of a metric plan's changed link.
+template <int KIND>
+__device__ __forceinline__ uint32_t w_fwd(const SetRef<KIND>& sr, uint32_t e, uint32_t w) {
+  if constexpr (KIND == kMetric) return e == sr.e_lo ? sr.w_lo : (e == sr.e_hi ? sr.w_hi : w);
+  else return w;
+}
+template <int KIND>
+__device__ __forceinline__ uint32_t w_rev(const SetRef<KIND>& sr, uint32_t e, uint32_t w) {
+  if constexpr (KIND == kMetric) return e == sr.e_lo ? sr.w_hi : (e == sr.e_hi ? sr.w_lo : w);
+  else return w;
+}
+// Does edge e = x -> c (graph weight w; unfailed distances dx, dc) put c into
+// D: a tight edge of the unfailed DAG -- for a metric plan an edge with slack
+// <= delta (in 64 bits: dc + delta may pass 2^32), whose head is reachable and
+// not src (src never changes, and D's nodes are seeded from outside D).
+template <int KIND>
+__device__ __forceinline__ bool grows(const SetRef<KIND>& sr, uint32_t src, uint32_t e, uint32_t dx,
+                                      uint32_t w, uint32_t c, uint32_t dc) {
+  if constexpr (KIND == kMetric)
+    return dc != kInf && c != src && (uint64_t)dx + w_fwd<KIND>(sr, e, w) <= (uint64_t)dc + sr.delta;
+  else
+    return dx + w == dc;
 }
 
 __device__ __forceinline__ uint32_t ld(const uint32_t* p) {
@@ -1063,12 +1137,20 @@ __device__ __forceinline__ const WiEmit* emit_arg(const WiSets&) { return nullpt
 __device__ __forceinline__ const WiEmit* emit_arg(const WiEmit& e, const WiSets&) { return &e; }
 __device__ __forceinline__ const WiSets& sets_arg(const WiSets& s) { return s; }
 __device__ __forceinline__ const WiSets& sets_arg(const WiEmit&, const WiSets& s) { return s; }
-// failure f's set (set plans), nothing for the other kinds
+// (metric plans: the pack ends with the WiMet)
+__device__ __forceinline__ const WiEmit* emit_arg(const WiMet&) { return nullptr; }
+__device__ __forceinline__ const WiEmit* emit_arg(const WiEmit& e, const WiMet&) { return &e; }
+__device__ __forceinline__ const WiMet& met_arg(const WiMet& m) { return m; }
+__device__ __forceinline__ const WiMet& met_arg(const WiEmit&, const WiMet& m) { return m; }
+// failure f's set (set plans) or change (metric plans), nothing for the other kinds
 template <int KIND, class... EM>
 __device__ __forceinline__ SetRef<KIND> set_arg(uint32_t f, const EM&... em) {
   if constexpr (KIND == kSet) return set_of(sets_arg(em...), f);
+  else if constexpr (KIND == kMetric) return met_of(met_arg(em...), f);
   else return SetRef<KIND>{};
 }
+// do the kernels of this kind end their argument pack with a per-plan table
+constexpr bool kind_has_table(int kind) { return kind == kSet || kind == kMetric; }
 
 // The head of link edge e0's tight direction in the unfailed DAG, kInf when
 // neither is tight (or e0 = kInf, a down link): classify_kernel's test --
@@ -1267,7 +1349,9 @@ __device__ __forceinline__ void ph_max(uint64_t* ph, int k, uint64_t v, bool lea
 // EMIT (spf_whatif_changes): the repair also counts (em->cnode NULL) or
 // writes (fill pass) failure f's change list, before the digest loop.
 // KIND: `y` is the failed link's tight edge (kLink) or the failed node; a set
-// plan's failure is `sr` (y is its size estimate, not used here).
+// plan's failure is `sr` (y is its size estimate, not used here).  kMetric: y
+// is the changed link's hot edge u -> v (D's root is its head v), `sr` the
+// change; nothing is failed, the edge weights come through w_fwd / w_rev.
 template <int TEAM, bool GROUP = false, bool CHK = false, bool GPH = false, bool EMIT = false,
           int KIND = kLink>
 __device__ bool repair(const WiGraph& g, const WiBase& B, uint32_t* mark, uint32_t* dlist,
@@ -1304,7 +1388,7 @@ __device__ bool repair(const WiGraph& g, const WiBase& B, uint32_t* mark, uint32
   // D's root b = dlist[0]: the failed link's head, or the failed node x
   const uint32_t x = y;
   const uint32_t l = KIND == kLink ? g.link[y] : 0u;
-  const uint32_t b = KIND == kLink ? g.col[y] : y;
+  const uint32_t b = KIND == kLink || KIND == kMetric ? g.col[y] : y;
   if (tt == 0) {
     stw<GROUP>(&ctl->n, KIND == kSet ? 0u : 1u);
     stw<GROUP>(&ctl->ovf, 0u);
@@ -1385,7 +1469,8 @@ __device__ bool repair(const WiGraph& g, const WiBase& B, uint32_t* mark, uint32
         if (act) {
           const uint4 q = g.ed[e];
           c = q.x;
-          if (dk + q.y == B.dist[c]) won = atomicCAS(&mark[c], kInf, kBusy) == kInf;
+          if (grows<KIND>(sr, g.src, e, dk, q.y, c, B.dist[c]))
+            won = atomicCAS(&mark[c], kInf, kBusy) == kInf;
         }
         const uint64_t wm = __ballot(won);
         if (wm) {
@@ -1441,7 +1526,7 @@ __device__ bool repair(const WiGraph& g, const WiBase& B, uint32_t* mark, uint32
         const uint32_t u = q.x;
         if (ldw<GROUP>(&mark[u]) == kInf && !(g.ovl[u] && u != g.src)) {
           const uint32_t du = B.dist[u];
-          if (du != kInf) s = du + q.w;
+          if (du != kInf) s = du + w_rev<KIND>(sr, e, q.w);
         }
       }
       if (s != kInf) {
@@ -1465,7 +1550,7 @@ __device__ bool repair(const WiGraph& g, const WiBase& B, uint32_t* mark, uint32
       if ((g.ovl[u] && u != g.src) || drain_x<KIND>(x, u)) continue;
       const uint32_t mu = chk(ldw<GROUP>(&mark[u]), n, true, 5, kInf);
       const uint32_t du = mu != kInf ? ldw<GROUP>(&dnew[mu]) : B.dist[u];
-      if (du == kInf || du + in_w(g, e) != dv) continue;
+      if (du == kInf || du + w_rev<KIND>(sr, e, in_w(g, e)) != dv) continue;
       if (u == g.src) {
         const uint32_t jb = g.nbr_bit[v];
         if ((jb >> 5) == j) acc |= 1u << (jb & 31);
@@ -1562,10 +1647,10 @@ __device__ bool repair(const WiGraph& g, const WiBase& B, uint32_t* mark, uint32
           mu = chk(ldw<GROUP>(&mark[u]), n, true, 13, kInf);
           if (!(g.ovl[u] && u != g.src) && !drain_x<KIND>(x, u)) {
             const uint32_t du = mu != kInf ? ldw<GROUP>(&dnew[mu]) : B.dist[u];
-            tight = du != kInf && du + (g.hop ? 1u : q.w) == t;
+            tight = du != kInf && du + w_rev<KIND>(sr, e, g.hop ? 1u : q.w) == t;
           }
           if (tk && mu != kInf) {  // relax v -> u (u pending: its value only drops)
-            const uint32_t nd = t + q.y;
+            const uint32_t nd = t + w_fwd<KIND>(sr, e, q.y);
             if (nd < atomicMin(&dnew[mu], nd)) m = min(m, nd);
           }
           if (tight && u == g.src) {
@@ -1599,7 +1684,7 @@ __device__ bool repair(const WiGraph& g, const WiBase& B, uint32_t* mark, uint32
           if (failed<KIND>(sr, x, l, false, g.col[e], g.link[e])) continue;
           const uint32_t ic = chk(ldw<GROUP>(&mark[g.col[e]]), n, true, 14, kInf);
           if (ic == kInf) continue;
-          const uint32_t nd = dv + g.wt[e];
+          const uint32_t nd = dv + w_fwd<KIND>(sr, e, g.wt[e]);
           if (nd < atomicMin(&dnew[ic], nd)) any = true;
         }
       }
@@ -1846,7 +1931,7 @@ __device__ bool repair_wave(const WiGraph& g, const WiBase& B, const WaveSet& hs
   const uint32_t W = g.W;
   const uint32_t x = y;  // (repair(): l, b)
   const uint32_t l = KIND == kLink ? g.link[y] : 0u;
-  const uint32_t b = KIND == kLink ? g.col[y] : y;
+  const uint32_t b = KIND == kLink || KIND == kMetric ? g.col[y] : y;
   if (lane == 0) {
     if constexpr (KIND != kSet) {
       dlist[0] = b;
@@ -1908,7 +1993,7 @@ __device__ bool repair_wave(const WiGraph& g, const WiBase& B, const WaveSet& hs
         if (act) {
           const uint4 q = g.ed[e];
           c = q.x;
-          if (dk + q.y == B.dist[c]) slot = ws_claim(hs, c, full);
+          if (grows<KIND>(sr, g.src, e, dk, q.y, c, B.dist[c])) slot = ws_claim(hs, c, full);
         }
         const bool won = slot != ~0u;
         const uint64_t wm = __ballot(won);
@@ -1956,7 +2041,7 @@ __device__ bool repair_wave(const WiGraph& g, const WiBase& B, const WaveSet& hs
         const uint32_t u = q.x;
         if (ws_find(hs, u) == kInf && !(g.ovl[u] && u != g.src)) {
           const uint32_t du = B.dist[u];
-          if (du != kInf) s = du + q.w;
+          if (du != kInf) s = du + w_rev<KIND>(sr, e, q.w);
         }
       }
       if (s != kInf)
@@ -2030,10 +2115,10 @@ __device__ bool repair_wave(const WiGraph& g, const WiBase& B, const WaveSet& hs
           mu = chk(ws_find(hs, u), n, true, 13, kInf);
           if (!(g.ovl[u] && u != g.src) && !drain_x<KIND>(x, u)) {
             const uint32_t du = mu != kInf ? ldw<false>(&dnew[mu]) : B.dist[u];
-            tight = du != kInf && du + (g.hop ? 1u : q.w) == t;
+            tight = du != kInf && du + w_rev<KIND>(sr, e, g.hop ? 1u : q.w) == t;
           }
           if (tk && mu != kInf) {  // relax v -> u (u pending: its value only drops)
-            const uint32_t nd = t + q.y;
+            const uint32_t nd = t + w_fwd<KIND>(sr, e, q.y);
             if (nd < atomicMin(&dnew[mu], nd)) m = min(m, nd);
           }
           if (tight && u == g.src) {
@@ -2137,8 +2222,8 @@ __global__ __launch_bounds__(256) void repair_wave_kernel(
     uint32_t* cursor, uint2* big, uint32_t* n_big, unsigned long long* tab, uint32_t* dlist,
     uint32_t* dnew, uint32_t* nhn, uint32_t* lvl, uint32_t* ord, spf_whatif_digest* out, uint32_t cap,
     uint32_t tab_log2, unsigned long long* prof, uint32_t prof_rows, EM... em) {
-  static_assert(sizeof...(EM) == (EMIT ? 1 : 0) + (KIND == kSet ? 1 : 0) && (!EMIT || PROF == 0),
-                "EMIT: a WiEmit, PROF 0; set plans: a WiSets last");
+  static_assert(sizeof...(EM) == (EMIT ? 1 : 0) + (kind_has_table(KIND) ? 1 : 0) && (!EMIT || PROF == 0),
+                "EMIT: a WiEmit, PROF 0; set plans: a WiSets last, metric plans: a WiMet");
   __shared__ TeamCtl ctl[4];
   const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const size_t team = (size_t)blockIdx.x * 4 + w;
@@ -2173,8 +2258,8 @@ __global__ __launch_bounds__(1024) void repair_block_kernel(
     WiGraph g, WiBase B, const uint2* __restrict__ big, const uint32_t* __restrict__ n_big,
     uint32_t* mark, uint32_t* dlist, uint32_t* dnew, uint32_t* nhn, uint32_t* lvl, uint32_t* ord,
     spf_whatif_digest* out, unsigned long long* prof, uint32_t prof_rows, EM... em) {
-  static_assert(sizeof...(EM) == (EMIT ? 1 : 0) + (KIND == kSet ? 1 : 0) && (!EMIT || PROF == 0),
-                "EMIT: a WiEmit, PROF 0; set plans: a WiSets last");
+  static_assert(sizeof...(EM) == (EMIT ? 1 : 0) + (kind_has_table(KIND) ? 1 : 0) && (!EMIT || PROF == 0),
+                "EMIT: a WiEmit, PROF 0; set plans: a WiSets last, metric plans: a WiMet");
   __shared__ TeamCtl ctl;
   // the largest repairs are the critical path of a batch and share their CU
   // with wave teams running concurrently: win the issue arbitration
@@ -2239,8 +2324,8 @@ __global__ __launch_bounds__(kGroupWg) void repair_group_kernel(
     uint32_t* cursor, TeamCtl* ctls, uint32_t* mark, uint32_t* dlist, uint32_t* dnew,
     uint32_t* nhn, uint32_t* lvl, uint32_t* ord, spf_whatif_digest* out,
     unsigned long long* prof, uint32_t prof_rows, EM... em) {
-  static_assert(sizeof...(EM) == (EMIT ? 1 : 0) + (KIND == kSet ? 1 : 0) && (!EMIT || PROF == 0),
-                "EMIT: a WiEmit, PROF 0; set plans: a WiSets last");
+  static_assert(sizeof...(EM) == (EMIT ? 1 : 0) + (kind_has_table(KIND) ? 1 : 0) && (!EMIT || PROF == 0),
+                "EMIT: a WiEmit, PROF 0; set plans: a WiSets last, metric plans: a WiMet");
   constexpr int TEAM = kGroupWg * G;
   __builtin_amdgcn_s_setprio(3);
   const uint32_t idx = blockIdx.x >> 3;
@@ -2343,22 +2428,31 @@ const void* wave_kernel_nodes(int kind, bool emit);
 // and the set plans', after those
 const void* group_kernel_sets(uint32_t G, bool emit);
 const void* wave_kernel_sets(bool emit);
+// and the metric plans', after those
+const void* group_kernel_metrics(uint32_t G, bool emit);
+const void* wave_kernel_metrics(bool emit);
 
 // one launch, a workgroup per CU (every member of every team resident at
 // once: the team barrier's precondition); with `em` the EMIT instance, the
 // occupancy check made with its own pointer
 hipError_t launch_group(uint32_t G, GroupArgs& a, uint32_t n_cu, int prof, hipStream_t s,
-                        const WiEmit* em = nullptr, int kind = kLink, const WiSets* ss = nullptr) {
-  const void* k = kind == kSet ? group_kernel_sets(G, em != nullptr)
+                        const WiEmit* em = nullptr, int kind = kLink, const WiSets* ss = nullptr,
+                        const WiMet* mm = nullptr) {
+  const void* k = kind == kMetric ? group_kernel_metrics(G, em != nullptr)
+                  : kind == kSet ? group_kernel_sets(G, em != nullptr)
                   : kind != kLink ? group_kernel_nodes(kind, G, em != nullptr)
                   : em ? group_kernel_emit(G) : group_kernel(G, a.prof ? prof : 0);
-  if (!k || (kind == kSet) != (ss != nullptr)) return hipErrorInvalidValue;
+  if (!k || (kind == kSet) != (ss != nullptr) || (kind == kMetric) != (mm != nullptr))
+    return hipErrorInvalidValue;
   WiEmit e = em ? *em : WiEmit{};
   WiSets w = ss ? *ss : WiSets{};
-  // the trailing pack: the WiEmit (EMIT instances), then the WiSets (set plans)
+  WiMet m = mm ? *mm : WiMet{};
+  // the trailing pack: the WiEmit (EMIT instances), then the kind's table (the
+  // WiSets of a set plan, the WiMet of a metric plan)
+  void* const table = mm ? (void*)&m : (void*)&w;
   void* args[] = {&a.g, &a.B, &a.big, &a.n_big, &a.cursor, &a.ctls, &a.mark, &a.dlist, &a.dnew,
                   &a.nhn, &a.lvl, &a.ord, &a.out, &a.prof, &a.prof_rows,
-                  em || !ss ? (void*)&e : (void*)&w, &w};
+                  em || !(ss || mm) ? (void*)&e : table, table};
   return launch_resident(k, n_cu, kGroupWg, args, n_cu, s);
 }
 
@@ -2415,8 +2509,14 @@ struct spf_whatif_plan {
   // 0: d_fails holds link ids; SPF_WHATIF_NODE_*: node ids; SPF_WHATIF_LINK_SET:
   // set_ptr [n_fail + 1], the members in d_set_links (canonical: each set
   // ascending, duplicates removed) and d_link_edge for every link id
+  // SPF_WHATIF_LINK_METRIC: d_fails holds the link ids, d_met the changes as
+  // the kernels read them (WiMet::chg), d_delta what classify found, m_lo /
+  // m_hi the metrics as given (spf_whatif_plan_metrics)
   uint32_t kind = 0;
   DevBuf<uint32_t> d_set_links;
+  DevBuf<uint4> d_met;
+  DevBuf<uint32_t> d_delta;
+  std::vector<uint32_t> m_lo, m_hi;
   uint64_t epoch = 0;  // graph state the plan was derived from
   DevBuf<uint32_t> d_fails, d_link_edge, d_nbr_bit, d_dist, d_q, d_q2, d_bm, d_nhb, d_ctr;
   DevBuf<uint32_t> d_bar;  // the base kernel's grid-barrier counters
@@ -2577,12 +2677,15 @@ spf_status run_failures_nodes(spf_whatif_plan* p, const WiGraph& g, spf_whatif_d
                               hipStream_t s, const WiEmit* em);  // (below)
 spf_status run_failures_sets(spf_whatif_plan* p, const WiGraph& g, spf_whatif_digest* d_out,
                              hipStream_t s, const WiEmit* em);  // (below)
+spf_status run_failures_metrics(spf_whatif_plan* p, const WiGraph& g, spf_whatif_digest* d_out,
+                                hipStream_t s, const WiEmit* em);  // (below)
 
 // The failures of the plan's list on `s` and the context's side stream:
 // digests into d_out; with `em` the EMIT instances, which also count or fill
 // the change lists (one pass per call).
 spf_status run_failures(spf_whatif_plan* p, const WiGraph& g, spf_whatif_digest* d_out,
                         hipStream_t s, const WiEmit* em) {
+  if (p->kind == (uint32_t)kMetric) return run_failures_metrics(p, g, d_out, s, em);
   if (p->kind == (uint32_t)kSet) return run_failures_sets(p, g, d_out, s, em);
   if (p->kind) return run_failures_nodes(p, g, d_out, s, em);
   spf_ctx* c = p->ctx;
@@ -2986,6 +3089,141 @@ spf_status run_failures_sets(spf_whatif_plan* p, const WiGraph& g, spf_whatif_di
   return SPF_OK;
 }
 
+// ---------------------------------------------------------------------------
+//  metric plans: their kernels and launches, below the set plans' for the same
+//  reason.
+// ---------------------------------------------------------------------------
+// Link metric changes: cold -> digest now, hot -> work item (change, hot edge
+// u -> v) and delta[f].  A direction a -> b whose weight changes from w to w'
+// (a reachable and expanded) is hot when it is raised and tight, or lowered
+// with d(a) + w' <= d(b) (delta = the slack); one direction at most is
+// (positive metrics: a hot direction has d(a) < d(b)).  With delta = 0, D is
+// the DAG descendants of b (a raise) or holds them (a new tie), so the parent
+// subtree sub[b] is a lower bound of |D| and routes the item as a link
+// failure's; with delta > 0 no bound is known: the wave teams take it and
+// hand it to the workgroup teams when its D overflows.
+__global__ void classify_metrics_kernel(WiGraph g, const uint32_t* __restrict__ dist,
+                                        const unsigned long long* __restrict__ H,
+                                        const uint4* __restrict__ chg, uint32_t n_fail,
+                                        const uint32_t* __restrict__ sub, uint32_t wave_cap,
+                                        spf_whatif_digest* out, uint2* hot, uint32_t* n_hot,
+                                        uint2* big, uint32_t* n_big, uint32_t* delta) {
+  const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= n_fail) return;
+  const uint4 m = chg[f];
+  uint32_t root = kInf, dl = 0;
+  if (m.x != kInf && !g.hop) {  // (hop counts: no metric is read, every change is cold)
+    for (uint32_t k = 0; k < 2; ++k) {
+      const uint32_t e = k ? m.y : m.x, w1 = k ? m.w : m.z, w0 = g.wt[e];
+      const uint32_t a = g.col[g.rev[e]], b = g.col[e];  // a -> b
+      if (w1 == w0 || (g.ovl[a] && a != g.src)) continue;
+      const uint32_t da = dist[a], db = dist[b];
+      if (da == kInf) continue;  // (a reached and expanded over an up link: b is reached)
+      if (w1 > w0 ? da + w0 == db : (uint64_t)da + w1 <= db) {
+        root = e;
+        dl = w1 > w0 ? 0u : db - da - w1;
+      }
+    }
+  }
+  delta[f] = dl;
+  if (root == kInf) {
+    out[f] = spf_whatif_digest{0u, 0u, (uint64_t)*H};
+  } else if (dl == 0 && sub[g.col[root]] > wave_cap) {  // |D| >= subtree: a workgroup's repair
+    big[atomicAdd(n_big, 1u)] = make_uint2(f, root);
+  } else {
+    hot[atomicAdd(n_hot, 1u)] = make_uint2(f, root);
+  }
+}
+
+// the metric plans' instances (no profiled ones)
+const void* group_kernel_metrics(uint32_t G, bool emit) {
+  switch (G) {
+    case 2: return emit ? (const void*)repair_group_kernel<2, 0, true, kMetric, WiEmit, WiMet>
+                        : (const void*)repair_group_kernel<2, 0, false, kMetric, WiMet>;
+    case 4: return emit ? (const void*)repair_group_kernel<4, 0, true, kMetric, WiEmit, WiMet>
+                        : (const void*)repair_group_kernel<4, 0, false, kMetric, WiMet>;
+    case 8: return emit ? (const void*)repair_group_kernel<8, 0, true, kMetric, WiEmit, WiMet>
+                        : (const void*)repair_group_kernel<8, 0, false, kMetric, WiMet>;
+    case 16: return emit ? (const void*)repair_group_kernel<16, 0, true, kMetric, WiEmit, WiMet>
+                         : (const void*)repair_group_kernel<16, 0, false, kMetric, WiMet>;
+    default: return nullptr;
+  }
+}
+const void* wave_kernel_metrics(bool emit) {
+  return emit ? (const void*)repair_wave_kernel<0, true, kMetric, WiEmit, WiMet>
+              : (const void*)repair_wave_kernel<0, false, kMetric, WiMet>;
+}
+
+// run_failures of a metric plan: the same launches on the same streams and
+// scratch, the kMetric instances of the repairs, work items (change, hot
+// edge) -- the link plans' items, so the classified big ones are sorted by
+// sort_big_kernel.
+spf_status run_failures_metrics(spf_whatif_plan* p, const WiGraph& g, spf_whatif_digest* d_out,
+                                hipStream_t s, const WiEmit* em) {
+  spf_ctx* c = p->ctx;
+  HIP_TRY(c, hipMemsetAsync(p->d_cnt.p, 0, 32, s));
+  if (p->group) HIP_TRY(c, hipMemsetAsync(p->d_ctl.p, 0, sizeof(TeamCtl) * p->group_teams, s));
+  if (!p->n_fail) return SPF_OK;
+  hipLaunchKernelGGL(classify_metrics_kernel, dim3((p->n_fail + 255) / 256), dim3(256), 0, s, g,
+                     p->d_dist.p, p->d_H.p, p->d_met.p, p->n_fail, p->d_sub.p, p->classify_cap, d_out,
+                     p->d_hot.p, p->d_cnt.p, p->d_big0.p, p->d_cnt.p + 3, p->d_delta.p);
+  HIP_TRY(c, hipGetLastError());
+  const WiMet mm{p->d_met.p, p->d_delta.p};
+  WiBase B{p->d_dist.p, p->d_nhb.p, p->d_H.p};
+  hipStream_t side = c->side ? c->side : s;
+  if (c->side) {
+    HIP_TRY(c, hipEventRecord(c->side_fork, s));
+    HIP_TRY(c, hipStreamWaitEvent(c->side, c->side_fork, 0));
+  }
+  bool grouped = false;
+  if (p->group) {
+    hipLaunchKernelGGL(sort_big_kernel, dim3(1), dim3(1024), 0, side, p->d_big0.p, p->d_cnt.p + 3,
+                       p->d_sub.p, c->d_col.p, p->d_big1.p);
+    HIP_TRY(c, hipGetLastError());
+    GroupArgs ga{g, B, p->d_big1.p, p->d_cnt.p + 3, p->d_cnt.p + 4,
+                 reinterpret_cast<TeamCtl*>(p->d_ctl.p), p->c_mark.p, p->c_dlist.p, p->c_dnew.p,
+                 p->c_nhn.p, p->c_lvl.p, p->c_ord.p, d_out, nullptr, 0u};
+    if (const spf_status st = resident_order(c, side); st != SPF_OK) return st;
+    grouped = launch_group(p->group, ga, c->n_cu, 0, side, em, kMetric, nullptr, &mm) == hipSuccess;
+    if (!grouped) (void)hipGetLastError();  // fall back to one-workgroup teams
+    else if (const spf_status st = resident_done(c, side); st != SPF_OK) return st;
+  }
+  // a block-team launch over `list` (n_list items) with scratch set b_* or c_*
+  const auto blocks = [&](hipStream_t on, const uint2* list, const uint32_t* n_list, bool conc) {
+    uint32_t *mark = conc ? p->c_mark.p : p->b_mark.p, *dlist = conc ? p->c_dlist.p : p->b_dlist.p;
+    uint32_t *dnew = conc ? p->c_dnew.p : p->b_dnew.p, *nhn = conc ? p->c_nhn.p : p->b_nhn.p;
+    uint32_t *lvl = conc ? p->c_lvl.p : p->b_lvl.p, *ord = conc ? p->c_ord.p : p->b_ord.p;
+    if (em)
+      hipLaunchKernelGGL((repair_block_kernel<0, true, kMetric, WiEmit, WiMet>), dim3(p->big_teams),
+                         dim3(1024), 0, on, g, B, list, n_list, mark, dlist, dnew, nhn, lvl, ord, d_out,
+                         nullptr, 0u, *em, mm);
+    else
+      hipLaunchKernelGGL((repair_block_kernel<0, false, kMetric, WiMet>), dim3(p->big_teams), dim3(1024),
+                         0, on, g, B, list, n_list, mark, dlist, dnew, nhn, lvl, ord, d_out, nullptr, 0u,
+                         mm);
+  };
+  if (!grouped) blocks(side, p->d_big0.p, p->d_cnt.p + 3, true);
+  HIP_TRY(c, hipGetLastError());
+  if (c->side) HIP_TRY(c, hipEventRecord(c->side_join, c->side));
+  if (em)
+    hipLaunchKernelGGL((repair_wave_kernel<0, true, kMetric, WiEmit, WiMet>), dim3(p->wave_teams / 4),
+                       dim3(256), 0, s, g, B, p->d_hot.p, p->d_cnt.p, p->d_cnt.p + 1, p->d_big.p,
+                       p->d_cnt.p + 2, p->w_tab.p, p->w_dlist.p, p->w_dnew.p, p->w_nhn.p, p->w_lvl.p,
+                       p->w_ord.p, d_out, p->wave_cap, p->tab_log2, nullptr, 0u, *em, mm);
+  else
+    hipLaunchKernelGGL((repair_wave_kernel<0, false, kMetric, WiMet>), dim3(p->wave_teams / 4), dim3(256),
+                       0, s, g, B, p->d_hot.p, p->d_cnt.p, p->d_cnt.p + 1, p->d_big.p, p->d_cnt.p + 2,
+                       p->w_tab.p, p->w_dlist.p, p->w_dnew.p, p->w_nhn.p, p->w_lvl.p, p->w_ord.p,
+                       d_out, p->wave_cap, p->tab_log2, nullptr, 0u, mm);
+  HIP_TRY(c, hipGetLastError());
+  // the wave teams' overflow (|D| > wave_cap: the lowers with a large delta
+  // among them), after them on `s`
+  blocks(s, p->d_big.p, p->d_cnt.p + 2, false);
+  HIP_TRY(c, hipGetLastError());
+  if (c->side) HIP_TRY(c, hipStreamWaitEvent(s, c->side_join, 0));
+  return SPF_OK;
+}
+
 // The part of plan creation that link, node and set plans share, from the
 // source's neighbour bits to the teams' scratch: p holds ctx, src, kind and
 // n_fail, `fails` its list (link ids with `link_edge`, node ids without; a set
@@ -3079,7 +3317,12 @@ spf_status plan_build(spf_ctx* c, std::unique_ptr<spf_whatif_plan>& p,
       most = std::max(most, a.numRegs);
       return e;
     };
-    if (p->kind == (uint32_t)kSet) {
+    if (p->kind == (uint32_t)kMetric) {
+      for (const bool emit : {false, true}) {
+        HIP_TRY(c, regs(wave_kernel_metrics(emit), rw));
+        HIP_TRY(c, regs(group_kernel_metrics(p->group, emit), rg));
+      }
+    } else if (p->kind == (uint32_t)kSet) {
       for (const bool emit : {false, true}) {
         HIP_TRY(c, regs(wave_kernel_sets(emit), rw));
         HIP_TRY(c, regs(group_kernel_sets(p->group, emit), rg));
@@ -3105,7 +3348,8 @@ spf_status plan_build(spf_ctx* c, std::unique_ptr<spf_whatif_plan>& p,
       std::fprintf(stderr, "whatif%s: wave kernel %d VGPRs, group<%u> %d VGPRs: %u wave teams (%u per SIMD)\n",
                    p->kind == (uint32_t)kDown ? " (node down)"
                    : p->kind == (uint32_t)kDrain ? " (node drain)"
-                   : p->kind == (uint32_t)kSet ? " (link sets)" : "",
+                   : p->kind == (uint32_t)kSet ? " (link sets)"
+                   : p->kind == (uint32_t)kMetric ? " (link metrics)" : "",
                    rw, p->group, rg, p->wave_teams, per_simd_wave);
   }
   const size_t wt = p->wave_teams;
@@ -3203,6 +3447,8 @@ uint32_t spf_whatif_plan_failures(const spf_whatif_plan* p) { return p ? p->n_fa
 spf_status spf_whatif_plan_links(const spf_whatif_plan* p, uint32_t* links) {
   if (!p || !links) return SPF_E_INVALID;
   spf_ctx* c = p->ctx;
+  if (p->kind == (uint32_t)kMetric)
+    return fail(c, SPF_E_STATE, "spf_whatif_plan_links: a metric plan (spf_whatif_plan_metrics)");
   if (p->kind == (uint32_t)kSet)
     return fail(c, SPF_E_STATE, "spf_whatif_plan_links: a set plan (spf_whatif_plan_sets)");
   if (p->kind) return fail(c, SPF_E_STATE, "spf_whatif_plan_links: a node plan (spf_whatif_plan_nodes)");
@@ -3248,6 +3494,8 @@ spf_status spf_whatif_plan_nodes(const spf_whatif_plan* p, uint32_t* nodes) {
   if (!p->kind) return fail(c, SPF_E_STATE, "spf_whatif_plan_nodes: a link plan (spf_whatif_plan_links)");
   if (p->kind == (uint32_t)kSet)
     return fail(c, SPF_E_STATE, "spf_whatif_plan_nodes: a set plan (spf_whatif_plan_sets)");
+  if (p->kind == (uint32_t)kMetric)
+    return fail(c, SPF_E_STATE, "spf_whatif_plan_nodes: a metric plan (spf_whatif_plan_metrics)");
   HIP_TRY(c, hipMemcpy(nodes, p->d_fails.p, 4ull * p->n_fail, hipMemcpyDeviceToHost));
   return SPF_OK;
 }
@@ -3309,6 +3557,72 @@ spf_status spf_whatif_plan_sets(const spf_whatif_plan* p, uint32_t* set_ptr, uin
   HIP_TRY(c, hipMemcpy(set_ptr, p->d_fails.p, 4ull * ((size_t)p->n_fail + 1), hipMemcpyDeviceToHost));
   const uint32_t total = set_ptr[p->n_fail];
   if (total && set_links) HIP_TRY(c, hipMemcpy(set_links, p->d_set_links.p, 4ull * total, hipMemcpyDeviceToHost));
+  return SPF_OK;
+}
+
+spf_status spf_whatif_plan_create_metrics(spf_ctx* c, uint32_t src, const uint32_t* links,
+                                          const uint32_t* m_lo, const uint32_t* m_hi, uint32_t n,
+                                          spf_whatif_plan** out) {
+  if (!c || !out) return fail(c, SPF_E_INVALID, "spf_whatif_plan_create_metrics: NULL argument");
+  *out = nullptr;
+  if (!c->loaded) return fail(c, SPF_E_STATE, "no graph loaded");
+  if (src >= c->N) return fail(c, SPF_E_INVALID, "source %u out of range", src);
+  if (n && (!links || !m_lo || !m_hi))
+    return fail(c, SPF_E_INVALID, "spf_whatif_plan_create_metrics: NULL links, m_lo or m_hi");
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!c->E || links[i] > c->max_link)
+      return fail(c, SPF_E_INVALID, "link %u is not a link id of the graph", links[i]);
+    for (const uint32_t m : {m_lo[i], m_hi[i]})
+      if (spfi::metric_past_u32(m, c->N))  // the loader's bound on the largest metric
+        return fail(c, SPF_E_INVALID,
+                    "spf_whatif_plan_create_metrics: metric %u of change %u (link %u) x %u nodes "
+                    "leaves 32-bit distances", m, i, links[i], c->N);
+  }
+  if (c->nonpos || c->needs64)
+    return fail(c, SPF_E_UNSUPPORTED,
+                "spf_whatif_plan_create_metrics: link metric changes are not supported on graphs that "
+                "take the exact path (a metric <= 0 or u64 labels)");
+  // link -> its directed edge out of the endpoint with the smaller CSR id (the
+  // first met in row order); kInf: a down link (a dead slot is a self-loop)
+  std::vector<uint32_t> link_edge((size_t)c->max_link + 1, kInf);
+  for (uint32_t u = 0; u < c->N; ++u)
+    for (uint32_t e = c->row_ptr[u]; e < c->row_ptr[u + 1]; ++e)
+      if (c->col[e] != u && link_edge[c->link[e]] == kInf) link_edge[c->link[e]] = e;
+  auto p = std::make_unique<spf_whatif_plan>();
+  p->ctx = c;
+  p->src = src;
+  p->kind = (uint32_t)kMetric;
+  p->n_fail = n;
+  p->m_lo.assign(m_lo, m_lo + n);
+  p->m_hi.assign(m_hi, m_hi + n);
+  std::vector<uint32_t> fails(links, links + n);
+  if (fails.empty()) fails.push_back(0u);  // (never read: no change)
+  std::vector<uint4> chg(std::max<uint32_t>(n, 1), make_uint4(kInf, kInf, 0u, 0u));
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t e = link_edge[links[i]];
+    if (e == kInf) continue;
+    const uint32_t r = c->rev[e];
+    chg[i] = make_uint4(e, r, m_lo[i] != SPF_WHATIF_METRIC_KEEP ? m_lo[i] : c->wt[e],
+                        m_hi[i] != SPF_WHATIF_METRIC_KEEP ? m_hi[i] : c->wt[r]);
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, p->d_met.upload(chg.data(), chg.size(), c->stream));
+  HIP_TRY(c, p->d_delta.alloc(std::max<uint32_t>(n, 1)));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // (chg is freed on return)
+  return plan_build(c, p, fails, nullptr, out);
+}
+
+spf_status spf_whatif_plan_metrics(const spf_whatif_plan* p, uint32_t* links, uint32_t* m_lo,
+                                   uint32_t* m_hi) {
+  if (!p) return SPF_E_INVALID;
+  spf_ctx* c = p->ctx;
+  if (p->kind != (uint32_t)kMetric)
+    return fail(c, SPF_E_STATE,
+                "spf_whatif_plan_metrics: not a metric plan (spf_whatif_plan_links / _nodes / _sets)");
+  if (links && p->n_fail)
+    HIP_TRY(c, hipMemcpy(links, p->d_fails.p, 4ull * p->n_fail, hipMemcpyDeviceToHost));
+  if (m_lo) std::copy(p->m_lo.begin(), p->m_lo.end(), m_lo);
+  if (m_hi) std::copy(p->m_hi.begin(), p->m_hi.end(), m_hi);
   return SPF_OK;
 }
 

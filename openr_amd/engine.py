@@ -364,7 +364,7 @@ DIGEST_DTYPE =np.dtype([("n_dist_changed", "<u4"), ("n_nh_changed", "<u4"),
 
 
 WHATIF_KINDS = {"link": 0, "down": N.SPF_WHATIF_NODE_DOWN, "drain": N.SPF_WHATIF_NODE_DRAIN,
-                "sets": N.SPF_WHATIF_LINK_SET}
+                "sets": N.SPF_WHATIF_LINK_SET, "metric": N.SPF_WHATIF_LINK_METRIC}
 
 
 class WhatIfPlan(NativeHandle):
@@ -374,7 +374,10 @@ class WhatIfPlan(NativeHandle):
     link plan), or sets of links failing together (``"sets"``: `links` is a
     sequence of sequences of link ids; ``set_ptr`` / ``set_links`` / ``sets``
     hold them as the plan does, each ascending without duplicates, and
-    ``links`` and ``nodes`` are empty)."""
+    ``links`` and ``nodes`` are empty), or link metric changes (``"metric"``:
+    `links` is a sequence of ``(link, m_lo, m_hi)`` triples, 0 keeping a
+    direction's metric; ``metric_changes`` holds them as an ``[n, 3]`` array and
+    ``links`` their link ids, in the order given)."""
 
     _destroy = "spf_whatif_plan_destroy"
 
@@ -387,8 +390,12 @@ class WhatIfPlan(NativeHandle):
         h = C.c_void_p()
         none = np.zeros(0, np.uint32)
         self.set_ptr, self.set_links, self.sets = np.zeros(1, np.uint32), none, []
+        self.metric_changes = np.zeros((0, 3), np.uint32)
         if kind == "sets":
             self._init_sets(eng, src, links)
+            return
+        if kind == "metric":
+            self._init_metrics(eng, src, links)
             return
         arr = None if links is None else np.ascontiguousarray(links, np.uint32)
         a, n = (None if arr is None else N.ptr(arr)), (0 if arr is None else len(arr))
@@ -432,6 +439,22 @@ class WhatIfPlan(NativeHandle):
             eng._err(N.lib.spf_whatif_plan_sets(h, N.ptr(self.set_ptr), N.ptr(self.set_links)))
         self.sets = [self.set_links[int(a): int(b)]
                      for a, b in zip(self.set_ptr[:-1], self.set_ptr[1:])]
+
+    def _init_metrics(self, eng: "SpfEngine", src: int, changes) -> None:
+        if changes is None:
+            raise ValueError("a metric plan needs its (link, m_lo, m_hi) changes")
+        given = np.ascontiguousarray(changes, np.uint32).reshape(-1, 3)
+        cols = [np.ascontiguousarray(given[:, k]) for k in range(3)]
+        h = C.c_void_p()
+        args = [N.ptr(c) if len(given) else None for c in cols]
+        eng._err(N.lib.spf_whatif_plan_create_metrics(eng._h, src, *args, len(given), C.byref(h)))
+        self._adopt(h)
+        self.n_fail = int(N.lib.spf_whatif_plan_failures(h))
+        self.nodes = np.zeros(0, np.uint32)
+        held = [np.zeros(max(1, self.n_fail), np.uint32) for _ in range(3)]
+        eng._err(N.lib.spf_whatif_plan_metrics(h, *[N.ptr(x) for x in held]))
+        self.metric_changes = np.stack([x[: self.n_fail] for x in held], axis=1)
+        self.links = self.metric_changes[:, 0].copy()
 
     def execute(self, d_out: int, d_base: int = 0, stream: int = 0) -> None:
         self._eng._err(N.lib.spf_whatif_execute(self._h, C.c_void_p(d_out),
@@ -849,6 +872,43 @@ class SpfEngine(NativeHandle):
         """What each link-set failure changes (``whatif_changes`` for sets).
         close() the result (it owns its plan)."""
         plan = self.whatif_set_plan(src, sets)
+        try:
+            return WhatIfChanges(plan, own_plan=True)
+        except BaseException:
+            plan.close()
+            raise
+
+    def whatif_metric_plan(self, src: int, changes: Sequence[Sequence[int]]) -> WhatIfPlan:
+        """A what-if plan whose failures are link metric changes (cost-out,
+        undrain): change i is ``(link, m_lo, m_hi)``, the new metrics of the
+        link's direction from its endpoint with the smaller node id to the
+        larger and of the opposite one; 0 keeps a direction's metric."""
+        return self._track(WhatIfPlan(self, src, changes, "metric"))
+
+    def whatif_metrics(self, src: int, changes: Sequence[Sequence[int]]):
+        """Digests of runSpf(src) under each metric change:
+        (digests[n], base digest)."""
+        from .hiprt import DeviceArray, set_device
+
+        plan = self.whatif_metric_plan(src, changes)
+        try:
+            set_device(self.device)
+            d_out = DeviceArray(max(1, plan.n_fail), DIGEST_DTYPE)
+            d_base = DeviceArray(1, DIGEST_DTYPE)
+            try:
+                plan.execute(d_out.ptr, d_base.ptr)
+                plan.stats()  # waits for the execute, checks the device's fault word
+                return d_out.numpy()[: plan.n_fail], d_base.numpy()[0]
+            finally:
+                d_out.free()
+                d_base.free()
+        finally:
+            plan.close()
+
+    def whatif_metric_changes(self, src: int, changes: Sequence[Sequence[int]]) -> WhatIfChanges:
+        """What each link metric change changes (``whatif_changes`` for
+        metric changes).  close() the result (it owns its plan)."""
+        plan = self.whatif_metric_plan(src, changes)
         try:
             return WhatIfChanges(plan, own_plan=True)
         except BaseException:
