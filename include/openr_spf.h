@@ -710,6 +710,80 @@ spf_status spf_whatif_changes_buffers(spf_whatif_plan* plan, const uint64_t** d_
  * unreachable nodes), *W; every output may be NULL.  Waits for the last
  * execute / changes call; SPF_E_STATE before the first. */
 spf_status spf_whatif_base(spf_whatif_plan* plan, uint64_t* dist, uint32_t* nh, uint32_t* W);
+/* ---- what-if route impact: which ROUTES of src each failure changes.
+ * A route belongs to a prefix, a prefix is advertised by a set of nodes
+ * (anycast, a default route, a VIP).  Set s = set_nodes[set_ptr[s] ..
+ * set_ptr[s + 1]) is given exactly as for spf_routes: the advertisers of one
+ * prefix, already filtered by the caller for reachability / drain as
+ * buildRouteDb does.  A what-if drain does NOT re-filter them: a set keeps a
+ * member the failure drains.  The route of set s is (min_metric, nh):
+ *   min_metric  u64  getMinCostNodes (Decision.cpp:1082-1105): the min of
+ *                    dist(v) over the reachable members, UINT64_MAX when none
+ *                    is reachable
+ *   nh[W]       u32  the OR of nh(v) over the members at that min
+ *                    (getNextHopsWithMetric without LFA, :1107-1155), in the
+ *                    change lists' own bitset: bits over the distinct up
+ *                    neighbours of src in the unfailed graph, W words
+ * A repeated member counts once; a set that holds src is src's own prefix,
+ * metric 0 and no next hops whatever else it holds.
+ * For failure i of the plan: the sets whose route under failure i differs from
+ * the base route in min_metric or in any word.  One exactly sized set per
+ * plan, on the device until the next call:
+ *   rptr[n_fail + 1]   u64  failure i owns entries rptr[i] .. rptr[i + 1]
+ *   rset[total]        u32  set id (two identical sets are two entries)
+ *   rmetric[total]     u64  the new min_metric; a withdrawn route is listed
+ *                           with UINT64_MAX and zero words
+ *   rnh[total * W]     u32
+ * Empty sets, sets unreachable in the base and sets that hold src are never
+ * listed.  The order of a failure's entries on the device is unspecified
+ * (spf_whatif_routes_db sorts).  *n_entries = total, *pool_bytes =
+ * 8 (n_fail + 1) + total (12 + 4 W), *kernel_ms = the four phases of
+ * spf_whatif_routes_timing together; the outputs are optional.  n_sets == 0 is
+ * allowed: zero entries.
+ *
+ * A device-side consumer of the resident change lists: it needs
+ * spf_whatif_changes on the plan first, reads only the lists and the unfailed
+ * result, and so works on every plan kind (links, nodes down / drained, link
+ * sets, metric changes, and link plans on exact-path graphs).  Built as the
+ * lists are: the base routes and a lookup table over the list entries, a
+ * count pass driven by the entries, a scan, a fill pass into the exactly sized
+ * pools (kept while they are large enough).  Waits.
+ * SPF_E_INVALID: a NULL plan, set_ptr[0] != 0, set_ptr decreasing, a node id
+ * >= n_nodes, NULL arrays with members.  SPF_E_STATE: the plan holds no lists;
+ * the graph changed since the plan was created.  SPF_E_NOMEM: the pools or
+ * the table do not fit.  SPF_E_HIP: a fill pass that meets more entries than
+ * were counted drops them, as the lists do.  After a failed call the plan
+ * holds no route lists, and a new spf_whatif_changes on the plan invalidates
+ * them.
+ * Node-level next hops are the deliberate scope: the expansion over src's own
+ * links (getNextHopsThrift), LFA and SpfSolver's prefix bookkeeping stay with
+ * the caller. */
+spf_status spf_whatif_routes(spf_whatif_plan* plan, const uint32_t* set_ptr /* [n_sets + 1] */,
+                             const uint32_t* set_nodes /* [set_ptr[n_sets]] */, uint32_t n_sets,
+                             uint64_t* n_entries, uint64_t* pool_bytes, double* kernel_ms,
+                             void* stream);
+/* Every set's base route: min_metric[n_sets], nh[n_sets * W]; either may be
+ * NULL.  This and the calls below: SPF_E_STATE when the plan holds no route
+ * lists (before a successful spf_whatif_routes). */
+spf_status spf_whatif_routes_base(spf_whatif_plan* plan, uint64_t* min_metric, uint32_t* nh);
+/* Failure i's entries, ascending by set id (sorted on the host): *n of them;
+ * set[cap], min_metric[cap], nh[cap * W] are filled when cap >= *n,
+ * SPF_E_NOMEM (with *n set) otherwise.  Every output may be NULL. */
+spf_status spf_whatif_routes_db(spf_whatif_plan* plan, uint32_t i, uint32_t* set, uint64_t* min_metric,
+                                uint32_t* nh, uint64_t cap, uint64_t* n);
+/* The whole set in one copy per array, in device order: ptr[n_fail + 1],
+ * set[total], min_metric[total], nh[total * W].  Every output may be NULL. */
+spf_status spf_whatif_routes_read(spf_whatif_plan* plan, uint64_t* ptr, uint32_t* set,
+                                  uint64_t* min_metric, uint32_t* nh);
+/* The device arrays, for device-side consumers (valid until the next
+ * spf_whatif_routes or spf_whatif_changes on the plan); every output may be
+ * NULL. */
+spf_status spf_whatif_routes_buffers(spf_whatif_plan* plan, const uint64_t** d_ptr,
+                                     const uint32_t** d_set, const uint64_t** d_metric,
+                                     const uint32_t** d_nh, uint32_t* W, uint64_t* n_entries);
+/* ms[4] = base routes + table, count pass, scan, fill pass of the last
+ * spf_whatif_routes. */
+spf_status spf_whatif_routes_timing(const spf_whatif_plan* plan, double* ms);
 /* Convenience: plan + execute + copy back. out = [n_fail] (n_fail = number of
  * up links when fail_links is NULL), base may be NULL. */
 spf_status spf_whatif_solve(spf_ctx* ctx, uint32_t src, const uint32_t* fail_links,

@@ -278,6 +278,14 @@ PROTOTYPES = {
     "spf_whatif_changes_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
                                              C.POINTER(_vp), _u32p, _u64p]),
     "spf_whatif_base": (C.c_int, [_vp, _u64p, _u32p, _u32p]),
+    "spf_whatif_routes": (C.c_int, [_vp, _u32p, _u32p, C.c_uint32, _u64p, _u64p,
+                                    C.POINTER(C.c_double), _vp]),
+    "spf_whatif_routes_base": (C.c_int, [_vp, _u64p, _u32p]),
+    "spf_whatif_routes_db": (C.c_int, [_vp, C.c_uint32, _u32p, _u64p, _u32p, C.c_uint64, _u64p]),
+    "spf_whatif_routes_read": (C.c_int, [_vp, _u64p, _u32p, _u64p, _u32p]),
+    "spf_whatif_routes_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
+                                            C.POINTER(_vp), _u32p, _u64p]),
+    "spf_whatif_routes_timing": (C.c_int, [_vp, C.POINTER(C.c_double)]),
     "spf_routes": (C.c_int, [_vp, C.c_uint32, _u32p, _u32p, C.c_uint32, C.c_uint32, _u64p,
                              _u32p, _u32p, _u64p]),
     # multi-device context (openr_spf.h)

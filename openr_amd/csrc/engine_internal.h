@@ -131,6 +131,51 @@ struct ExactWhatIf {
   uint32_t src = 0, n_fail = 0, W = 1;
 };
 
+// Route lists of a what-if batch (spf_whatif_routes, whatif_routes.hip): the
+// caller's sets and their inverse index on the device, the base in the lists'
+// layout, every set's base route, the lookup table over the change lists'
+// entries and the exactly sized pools (all kept while they are large enough).
+struct WiRoutes {
+  bool valid = false;  // a call succeeded; no spf_whatif_changes or failed call since
+  uint32_t n_sets = 0;
+  uint64_t total = 0;
+  double ms[4] = {0, 0, 0, 0};  // base + index, count, scan, fill of the last call
+  DevBuf<uint32_t> d_set_ptr, d_set_nodes, d_inv_ptr, d_inv_set, d_inv_pos;
+  DevBuf<unsigned long long> d_bd;  // [N] base metrics, ~0: unreachable
+  DevBuf<uint32_t> d_bnh;           // [N][W] base rows, zero where unreachable
+  DevBuf<unsigned long long> d_rbm;  // [n_sets] base routes
+  DevBuf<uint32_t> d_rbnh;           // [n_sets][W]
+  DevBuf<unsigned long long> d_keys;  // (failure << 32 | node), ~0: empty
+  DevBuf<uint32_t> d_vals, d_efail;   // entry index per slot; failure per entry
+  DevBuf<uint32_t> d_cnt, d_cur;      // [n_fail] counts, fill cursors
+  DevBuf<unsigned long long> d_rptr, d_rmet;  // [n_fail + 1], [total]
+  DevBuf<uint32_t> d_rset, d_rnh;             // [total], [total][W]
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  ~WiRoutes() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+// What whatif_routes.hip reads of a plan (whatif.hip owns spf_whatif_plan):
+// the lists of the last spf_whatif_changes, the unfailed result as the plan
+// holds it (u32 metrics with kInf and rows that are undefined where
+// unreachable, or the exact plan's u64 ones), and the plan's route lists.
+struct WiListsView {
+  spf_ctx* ctx = nullptr;
+  WiRoutes* rt = nullptr;
+  bool has_lists = false, no_nbr = false;  // no_nbr: src has no up neighbour (rows undefined)
+  uint64_t epoch = 0, total = 0;
+  uint32_t src = 0, n_fail = 0, W = 1;
+  const unsigned long long* cptr = nullptr;
+  const uint32_t* cnode = nullptr;
+  const unsigned long long* cdist = nullptr;
+  const uint32_t* cnh = nullptr;
+  const uint32_t* base_d32 = nullptr;  // one of the two
+  const uint64_t* base_d64 = nullptr;
+  const uint32_t* base_nh = nullptr;  // [N][W]
+};
+
 // KSP2 on the exact kernel: the sources' runs (labels, pop ranks), then a
 // wave per pair tracing k = 1 and replaying k = 2 (exact.hip).
 struct ExactKsp2 {
@@ -452,6 +497,9 @@ spf_status launch_exact(spf_ctx* c, ExactScratch* x, const uint32_t* d_srcs, uin
                         const uint64_t* d_nh_off, uint32_t Wmax, bool hop, bool dist64,
                         const uint32_t* ign, void* d_dist, uint32_t* d_nh, uint32_t* d_pop,
                         hipStream_t s);
+// A what-if plan's lists, base and route-list state (whatif.hip), for
+// spf_whatif_routes (whatif_routes.hip); p is not NULL.
+void whatif_lists_view(spf_whatif_plan* p, WiListsView* v);
 // spf_big_kernel (whatif.hip): the plan's sources one after another on the
 // whole chip -- frontier SSSP into the dist rows, next hops in distance
 // order, transposed into the plan's bitmaps.  Positive metrics or hop counts.

@@ -2557,6 +2557,9 @@ struct spf_whatif_plan {
   bool has_lists = false;
   hipEvent_t l_ev[4] = {nullptr, nullptr, nullptr, nullptr};
   float l_ms[3] = {0, 0, 0};
+  // route lists of the last spf_whatif_routes (whatif_routes.hip), a consumer
+  // of the lists above: spf_whatif_changes invalidates them
+  spfi::WiRoutes rt;
   ~spf_whatif_plan() {
     for (hipEvent_t e : ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : l_ev)
@@ -2565,6 +2568,26 @@ struct spf_whatif_plan {
 };
 
 namespace spfi {
+
+void whatif_lists_view(spf_whatif_plan* p, WiListsView* v) {
+  const spf_ctx* c = p->ctx;
+  v->ctx = p->ctx;
+  v->rt = &p->rt;
+  v->has_lists = p->has_lists;
+  v->no_nbr = p->src + 1 < c->nb_ptr.size() && c->nb_ptr[p->src + 1] == c->nb_ptr[p->src];
+  v->epoch = p->epoch;
+  v->total = p->l_total;
+  v->src = p->src;
+  v->n_fail = p->n_fail;
+  v->W = p->W;
+  v->cptr = p->l_ptr.p;
+  v->cnode = p->l_node.p;
+  v->cdist = p->l_dist.p;
+  v->cnh = p->l_nh.p;
+  v->base_d32 = p->exact ? nullptr : p->d_dist.p;
+  v->base_d64 = p->exact ? p->exact->base_d.p : nullptr;
+  v->base_nh = p->exact ? p->exact->base_nh.p : p->d_nhb.p;
+}
 
 // Blocks of a grid-barrier launch: `per_cu` 512-thread blocks per CU, clamped
 // to what the occupancy calculator says stays co-resident (XGrid needs every
@@ -3715,6 +3738,7 @@ spf_status spf_whatif_changes(spf_whatif_plan* p, spf_whatif_digest* d_out, spf_
   if (!p) return fail(nullptr, SPF_E_INVALID, "spf_whatif_changes: NULL plan");
   spf_ctx* c = p->ctx;
   p->has_lists = false;  // after a failed call the plan holds no lists
+  p->rt.valid = false;   // ... and the route lists were built from the old ones
   if (!c->loaded) return fail(c, SPF_E_STATE, "graph no longer loaded");
   if (p->epoch != c->epoch)
     return fail(c, SPF_E_STATE, "graph changed since the plan was created: recreate it");

@@ -367,6 +367,19 @@ WHATIF_KINDS = {"link": 0, "down": N.SPF_WHATIF_NODE_DOWN, "drain": N.SPF_WHATIF
                 "sets": N.SPF_WHATIF_LINK_SET, "metric": N.SPF_WHATIF_LINK_METRIC}
 
 
+def _flat_sets(sets) -> Tuple[np.ndarray, np.ndarray]:
+    """A sequence of sequences, or a 2-D array with one row per set, as
+    (ptr[n + 1], members[ptr[n]]) u32 arrays."""
+    if isinstance(sets, np.ndarray) and sets.ndim == 2:  # equal sizes: one row per set
+        ptr = (np.arange(len(sets) + 1, dtype=np.uint64) * sets.shape[1]).astype(np.uint32)
+        return ptr, np.ascontiguousarray(sets, np.uint32).reshape(-1)
+    members = [np.ascontiguousarray(s, np.uint32).reshape(-1) for s in sets]
+    ptr = np.zeros(len(members) + 1, np.uint32)
+    ptr[1:] = np.cumsum([len(m) for m in members])
+    flat = np.concatenate(members) if members else np.zeros(0, np.uint32)
+    return ptr, np.ascontiguousarray(flat, np.uint32)
+
+
 class WhatIfPlan(NativeHandle):
     """One source and a list of failures (``spf_whatif_plan``): single links
     (``kind == "link"``, ``links``), or nodes down / drained (``"down"`` /
@@ -415,20 +428,11 @@ class WhatIfPlan(NativeHandle):
     def _init_sets(self, eng: "SpfEngine", src: int, sets) -> None:
         if sets is None:
             raise ValueError("a set plan needs its sets")
-        if isinstance(sets, np.ndarray) and sets.ndim == 2:  # equal sizes: one row per set
-            members = sets
-            ptr = (np.arange(len(sets) + 1, dtype=np.uint64) * sets.shape[1]).astype(np.uint32)
-            flat = np.ascontiguousarray(sets, np.uint32).reshape(-1)
-        else:
-            members = [np.ascontiguousarray(s, np.uint32).reshape(-1) for s in sets]
-            ptr = np.zeros(len(members) + 1, np.uint32)
-            ptr[1:] = np.cumsum([len(m) for m in members])
-            flat = np.concatenate(members) if members else np.zeros(0, np.uint32)
-            flat = np.ascontiguousarray(flat, np.uint32)
+        ptr, flat = _flat_sets(sets)
         h = C.c_void_p()
         eng._err(N.lib.spf_whatif_plan_create_sets(eng._h, src, N.ptr(ptr),
                                                    N.ptr(flat) if len(flat) else None,
-                                                   len(members), C.byref(h)))
+                                                   len(ptr) - 1, C.byref(h)))
         self._adopt(h)
         self.n_fail = int(N.lib.spf_whatif_plan_failures(h))
         self.links = self.nodes = np.zeros(0, np.uint32)
@@ -546,6 +550,12 @@ class WhatIfChanges:
                                             N.ptr(nh), m, C.byref(n)))
         return node, dist, nh
 
+    def routes(self, sets, stream: int = 0) -> "WhatIfRoutes":
+        """Every failure's changed routes over the destination sets `sets`
+        (``spf_whatif_routes``): a sequence of sequences of node ids, or a
+        2-D array with one row per set."""
+        return WhatIfRoutes(self, sets, stream)
+
     def close(self) -> None:
         if self._own:
             self.plan.close()
@@ -556,6 +566,57 @@ class WhatIfChanges:
 
     def __exit__(self, *exc) -> None:
         self.close()
+
+
+class WhatIfRoutes:
+    """The route lists of one ``spf_whatif_routes`` call on the host: failure
+    i owns entries ``ptr[i] .. ptr[i + 1]`` of ``set`` / ``min_metric``
+    (``SPF_UNREACHABLE64``: withdrawn) / ``nh[:, W]`` in device order;
+    ``of(i)`` returns them ascending by set id.  ``base_metric[n_sets]`` /
+    ``base_nh[n_sets, W]`` are the sets' routes on the unfailed graph.  The
+    device arrays stay with the plan until its next ``routes()`` or
+    ``changes()``."""
+
+    def __init__(self, changes: WhatIfChanges, sets, stream: int = 0) -> None:
+        self.changes, self.plan = changes, changes.plan
+        eng, h = self.plan._eng, self.plan._h
+        self.set_ptr, self.set_nodes = _flat_sets(sets)
+        self.n_sets, self.n_fail, self.W = len(self.set_ptr) - 1, changes.n_fail, changes.W
+        n, nbytes, ms = C.c_uint64(), C.c_uint64(), C.c_double()
+        eng._err(N.lib.spf_whatif_routes(h, N.ptr(self.set_ptr),
+                                         N.ptr(self.set_nodes) if len(self.set_nodes) else None,
+                                         self.n_sets, C.byref(n), C.byref(nbytes), C.byref(ms),
+                                         C.c_void_p(stream) if stream else None))
+        self.n_entries, self.pool_bytes, self.kernel_ms = int(n.value), int(nbytes.value), ms.value
+        self.ptr = np.zeros(self.n_fail + 1, np.uint64)
+        self.set = np.zeros(self.n_entries, np.uint32)
+        self.min_metric = np.zeros(self.n_entries, np.uint64)
+        self.nh = np.zeros((self.n_entries, self.W), np.uint32)
+        eng._err(N.lib.spf_whatif_routes_read(h, N.ptr(self.ptr, C.c_uint64), N.ptr(self.set),
+                                              N.ptr(self.min_metric, C.c_uint64), N.ptr(self.nh)))
+        self.base_metric = np.zeros(self.n_sets, np.uint64)
+        self.base_nh = np.zeros((self.n_sets, self.W), np.uint32)
+        eng._err(N.lib.spf_whatif_routes_base(h, N.ptr(self.base_metric, C.c_uint64),
+                                              N.ptr(self.base_nh)))
+
+    def timing(self) -> Tuple[float, float, float, float]:
+        """(base routes + table, count, scan, fill) ms of the call."""
+        ms = (C.c_double * 4)()
+        self.plan._eng._err(N.lib.spf_whatif_routes_timing(self.plan._h, ms))
+        return ms[0], ms[1], ms[2], ms[3]
+
+    def of(self, i: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Failure i's (set[n], min_metric[n], nh[n, W]), ascending by set id."""
+        n = C.c_uint64()
+        err = self.plan._eng._err
+        err(N.lib.spf_whatif_routes_db(self.plan._h, i, None, None, None, 0, C.byref(n)))
+        m = int(n.value)
+        sets, metric = np.zeros(m, np.uint32), np.zeros(m, np.uint64)
+        nh = np.zeros((m, self.W), np.uint32)
+        if m:
+            err(N.lib.spf_whatif_routes_db(self.plan._h, i, N.ptr(sets), N.ptr(metric, C.c_uint64),
+                                           N.ptr(nh), m, C.byref(n)))
+        return sets, metric, nh
 
 
 class SpfEngine(NativeHandle):
@@ -802,6 +863,14 @@ class SpfEngine(NativeHandle):
         except BaseException:
             plan.close()
             raise
+
+    def whatif_routes(self, plan_or_changes, sets) -> WhatIfRoutes:
+        """Which routes of the plan's source each failure changes, over the
+        destination sets `sets` (``spf_whatif_routes``).  Takes a
+        ``WhatIfChanges``, or a ``WhatIfPlan`` of any kind, whose change lists
+        are then computed first (``result.changes``)."""
+        ch = plan_or_changes.changes() if isinstance(plan_or_changes, WhatIfPlan) else plan_or_changes
+        return ch.routes(sets)
 
     def whatif_node_plan(self, src: int, nodes: Optional[Sequence[int]] = None,
                          kind: str = "down") -> WhatIfPlan:
