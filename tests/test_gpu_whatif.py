@@ -79,6 +79,53 @@ def test_whatif_explicit_link_list_and_drained_source():
     assert [as_tuple(d) for d in got] == want
 
 
+def executed(plan):
+    """A plan's digests and its (hot, big) failure counts."""
+    from openr_amd.engine import DIGEST_DTYPE
+    from openr_amd.hiprt import DeviceArray, set_device
+
+    set_device(plan._eng.device)
+    d_out = DeviceArray(max(1, plan.n_fail), DIGEST_DTYPE)
+    try:
+        plan.execute(d_out.ptr)
+        stats = plan.stats()  # waits for the execute, checks the device's fault word
+        return d_out.numpy()[: plan.n_fail], stats
+    finally:
+        d_out.free()
+
+
+# the team environments of test_gpu_whatif_nodes.TEAMS: wave teams that
+# overflow, classified big failures on group teams, and on one-workgroup teams
+PROF_TEAMS = [("wavecap64", {"SPF_WHATIF_WAVECAP": "64"}),
+              ("classify16", {"SPF_WHATIF_CLASSIFY": "16"}),
+              ("classify16_one_workgroup", {"SPF_WHATIF_CLASSIFY": "16", "SPF_WHATIF_GROUP": "1"})]
+
+
+@pytest.mark.parametrize("env", [t[1] for t in PROF_TEAMS], ids=[t[0] for t in PROF_TEAMS])
+def test_profiled_link_instances_equal_the_production_ones(monkeypatch, env):
+    """SPF_WHATIF_PROF (read at plan creation) selects the link plans' PROF 1 /
+    PROF 2 instances of the three repair kernels: the digests of every link of
+    ba1500 equal the unprofiled plan's on every team path.  Node plans have no
+    profiled instances and ignore the variable."""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    monkeypatch.delenv("SPF_WHATIF_PROF", raising=False)
+    ls, names, eng, orc, _ = setup(SMALL[0][1]())
+    s = names.index(SMALL[0][2])
+    want, (hot, big) = executed(eng.whatif_plan(s))
+    print(f"{env}: {len(want)} links, {hot} hot, {big} big")
+    assert hot > big > 0  # repairs by wave teams and by workgroup teams
+    nodes, want_down, _ = eng.whatif_nodes(s, kind="down")
+    for mode in ("1", "global"):
+        monkeypatch.setenv("SPF_WHATIF_PROF", mode)
+        got, stats = executed(eng.whatif_plan(s))
+        assert stats == (hot, big)
+        assert np.array_equal(got, want), mode
+    monkeypatch.setenv("SPF_WHATIF_PROF", "1")
+    nodes1, got_down, _ = eng.whatif_nodes(s, kind="down")
+    assert np.array_equal(nodes1, nodes) and np.array_equal(got_down, want_down)
+
+
 WIDE = [
     # U[1, 1000] metrics on a 3000-node WAN: the big repairs hold far more than
     # kDialLevels (1024) distinct distances, so the workgroup teams leave the
