@@ -784,6 +784,95 @@ spf_status spf_whatif_routes_buffers(spf_whatif_plan* plan, const uint64_t** d_p
 /* ms[4] = base routes + table, count pass, scan, fill pass of the last
  * spf_whatif_routes. */
 spf_status spf_whatif_routes_timing(const spf_whatif_plan* plan, double* ms);
+/* ---- what-if impact by destination: the lists above, keyed by what is hit.
+ * The change and route lists are keyed by the failure.  "Which failures touch
+ * node v (or prefix s), which of them cut it off, which is the worst and how
+ * narrow does its ECMP get" is keyed by the destination: the resident lists
+ * transposed on the device, and a summary per key.  Keys are nodes over the
+ * change lists (spf_whatif_by_node: n_keys = n_nodes, base = what
+ * spf_whatif_base returns) and set ids over the route lists
+ * (spf_whatif_by_set: n_keys = the n_sets of the last spf_whatif_routes, base =
+ * spf_whatif_routes_base).  An "entry of key k" is a list entry whose node /
+ * set is k; a plan that lists a failure twice gives k two entries. */
+#define SPF_WHATIF_NONE 0xFFFFFFFFu
+#define SPF_WHATIF_BY_NODE 0u /* `which` of spf_whatif_impact_timing */
+#define SPF_WHATIF_BY_SET 1u
+typedef struct spf_whatif_impact { /* 32 bytes, one per key (node or set) */
+  uint32_t n_changed;     /* failures of the plan whose list holds the key            */
+  uint32_t n_unreachable; /* ... with the new metric UINT64_MAX (cut off / withdrawn) */
+  uint32_t n_metric;      /* ... with the new metric != the base metric (incl. those) */
+  uint32_t min_width;     /* smallest popcount of the next-hop words over the key's
+                             entries with a finite metric; the base popcount when none */
+  uint64_t max_metric;    /* max(base metric, largest finite new metric of an entry)  */
+  uint32_t max_fail;      /* smallest failure index i whose entry has that metric, when
+                             it is > the base metric; SPF_WHATIF_NONE otherwise        */
+  uint32_t reserved;      /* 0 */
+} spf_whatif_impact;
+/* One exactly sized set per plan and flavour, on the device until the next
+ * call of that flavour:
+ *   tptr[n_keys + 1]   u64  key k owns transposed entries tptr[k] .. tptr[k + 1]
+ *   tfail[total]       u32  the failure index i
+ *   tent[total]        u64  the index e of that entry in the list pools, so a
+ *                           consumer reads cdist[e] and cnh[e * W] (rmetric[e],
+ *                           rnh[e * W]) without a search
+ *   imp[n_keys]             the summaries
+ * total equals the lists' n_entries.  *pool_bytes = 8 (n_keys + 1) + 12 total +
+ * 32 n_keys, *kernel_ms = the three phases of spf_whatif_impact_timing
+ * together; the outputs are optional.  The order of a key's entries on the
+ * device is unspecified (the _db calls sort).  A key with no entry -- by set:
+ * also the sets never listed, empty, holding src or unreachable in the base --
+ * has n_* = 0, min_width = the base popcount, max_metric = the base metric
+ * (UINT64_MAX when unreachable in the base) and max_fail = SPF_WHATIF_NONE.
+ * Zero entries (or zero keys) is allowed.
+ *
+ * Device-side consumers of the resident lists, as spf_whatif_routes is: they
+ * read only the lists and the base, and so work on every plan kind and on link
+ * plans on exact-path graphs.  Built as the lists are: the summaries start as
+ * the base; a count pass with a lane per entry adds to the three counts, takes
+ * the 64-bit max of the finite metrics and the min of their popcounts (device-
+ * scope atomics); the change lists' scan turns n_changed into tptr; a fill pass
+ * finds each entry's failure by bisecting cptr / rptr and places (i, e) at
+ * tptr[k] + a per-key cursor.  No buffer is n_fail x n_keys.  Waits.
+ * SPF_E_INVALID: a NULL plan.  SPF_E_STATE: the plan holds no change lists
+ * (by_node) or no route lists (by_set: spf_whatif_routes first); the graph
+ * changed since the plan was created.  SPF_E_NOMEM: the pools do not fit.
+ * SPF_E_HIP: an entry placed past its key's count is dropped, as in the lists.
+ * After a failed call the plan holds none of that flavour; a new
+ * spf_whatif_changes invalidates both flavours, a new spf_whatif_routes by_set. */
+spf_status spf_whatif_by_node(spf_whatif_plan* plan, uint64_t* n_entries, uint64_t* pool_bytes,
+                              double* kernel_ms, void* stream);
+spf_status spf_whatif_by_set(spf_whatif_plan* plan, uint64_t* n_entries, uint64_t* pool_bytes,
+                             double* kernel_ms, void* stream);
+/* The summaries: out[n_keys], may be NULL.  This and the calls below:
+ * SPF_E_STATE before a successful spf_whatif_by_node / _by_set. */
+spf_status spf_whatif_by_node_impact(spf_whatif_plan* plan, spf_whatif_impact* out);
+spf_status spf_whatif_by_set_impact(spf_whatif_plan* plan, spf_whatif_impact* out);
+/* Key `key`'s entries, ascending by failure index (sorted on the host): *n of
+ * them; fail[cap], ent[cap] are filled when cap >= *n, SPF_E_NOMEM (with *n
+ * set) otherwise.  Every output may be NULL.  SPF_E_INVALID: key >= n_keys. */
+spf_status spf_whatif_by_node_db(spf_whatif_plan* plan, uint32_t key, uint32_t* fail, uint64_t* ent,
+                                 uint64_t cap, uint64_t* n);
+spf_status spf_whatif_by_set_db(spf_whatif_plan* plan, uint32_t key, uint32_t* fail, uint64_t* ent,
+                                uint64_t cap, uint64_t* n);
+/* The whole set in one copy per array, in device order: ptr[n_keys + 1],
+ * fail[total], ent[total], imp[n_keys].  Every output may be NULL. */
+spf_status spf_whatif_by_node_read(spf_whatif_plan* plan, uint64_t* ptr, uint32_t* fail, uint64_t* ent,
+                                   spf_whatif_impact* imp);
+spf_status spf_whatif_by_set_read(spf_whatif_plan* plan, uint64_t* ptr, uint32_t* fail, uint64_t* ent,
+                                  spf_whatif_impact* imp);
+/* The device arrays, for device-side consumers (valid until the next call of
+ * the flavour or of what invalidates it); every output may be NULL. */
+spf_status spf_whatif_by_node_buffers(spf_whatif_plan* plan, const uint64_t** d_ptr,
+                                      const uint32_t** d_fail, const uint64_t** d_ent,
+                                      const spf_whatif_impact** d_imp, uint32_t* n_keys,
+                                      uint64_t* n_entries);
+spf_status spf_whatif_by_set_buffers(spf_whatif_plan* plan, const uint64_t** d_ptr,
+                                     const uint32_t** d_fail, const uint64_t** d_ent,
+                                     const spf_whatif_impact** d_imp, uint32_t* n_keys,
+                                     uint64_t* n_entries);
+/* ms[3] = count pass (with the summaries' initialisation), scan, fill pass of
+ * the last spf_whatif_by_node (which = SPF_WHATIF_BY_NODE) or _by_set. */
+spf_status spf_whatif_impact_timing(const spf_whatif_plan* plan, uint32_t which, double* ms);
 /* Convenience: plan + execute + copy back. out = [n_fail] (n_fail = number of
  * up links when fail_links is NULL), base may be NULL. */
 spf_status spf_whatif_solve(spf_ctx* ctx, uint32_t src, const uint32_t* fail_links,

@@ -286,6 +286,16 @@ PROTOTYPES = {
     "spf_whatif_routes_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
                                             C.POINTER(_vp), _u32p, _u64p]),
     "spf_whatif_routes_timing": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "spf_whatif_impact_timing": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_double)]),
+    **{f"spf_whatif_by_{flavour}{call}": (C.c_int, list(args))
+       for flavour in ("node", "set")
+       for call, args in (
+           ("", (_vp, _u64p, _u64p, C.POINTER(C.c_double), _vp)),
+           ("_impact", (_vp, _vp)),
+           ("_db", (_vp, C.c_uint32, _u32p, _u64p, C.c_uint64, _u64p)),
+           ("_read", (_vp, _u64p, _u32p, _u64p, _vp)),
+           ("_buffers", (_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _u32p,
+                         _u64p)))},
     "spf_routes": (C.c_int, [_vp, C.c_uint32, _u32p, _u32p, C.c_uint32, C.c_uint32, _u64p,
                              _u32p, _u32p, _u64p]),
     # multi-device context (openr_spf.h)

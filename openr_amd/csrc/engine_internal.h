@@ -157,13 +157,34 @@ struct WiRoutes {
   }
 };
 
-// What whatif_routes.hip reads of a plan (whatif.hip owns spf_whatif_plan):
-// the lists of the last spf_whatif_changes, the unfailed result as the plan
-// holds it (u32 metrics with kInf and rows that are undefined where
-// unreachable, or the exact plan's u64 ones), and the plan's route lists.
+// Impact by destination (spf_whatif_by_node / spf_whatif_by_set,
+// whatif_impact.hip): the change or route lists transposed to key-major and
+// every key's summary, in exactly sized pools (kept while they are large
+// enough).  A plan holds one per flavour.
+struct WiImpact {
+  bool valid = false;  // a call succeeded; its lists were not rebuilt, no failed call since
+  uint32_t n_keys = 0;
+  uint64_t total = 0;
+  double ms[3] = {0, 0, 0};  // count (with init), scan, fill of the last call
+  DevBuf<unsigned long long> d_tptr, d_tent;  // [n_keys + 1], [total]
+  DevBuf<uint32_t> d_tfail, d_cur;            // [total]; [n_keys] fill cursors
+  DevBuf<spf_whatif_impact> d_imp;            // [n_keys]
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  ~WiImpact() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+// What whatif_routes.hip and whatif_impact.hip read of a plan (whatif.hip owns
+// spf_whatif_plan): the lists of the last spf_whatif_changes, the unfailed
+// result as the plan holds it (u32 metrics with kInf and rows that are
+// undefined where unreachable, or the exact plan's u64 ones), the plan's route
+// lists and its two transpositions.
 struct WiListsView {
   spf_ctx* ctx = nullptr;
   WiRoutes* rt = nullptr;
+  WiImpact* imp[2] = {nullptr, nullptr};  // SPF_WHATIF_BY_NODE, SPF_WHATIF_BY_SET
   bool has_lists = false, no_nbr = false;  // no_nbr: src has no up neighbour (rows undefined)
   uint64_t epoch = 0, total = 0;
   uint32_t src = 0, n_fail = 0, W = 1;
@@ -497,9 +518,15 @@ spf_status launch_exact(spf_ctx* c, ExactScratch* x, const uint32_t* d_srcs, uin
                         const uint64_t* d_nh_off, uint32_t Wmax, bool hop, bool dist64,
                         const uint32_t* ign, void* d_dist, uint32_t* d_nh, uint32_t* d_pop,
                         hipStream_t s);
-// A what-if plan's lists, base and route-list state (whatif.hip), for
-// spf_whatif_routes (whatif_routes.hip); p is not NULL.
+// A what-if plan's lists, base, route-list and impact state (whatif.hip), for
+// spf_whatif_routes (whatif_routes.hip) and spf_whatif_by_node / _by_set
+// (whatif_impact.hip); p is not NULL.
 void whatif_lists_view(spf_whatif_plan* p, WiListsView* v);
+// The change lists' scan (whatif_scan_kernel, whatif.hip) on `s`: ptr[0 .. n]
+// = the exclusive scan of cnt[0], cnt[stride], ... (n counts) and the total.
+// stride is 1 (a plain array) or 8 (spf_whatif_impact::n_changed).
+hipError_t whatif_scan(const uint32_t* cnt, uint32_t stride, uint32_t n, unsigned long long* ptr,
+                       hipStream_t s);
 // spf_big_kernel (whatif.hip): the plan's sources one after another on the
 // whole chip -- frontier SSSP into the dist rows, next hops in distance
 // order, transposed into the plan's bitmaps.  Positive metrics or hop counts.

@@ -790,8 +790,11 @@ __global__ void classify_kernel(WiGraph g, const uint32_t* __restrict__ dist,
 // cptr[0 .. n] = exclusive scan of the failures' entry counts, cptr[n] the
 // total: one workgroup, 8 counts per thread and tile, the per-thread sums
 // scanned with the DPP wave scans (a sum < 2^35 as two words of 24 and 11
-// bits: 64 of either stay below 2^32), u64 offsets.
+// bits: 64 of either stay below 2^32), u64 offsets.  Count t is cnt[t *
+// STRIDE]: 1 for the lists' own arrays, 8 for the counts inside the impact
+// summaries (spfi::whatif_scan).
 constexpr uint32_t kListScanPer = 8;
+template <uint32_t STRIDE>
 __global__ __launch_bounds__(1024) void whatif_scan_kernel(const uint32_t* __restrict__ cnt,
                                                            uint32_t n,
                                                            unsigned long long* __restrict__ cptr) {
@@ -804,7 +807,7 @@ __global__ __launch_bounds__(1024) void whatif_scan_kernel(const uint32_t* __res
     unsigned long long sum = 0;
 #pragma unroll
     for (uint32_t j = 0; j < kListScanPer; ++j) {
-      x[j] = b + j < n ? cnt[b + j] : 0u;
+      x[j] = b + j < n ? cnt[(b + j) * STRIDE] : 0u;
       sum += x[j];
     }
     uint32_t tl = 0, th = 0;
@@ -853,10 +856,20 @@ hipError_t launch_resident(const void* kernel, uint32_t blocks, uint32_t threads
   return hipLaunchKernel(kernel, dim3(blocks), dim3(threads), args, 0, s);
 }
 
+hipError_t whatif_scan(const uint32_t* cnt, uint32_t stride, uint32_t n, unsigned long long* ptr,
+                       hipStream_t s) {
+  if (stride == 1) hipLaunchKernelGGL(whatif_scan_kernel<1>, dim3(1), dim3(1024), 0, s, cnt, n, ptr);
+  else if (stride == 8) hipLaunchKernelGGL(whatif_scan_kernel<8>, dim3(1), dim3(1024), 0, s, cnt, n, ptr);
+  else return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
 void whatif_lists_view(spf_whatif_plan* p, WiListsView* v) {
   const spf_ctx* c = p->ctx;
   v->ctx = p->ctx;
   v->rt = &p->rt;
+  v->imp[SPF_WHATIF_BY_NODE] = &p->imp_node;
+  v->imp[SPF_WHATIF_BY_SET] = &p->imp_set;
   v->has_lists = p->has_lists;
   v->no_nbr = p->src + 1 < c->nb_ptr.size() && c->nb_ptr[p->src + 1] == c->nb_ptr[p->src];
   v->epoch = p->epoch;
@@ -1315,6 +1328,7 @@ spf_status spf_whatif_changes(spf_whatif_plan* p, spf_whatif_digest* d_out, spf_
   spf_ctx* c = p->ctx;
   p->has_lists = false;  // after a failed call the plan holds no lists
   p->rt.valid = false;   // ... and the route lists were built from the old ones
+  p->imp_node.valid = p->imp_set.valid = false;  // ... as were the transpositions
   if (!c->loaded) return fail(c, SPF_E_STATE, "graph no longer loaded");
   if (p->epoch != c->epoch)
     return fail(c, SPF_E_STATE, "graph changed since the plan was created: recreate it");
@@ -1349,8 +1363,7 @@ spf_status spf_whatif_changes(spf_whatif_plan* p, spf_whatif_digest* d_out, spf_
   HIP_TRY(c, hipEventRecord(p->l_ev[0], s));
   if (const spf_status st = pass(true); st != SPF_OK) return st;
   HIP_TRY(c, hipEventRecord(p->l_ev[1], s));
-  hipLaunchKernelGGL(whatif_scan_kernel, dim3(1), dim3(1024), 0, s, p->l_cnt.p, nf, p->l_ptr.p);
-  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, whatif_scan(p->l_cnt.p, 1, nf, p->l_ptr.p, s));
   HIP_TRY(c, hipEventRecord(p->l_ev[2], s));
   // the pools are sized from the scan's total
   unsigned long long total = 0;

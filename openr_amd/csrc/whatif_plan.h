@@ -3,8 +3,8 @@
 //  what whatif.hip builds and launches for all of them, and the one launch
 //  path of a plan's failures, run_failures<K>, over a kind description K.
 //  Included by the kinds' units only (whatif.hip, whatif_nodes.hip,
-//  whatif_sets.hip, whatif_metrics.hip); whatif_routes.hip reads a plan through
-//  whatif_lists_view.
+//  whatif_sets.hip, whatif_metrics.hip); whatif_routes.hip and
+//  whatif_impact.hip read a plan through whatif_lists_view.
 // ============================================================================
 #ifndef OPENR_AMD_WHATIF_PLAN_H
 #define OPENR_AMD_WHATIF_PLAN_H
@@ -76,6 +76,10 @@ struct spf_whatif_plan {
   // route lists of the last spf_whatif_routes (whatif_routes.hip), a consumer
   // of the lists above: spf_whatif_changes invalidates them
   spfi::WiRoutes rt;
+  // the lists transposed to destination-major with every destination's summary
+  // (whatif_impact.hip): imp_node over the change lists, imp_set over the route
+  // lists; spf_whatif_changes invalidates both, spf_whatif_routes imp_set
+  spfi::WiImpact imp_node, imp_set;
   ~spf_whatif_plan() {
     for (hipEvent_t e : ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : l_ev)

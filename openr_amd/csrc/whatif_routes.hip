@@ -33,6 +33,7 @@
 // ============================================================================
 #include "engine_internal.h"
 #include "wave_ops.h"
+#include "whatif_owner.h"
 #include "whatif_routes_host.h"
 
 #include <numeric>
@@ -125,13 +126,7 @@ __global__ __launch_bounds__(kThreads) void wr_table_kernel(
     uint32_t* __restrict__ efail) {
   const unsigned long long e = (unsigned long long)blockIdx.x * kThreads + threadIdx.x;
   if (e >= total) return;
-  // the failure that owns entry e: the last i with cptr[i] <= e (cold failures own nothing)
-  uint32_t lo = 0, hi = n_fail;
-  while (hi - lo > 1) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (cptr[mid] <= e) lo = mid;
-    else hi = mid;
-  }
+  const uint32_t lo = list_owner(cptr, n_fail, e);
   efail[e] = lo;
   const unsigned long long key = ((unsigned long long)lo << 32) | cnode[e];
   for (uint32_t h = wr_hash(key) & mask;; h = (h + 1) & mask) {
@@ -367,6 +362,7 @@ spf_status spf_whatif_routes(spf_whatif_plan* p, const uint32_t* set_ptr, const 
   spf_ctx* c = v.ctx;
   WiRoutes& r = *v.rt;
   r.valid = false;  // after a failed call the plan holds no route lists
+  v.imp[SPF_WHATIF_BY_SET]->valid = false;  // ... and none transposed from the old ones
   if (const char* why = route_sets_check(c->N, set_ptr, set_nodes, n_sets))
     return fail(c, SPF_E_INVALID, "spf_whatif_routes: %s", why);
   if (!c->loaded) return fail(c, SPF_E_STATE, "graph no longer loaded");

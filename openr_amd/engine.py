@@ -361,6 +361,10 @@ class Ksp2Routes:
 
 DIGEST_DTYPE =np.dtype([("n_dist_changed", "<u4"), ("n_nh_changed", "<u4"),
                          ("hash", "<u8")])  # spf_whatif_digest
+IMPACT_DTYPE = np.dtype([("n_changed", "<u4"), ("n_unreachable", "<u4"), ("n_metric", "<u4"),
+                         ("min_width", "<u4"), ("max_metric", "<u8"), ("max_fail", "<u4"),
+                         ("reserved", "<u4")])  # spf_whatif_impact
+WHATIF_NONE = 0xFFFFFFFF  # SPF_WHATIF_NONE
 
 
 WHATIF_KINDS = {"link": 0, "down": N.SPF_WHATIF_NODE_DOWN, "drain": N.SPF_WHATIF_NODE_DRAIN,
@@ -556,6 +560,11 @@ class WhatIfChanges:
         2-D array with one row per set."""
         return WhatIfRoutes(self, sets, stream)
 
+    def by_node(self, stream: int = 0) -> "WhatIfImpact":
+        """These lists by destination node (``spf_whatif_by_node``): per node
+        the failures that list it and its summary."""
+        return WhatIfImpact(self.plan, "node", stream)
+
     def close(self) -> None:
         if self._own:
             self.plan.close()
@@ -617,6 +626,60 @@ class WhatIfRoutes:
             err(N.lib.spf_whatif_routes_db(self.plan._h, i, N.ptr(sets), N.ptr(metric, C.c_uint64),
                                            N.ptr(nh), m, C.byref(n)))
         return sets, metric, nh
+
+    def by_set(self, stream: int = 0) -> "WhatIfImpact":
+        """These lists by destination set (``spf_whatif_by_set``): per set the
+        failures that list it and its summary."""
+        return WhatIfImpact(self.plan, "set", stream)
+
+
+class WhatIfImpact:
+    """A plan's change lists by node (``flavour == "node"``) or its route lists
+    by set (``"set"``), on the host: key k owns transposed entries ``ptr[k] ..
+    ptr[k + 1]`` of ``fail`` (the failure index) / ``ent`` (the index of that
+    entry in the lists' pools: ``changes.dist[e]``, ``routes.min_metric[e]``) in
+    device order; ``of(k)`` returns them ascending by failure.  ``impact`` holds
+    the summaries (``IMPACT_DTYPE``, one per key).  The device arrays stay with
+    the plan until its next call of the flavour, ``changes()`` or, by set,
+    ``routes()``."""
+
+    def __init__(self, plan: "WhatIfPlan", flavour: str, stream: int = 0) -> None:
+        if flavour not in ("node", "set"):
+            raise ValueError(f"impact flavour {flavour!r}: 'node' or 'set'")
+        self.plan, self.flavour = plan, flavour
+        eng, h = plan._eng, plan._h
+        self._call = lambda name: getattr(N.lib, f"spf_whatif_by_{flavour}{name}")
+        n, nbytes, ms = C.c_uint64(), C.c_uint64(), C.c_double()
+        eng._err(self._call("")(h, C.byref(n), C.byref(nbytes), C.byref(ms),
+                                C.c_void_p(stream) if stream else None))
+        self.n_entries, self.pool_bytes, self.kernel_ms = int(n.value), int(nbytes.value), ms.value
+        k = C.c_uint32()
+        eng._err(self._call("_buffers")(h, None, None, None, None, C.byref(k), None))
+        self.n_keys = int(k.value)
+        self.ptr = np.zeros(self.n_keys + 1, np.uint64)
+        self.fail = np.zeros(self.n_entries, np.uint32)
+        self.ent = np.zeros(self.n_entries, np.uint64)
+        self.impact = np.zeros(self.n_keys, IMPACT_DTYPE)
+        eng._err(self._call("_read")(h, N.ptr(self.ptr, C.c_uint64), N.ptr(self.fail),
+                                     N.ptr(self.ent, C.c_uint64), C.c_void_p(self.impact.ctypes.data)))
+
+    def timing(self) -> Tuple[float, float, float]:
+        """(count, scan, fill) ms of the call."""
+        ms = (C.c_double * 3)()
+        which = 0 if self.flavour == "node" else 1
+        self.plan._eng._err(N.lib.spf_whatif_impact_timing(self.plan._h, which, ms))
+        return ms[0], ms[1], ms[2]
+
+    def of(self, key: int) -> Tuple[np.ndarray, np.ndarray]:
+        """Key `key`'s (fail[n], ent[n]), ascending by failure index."""
+        n = C.c_uint64()
+        err = self.plan._eng._err
+        err(self._call("_db")(self.plan._h, key, None, None, 0, C.byref(n)))
+        m = int(n.value)
+        fail, ent = np.zeros(m, np.uint32), np.zeros(m, np.uint64)
+        if m:
+            err(self._call("_db")(self.plan._h, key, N.ptr(fail), N.ptr(ent, C.c_uint64), m, C.byref(n)))
+        return fail, ent
 
 
 class SpfEngine(NativeHandle):
@@ -871,6 +934,14 @@ class SpfEngine(NativeHandle):
         are then computed first (``result.changes``)."""
         ch = plan_or_changes.changes() if isinstance(plan_or_changes, WhatIfPlan) else plan_or_changes
         return ch.routes(sets)
+
+    def whatif_impact(self, changes_or_routes) -> WhatIfImpact:
+        """The lists of a ``WhatIfChanges`` by node, or of a ``WhatIfRoutes`` by
+        set: per destination the failures that touch it and its summary
+        (``spf_whatif_by_node`` / ``spf_whatif_by_set``)."""
+        if isinstance(changes_or_routes, WhatIfRoutes):
+            return changes_or_routes.by_set()
+        return changes_or_routes.by_node()
 
     def whatif_node_plan(self, src: int, nodes: Optional[Sequence[int]] = None,
                          kind: str = "down") -> WhatIfPlan:
