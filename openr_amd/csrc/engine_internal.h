@@ -3,7 +3,8 @@
 //  context (the graph's host state of graph_host.h plus its device copy and
 //  the kernels' scratch), the plans (their host tables derived by
 //  plan_host.h), and the launch functions each unit offers the others
-//  (graph.cpp: the spf_graph_* calls; spf_engine.hip: SPF/ECMP plans;
+//  (graph.cpp: the spf_graph_* calls; engine_ctx.cpp: the context;
+//  spf_engine.hip: SPF/ECMP plans over the kernel units of spf_units.h;
 //  ksp2.hip: batched KSP2; ...).  Not part of the C-ABI:
 //  include/openr_spf.h is the boundary.
 // ============================================================================
@@ -510,7 +511,8 @@ spf_status exact_whatif_prepare(spf_ctx* c, ExactWhatIf* x, uint32_t src,
 // base_run false skips the unfailed run (the fill pass: base_* are there).
 spf_status exact_whatif_launch(spf_ctx* c, ExactWhatIf* x, spf_whatif_digest* d_out,
                                spf_whatif_digest* d_base, hipStream_t s, hipEvent_t mid,
-                               const WiEmit* em = nullptr, bool base_run = true);spf_status exact_ksp2_prepare(spf_ctx* c, ExactKsp2* x, const std::vector<uint32_t>& srcs);
+                               const WiEmit* em = nullptr, bool base_run = true);
+spf_status exact_ksp2_prepare(spf_ctx* c, ExactKsp2* x, const std::vector<uint32_t>& srcs);
 spf_status exact_ksp2_launch(spf_ctx* c, ExactKsp2* x, spf_ksp2_pair* d_pairs, uint32_t* d_pool,
                              uint64_t pool_words, uint64_t* d_counters, hipStream_t s,
                              hipEvent_t mid);
@@ -532,11 +534,12 @@ hipError_t whatif_scan(const uint32_t* cnt, uint32_t stride, uint32_t n, unsigne
 // order, transposed into the plan's bitmaps.  Positive metrics or hop counts.
 spf_status launch_big(spf_ctx* c, spf_plan* p, uint32_t* d_dist, uint32_t* d_nh, bool hop,
                       hipStream_t s);
-// Raise the dynamic-LDS limit of the engine's LDS-resident kernels.
+// Raise the dynamic-LDS limit of the engine's LDS-resident kernels (once per
+// process; each unit registers its own, spf_units.h).
 spf_status set_lds_limits(spf_ctx* c);
 // msbfs_kernel's twin-class quotient: its tables rebuilt and uploaded when
 // stale (graph.cpp); whether the BFS sweeps it, and whether the register-plane
-// BFS runs instead (spf_engine.hip, with the kernels)
+// BFS runs instead (msbfs.hip, with the kernels)
 spf_status quotient_prepare(spf_ctx* c);
 bool use_quotient(const spf_ctx* c);
 bool use_planes(const spf_ctx* c);

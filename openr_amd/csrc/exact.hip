@@ -1,8 +1,8 @@
 // ============================================================================
 //  exact.hip -- the exact-envelope SPF kernel: LinkState::runSpf
 //  (openr/decision/LinkState.cpp:808-882) replayed step for step, one
-//  wavefront per source, for the inputs the data-parallel kernels of
-//  spf_engine.hip do not cover:
+//  wavefront per source, for the inputs the data-parallel kernels (sssp.hip,
+//  msbfs.hip, mssp.hip with ecmp.hip's next-hop pass) do not cover:
 //    * zero-metric links: next-hop sets then depend on the heap's pop order
 //      among equal-metric nodes (LinkState.h:488-498), which this kernel
 //      reproduces exactly -- (metric, node id) with ids ascending by name;

@@ -24,12 +24,33 @@ constexpr uint32_t kSliceW = 64;  // nodes per sliced-ELL slice (= wave width)
 constexpr uint32_t kNoSlice = 0x03FFFFFFu;  // unused slot: its nodes (kNoSlice * 64 + lane) lie past N
 constexpr uint32_t kQChunk = 8;  // columns per chunk of a quotient row
 
-// owned slots per thread of msbfs_kernel (the template instances: 1, 2, 4, 8,
-// 10, 12, 16) for an N-node graph
-inline uint32_t ms_own(uint32_t N) {
+// The owned-slot counts the multi-source BFS kernels are instantiated for,
+// ascending, the last one kMsMaxOwn.  This list is the only place they are
+// written: ms_own's bands below and the kernels' instance tables (msbfs.hip:
+// one row per entry, which the launches and the LDS-limit registration both
+// walk) are generated from it.
+#define SPF_MS_OWNS(X) X(1) X(2) X(4) X(8) X(10) X(12) X(16)
+
+// owned slots per thread of msbfs_kernel for an N-node graph: the smallest
+// instance that holds ceil(N / kMsThreads) slots
+constexpr uint32_t ms_own(uint32_t N) {
   const uint32_t own = (N + kMsThreads - 1) / kMsThreads;
-  return own <= 1 ? 1 : own <= 2 ? 2 : own <= 4 ? 4 : own <= 8 ? 8 : own <= 10 ? 10 : own <= 12 ? 12 : 16;
+#define SPF_MS_BAND(o) \
+  if (own <= o) return o;
+  SPF_MS_OWNS(SPF_MS_BAND)
+#undef SPF_MS_BAND
+  return kMsMaxOwn;
 }
+#define SPF_MS_OWN_ENTRY(o) o,
+constexpr uint32_t kMsOwns[] = {SPF_MS_OWNS(SPF_MS_OWN_ENTRY)};
+#undef SPF_MS_OWN_ENTRY
+constexpr bool ms_owns_sound() {
+  constexpr uint32_t n = sizeof kMsOwns / sizeof kMsOwns[0];
+  for (uint32_t i = 1; i < n; ++i)
+    if (kMsOwns[i - 1] >= kMsOwns[i]) return false;
+  return kMsOwns[0] >= 1 && kMsOwns[n - 1] == kMsMaxOwn;
+}
+static_assert(ms_owns_sound(), "SPF_MS_OWNS: ascending, ending with kMsMaxOwn");
 
 // Does a largest metric `m` on an N-node graph leave 32-bit distances (the
 // bound argued at metric_flags; what-if metric changes are held to it too)

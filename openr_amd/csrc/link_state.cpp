@@ -12,7 +12,8 @@
 //     reference's Dijkstra uses to order parallel links in pathLinks -- is
 //     reproduced; the CSR lists each node's edges in that order.
 //   * Shortest paths: flatten the up links into a CSR once per topology
-//     version and run every SPF on the MI355X engine (spf_engine.hip).  Results
+//     version and run every SPF on the MI355X engine (spf_engine.hip's plans
+//     over the kernel units of spf_units.h).  Results
 //     are memoised per (node, useLinkMetric) and per (src, dst, k) and
 //     invalidated on topology changes, as LinkState.h:271-301 does.
 // ============================================================================

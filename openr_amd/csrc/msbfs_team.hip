@@ -4,7 +4,7 @@
 //  workgroups on one XCD, each owning 1/G of the graph's 64-node slices.
 //
 //  Reference: LinkState::runSpf (openr/decision/LinkState.cpp:808-882) with
-//  unit metrics; same result as msbfs_kernel (spf_engine.hip): per node a
+//  unit metrics; same result as msbfs_kernel (msbfs.hip): per node a
 //  64-bit mask (bit = source of the batch), a level = one pull sweep
 //  new(v) = OR_{u in N(v)} F(u) & ~visited(v), drained nodes record but
 //  expand only as their own source (:831-838).

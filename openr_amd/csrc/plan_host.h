@@ -16,7 +16,8 @@
 
 namespace spfi {
 
-// shared with the kernels of spf_engine.hip
+// shared with the next-hop kernels (ecmp.hip) and the class-row expansion
+// (class_rows.hip)
 constexpr uint32_t kEcmpRunsPerXcd = 64;  // source runs dealt to each XCD
 constexpr uint32_t kSlSlots = 8;     // plane slots per word of a sliced row
 constexpr uint32_t kSlSat = 254;     // maxd at which the u8 copy saturates

@@ -1,4 +1,5 @@
-// Wave-wide scans and reductions with DPP moves (shared by the BFS kernels).
+// Wave-wide scans and reductions with DPP moves (shared by the BFS kernels),
+// and the device one-liners several units' kernels share.
 //
 // row_shr 1/2/4/8 inside each 16-lane row (lanes shifted in from outside the
 // row read 0 -- the identity of +, | and max over unsigned values), then
@@ -40,6 +41,14 @@ __device__ __forceinline__ uint32_t wave_max32(uint32_t x) {
 }
 __device__ __forceinline__ uint64_t wave_or64(uint64_t x) {
   return ((uint64_t)wave_or32((uint32_t)(x >> 32)) << 32) | wave_or32((uint32_t)x);
+}
+
+// One-liners more than one unit's kernels use.
+__device__ __forceinline__ uint32_t lane_id() { return __lane_id(); }
+
+// bit l of an ignore set (undirected link ids, upload_ignore's bitmap)
+__device__ __forceinline__ bool link_ignored(const uint32_t* ign, uint32_t l) {
+  return (ign[l >> 5] >> (l & 31)) & 1u;
 }
 
 }  // namespace spfi

@@ -304,3 +304,63 @@ def test_weighted_sliced_next_hops(name, make, monkeypatch):
     plan = eng.plan(list(range(len(names))))
     assert plan.kernels()[0] == "mssp_kernel" and plan.row_mode() == "sliced"
     compare(names, eng, orc, list(range(len(names))))
+
+
+def quotient_in_use(eng):
+    import ctypes as C
+
+    from openr_amd import _native as N
+
+    n_cls, n_edge, used = C.c_uint32(), C.c_uint64(), C.c_uint32()
+    eng._err(N.lib.spf_graph_quotient(eng._h, C.byref(n_cls), C.byref(n_edge), C.byref(used)))
+    return bool(used.value)
+
+
+# (graph, SPF_MSBFS, expected kernel, quotient sweep): node counts in the
+# owned-slot bands no other test reaches (OWN = ceil(N / 1024) rounded up to
+# the next template instance)
+BANDS = [
+    ("grid50", lambda: T.grid(50), "masks", False),       # 2,500 nodes: OWN 4, columns in LDS
+    ("grid70", lambda: T.grid(70), "masks", False),       # 4,900 nodes: OWN 8, columns in LDS
+    ("grid105", lambda: T.grid(105), "masks", False),     # 11,025 nodes: OWN 12, columns from L2
+    ("grid115", lambda: T.grid(115), "masks", False),     # 13,225 nodes: OWN 16
+    ("grid50", lambda: T.grid(50), "planes", False),      # planes need N <= 10,240
+    ("grid70", lambda: T.grid(70), "planes", False),
+    ("fabric3000", lambda: T.fabric(3000, full=True), "masks", True),  # 2,976 nodes: OWN 4
+    ("fabric6000", lambda: T.fabric(6000, full=True), "masks", True),  # 6,000 nodes: OWN 8
+    ("fabric10000", lambda: T.fabric(10000, full=True), "masks", True),  # 9,976 nodes: OWN 10
+    ("fabric11500", lambda: T.fabric(11500, full=True), "masks", True),  # 11,488 nodes: OWN 12, the last
+]
+
+
+@pytest.mark.parametrize("name,make,variant,twins", BANDS,
+                         ids=[f"{b[0]}-{b[2]}{'-quotient' if b[3] else ''}" for b in BANDS])
+def test_every_instance_band(name, make, variant, twins, monkeypatch):
+    """The template instances of msbfs_kernel and msbfs_planes_kernel that the
+    smaller graphs of this file never launch: OWN 4, 8, 12 and 16 of the
+    per-level kernel (grids), OWN 4 and 8 of the register-plane kernel, and
+    OWN 4, 8, 10 and 12 of the quotient sweep (fabrics; with class rows off,
+    which would run class_bfs_kernel instead).  With the quotient off as well,
+    the same fabrics run the plain sweep where a fabric's wide columns send it:
+    columns in LDS at OWN 4, the double-buffered frontier at OWN 8 and 10,
+    columns from L2 at OWN 12.  Three sources per graph, hop counts, u32 rows
+    and the sliced (planes: u8) rows, against the oracle."""
+    monkeypatch.setenv("SPF_MSBFS", variant)
+    monkeypatch.setenv("SPF_MSBFS_TEAM", "0")  # three sources would make a team plan
+    monkeypatch.setenv("SPF_CLASS_ROWS", "0")  # msbfs_kernel's own quotient sweep
+    names, eng, orc = load(make())
+    n = len(names)
+    assert n == {"grid50": 2500, "grid70": 4900, "grid105": 11025, "grid115": 13225,
+                 "fabric3000": 2976, "fabric6000": 6000, "fabric10000": 9976, "fabric11500": 11488}[name]
+    srcs = [0, n // 2, n - 1]
+    kernel = "msbfs_planes_kernel" if variant == "planes" else "msbfs_kernel"
+    for quotient in ((None, "0") if twins else (None,)):
+        if quotient is not None:
+            monkeypatch.setenv("SPF_QUOTIENT", quotient)
+        for narrow in ("0", "2"):
+            monkeypatch.setenv("SPF_NARROW", narrow)
+            plan = eng.plan(srcs, hop=True)
+            assert plan.kernels()[0] == kernel
+            assert plan.row_mode() == ("u32" if narrow == "0" else "sliced" if variant == "masks" else "u8")
+            assert quotient_in_use(eng) == (twins and quotient is None)
+            compare(names, eng, orc, srcs, hop=True)

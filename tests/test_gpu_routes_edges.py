@@ -325,7 +325,7 @@ def wide_random():
 
 
 # The largest metric a 50-node graph may carry and still get a resident pass:
-# max metric x N < 2^32 - 1 (needs64, spf_engine.hip metric_flags).
+# max metric x N < 2^32 - 1 (needs64, graph_host.cpp metric_flags).
 WIDE_N = 50
 WIDE_M = (2**32 - 2) // WIDE_N
 
