@@ -132,14 +132,28 @@ struct ExactWhatIf {
   uint32_t src = 0, n_fail = 0, W = 1;
 };
 
+// A list product of a what-if plan (whatif_pool.cpp): owner o holds entries
+// ptr[o] .. ptr[o + 1] of key / val / rows, in the order the fill pass's
+// atomics left them.  Built by count, scan (whatif_scan), pool_size from the
+// scan's total, and fill; the arrays are kept while they are large enough.
+//   change lists   owner = failure, key = node, val = metric, rows = next hops
+//   route lists    owner = failure, key = set,  val = min metric, rows = next hops
+//   impact lists   owner = node or set, key = failure, val = entry index, no rows
+struct WiPool {
+  bool valid = false;  // the call that builds it succeeded; nothing it reads was rebuilt since
+  uint32_t n_owners = 0, W = 0;  // W: words per row (0: no row column)
+  uint64_t total = 0;
+  DevBuf<unsigned long long> ptr, val;  // [n_owners + 1], [total] (~0: unreachable / withdrawn)
+  DevBuf<uint32_t> key, rows;           // [total], [total][W]
+};
+
 // Route lists of a what-if batch (spf_whatif_routes, whatif_routes.hip): the
 // caller's sets and their inverse index on the device, the base in the lists'
 // layout, every set's base route, the lookup table over the change lists'
-// entries and the exactly sized pools (all kept while they are large enough).
+// entries and the pool (all kept while they are large enough).
 struct WiRoutes {
-  bool valid = false;  // a call succeeded; no spf_whatif_changes or failed call since
+  WiPool pool;  // invalid after spf_whatif_changes or a failed call
   uint32_t n_sets = 0;
-  uint64_t total = 0;
   double ms[4] = {0, 0, 0, 0};  // base + index, count, scan, fill of the last call
   DevBuf<uint32_t> d_set_ptr, d_set_nodes, d_inv_ptr, d_inv_set, d_inv_pos;
   DevBuf<unsigned long long> d_bd;  // [N] base metrics, ~0: unreachable
@@ -149,8 +163,6 @@ struct WiRoutes {
   DevBuf<unsigned long long> d_keys;  // (failure << 32 | node), ~0: empty
   DevBuf<uint32_t> d_vals, d_efail;   // entry index per slot; failure per entry
   DevBuf<uint32_t> d_cnt, d_cur;      // [n_fail] counts, fill cursors
-  DevBuf<unsigned long long> d_rptr, d_rmet;  // [n_fail + 1], [total]
-  DevBuf<uint32_t> d_rset, d_rnh;             // [total], [total][W]
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   ~WiRoutes() {
     for (hipEvent_t e : ev)
@@ -160,16 +172,13 @@ struct WiRoutes {
 
 // Impact by destination (spf_whatif_by_node / spf_whatif_by_set,
 // whatif_impact.hip): the change or route lists transposed to key-major and
-// every key's summary, in exactly sized pools (kept while they are large
-// enough).  A plan holds one per flavour.
+// every key's summary (kept while they are large enough).  A plan holds one
+// per flavour.
 struct WiImpact {
-  bool valid = false;  // a call succeeded; its lists were not rebuilt, no failed call since
-  uint32_t n_keys = 0;
-  uint64_t total = 0;
+  WiPool pool;  // owners: the keys; invalid once its lists were rebuilt or a call failed
   double ms[3] = {0, 0, 0};  // count (with init), scan, fill of the last call
-  DevBuf<unsigned long long> d_tptr, d_tent;  // [n_keys + 1], [total]
-  DevBuf<uint32_t> d_tfail, d_cur;            // [total]; [n_keys] fill cursors
-  DevBuf<spf_whatif_impact> d_imp;            // [n_keys]
+  DevBuf<uint32_t> d_cur;           // [n_keys] fill cursors
+  DevBuf<spf_whatif_impact> d_imp;  // [n_keys]
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   ~WiImpact() {
     for (hipEvent_t e : ev)
@@ -178,21 +187,22 @@ struct WiImpact {
 };
 
 // What whatif_routes.hip and whatif_impact.hip read of a plan (whatif.hip owns
-// spf_whatif_plan): the lists of the last spf_whatif_changes, the unfailed
-// result as the plan holds it (u32 metrics with kInf and rows that are
-// undefined where unreachable, or the exact plan's u64 ones), the plan's route
-// lists and its two transpositions.
+// spf_whatif_plan): the change lists of the last spf_whatif_changes, the
+// unfailed result as the plan holds it (u32 metrics with kInf and rows that
+// are undefined where unreachable, or the exact plan's u64 ones), the plan's
+// route lists and its two transpositions.
+enum WiPoolId { kPoolChanges, kPoolRoutes, kPoolByNode, kPoolBySet };  // kPoolByNode + SPF_WHATIF_BY_*
 struct WiListsView {
   spf_ctx* ctx = nullptr;
+  const WiPool* changes = nullptr;
   WiRoutes* rt = nullptr;
   WiImpact* imp[2] = {nullptr, nullptr};  // SPF_WHATIF_BY_NODE, SPF_WHATIF_BY_SET
-  bool has_lists = false, no_nbr = false;  // no_nbr: src has no up neighbour (rows undefined)
-  uint64_t epoch = 0, total = 0;
+  const WiPool* pool(WiPoolId id) const {
+    return id == kPoolChanges ? changes : id == kPoolRoutes ? &rt->pool : &imp[id - kPoolByNode]->pool;
+  }
+  bool no_nbr = false;  // src has no up neighbour (rows undefined)
+  uint64_t epoch = 0;
   uint32_t src = 0, n_fail = 0, W = 1;
-  const unsigned long long* cptr = nullptr;
-  const uint32_t* cnode = nullptr;
-  const unsigned long long* cdist = nullptr;
-  const uint32_t* cnh = nullptr;
   const uint32_t* base_d32 = nullptr;  // one of the two
   const uint64_t* base_d64 = nullptr;
   const uint32_t* base_nh = nullptr;  // [N][W]
@@ -524,11 +534,30 @@ spf_status launch_exact(spf_ctx* c, ExactScratch* x, const uint32_t* d_srcs, uin
 // spf_whatif_routes (whatif_routes.hip) and spf_whatif_by_node / _by_set
 // (whatif_impact.hip); p is not NULL.
 void whatif_lists_view(spf_whatif_plan* p, WiListsView* v);
-// The change lists' scan (whatif_scan_kernel, whatif.hip) on `s`: ptr[0 .. n]
-// = the exclusive scan of cnt[0], cnt[stride], ... (n counts) and the total.
+// Every pool's scan (whatif_scan_kernel, whatif.hip) on `s`: ptr[0 .. n] = the
+// exclusive scan of cnt[0], cnt[stride], ... (n counts) and the total.
 // stride is 1 (a plain array) or 8 (spf_whatif_impact::n_changed).
 hipError_t whatif_scan(const uint32_t* cnt, uint32_t stride, uint32_t n, unsigned long long* ptr,
                        hipStream_t s);
+// What the pools share on the host (whatif_pool.cpp).  `who` is the C call's
+// name, in front of every message.
+// v = the view of plan p when it holds pool `id`; else "NULL plan" (p NULL) or
+// "the plan holds no <lists>".
+spf_status pool_held(spf_whatif_plan* p, WiPoolId id, const char* who, WiListsView* v);
+// key / val / rows for `total` entries of W words, exactly (at least one);
+// all three freed and SPF_E_NOMEM when the device has no room.  Sets q->W.
+spf_status pool_size(spf_ctx* c, WiPool* q, uint64_t total, uint32_t W, const char* who);
+uint64_t pool_bytes(const WiPool& q);  // offsets and entries
+// The _read, _buffers and _db calls of pool `id` (any output may be NULL;
+// rows are left alone in a pool without a row column).  _db: the owner's
+// entries ascending by (key, val), *n their number, SPF_E_NOMEM past `cap`.
+spf_status pool_read(spf_whatif_plan* p, WiPoolId id, const char* who, uint64_t* ptr, uint32_t* key,
+                     uint64_t* val, uint32_t* rows);
+spf_status pool_buffers(spf_whatif_plan* p, WiPoolId id, const char* who, const uint64_t** d_ptr,
+                        const uint32_t** d_key, const uint64_t** d_val, const uint32_t** d_rows,
+                        uint32_t* n_owners, uint32_t* W, uint64_t* n_entries);
+spf_status pool_db(spf_whatif_plan* p, WiPoolId id, const char* who, uint32_t owner, uint32_t* key,
+                   uint64_t* val, uint32_t* rows, uint64_t cap, uint64_t* n);
 // spf_big_kernel (whatif.hip): the plan's sources one after another on the
 // whole chip -- frontier SSSP into the dist rows, next hops in distance
 // order, transposed into the plan's bitmaps.  Positive metrics or hop counts.

@@ -870,17 +870,12 @@ void whatif_lists_view(spf_whatif_plan* p, WiListsView* v) {
   v->rt = &p->rt;
   v->imp[SPF_WHATIF_BY_NODE] = &p->imp_node;
   v->imp[SPF_WHATIF_BY_SET] = &p->imp_set;
-  v->has_lists = p->has_lists;
+  v->changes = &p->lists;
   v->no_nbr = p->src + 1 < c->nb_ptr.size() && c->nb_ptr[p->src + 1] == c->nb_ptr[p->src];
   v->epoch = p->epoch;
-  v->total = p->l_total;
   v->src = p->src;
   v->n_fail = p->n_fail;
   v->W = p->W;
-  v->cptr = p->l_ptr.p;
-  v->cnode = p->l_node.p;
-  v->cdist = p->l_dist.p;
-  v->cnh = p->l_nh.p;
   v->base_d32 = p->exact ? nullptr : p->d_dist.p;
   v->base_d64 = p->exact ? p->exact->base_d.p : nullptr;
   v->base_nh = p->exact ? p->exact->base_nh.p : p->d_nhb.p;
@@ -1326,9 +1321,10 @@ spf_status spf_whatif_changes(spf_whatif_plan* p, spf_whatif_digest* d_out, spf_
                               void* stream) {
   if (!p) return fail(nullptr, SPF_E_INVALID, "spf_whatif_changes: NULL plan");
   spf_ctx* c = p->ctx;
-  p->has_lists = false;  // after a failed call the plan holds no lists
-  p->rt.valid = false;   // ... and the route lists were built from the old ones
-  p->imp_node.valid = p->imp_set.valid = false;  // ... as were the transpositions
+  WiPool& L = p->lists;
+  L.valid = false;             // after a failed call the plan holds no lists
+  p->rt.pool.valid = false;    // ... and the route lists were built from the old ones
+  p->imp_node.pool.valid = p->imp_set.pool.valid = false;  // ... as were the transpositions
   if (!c->loaded) return fail(c, SPF_E_STATE, "graph no longer loaded");
   if (p->epoch != c->epoch)
     return fail(c, SPF_E_STATE, "graph changed since the plan was created: recreate it");
@@ -1336,7 +1332,7 @@ spf_status spf_whatif_changes(spf_whatif_plan* p, spf_whatif_digest* d_out, spf_
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   const uint32_t nf = p->n_fail;
   HIP_TRY(c, p->l_cnt.alloc(std::max<uint32_t>(1, nf)));
-  HIP_TRY(c, p->l_ptr.alloc((size_t)nf + 1));
+  HIP_TRY(c, L.ptr.alloc((size_t)nf + 1));
   if (!d_out) {
     HIP_TRY(c, p->l_dig.alloc(std::max<uint32_t>(1, nf)));
     d_out = p->l_dig.p;
@@ -1363,28 +1359,19 @@ spf_status spf_whatif_changes(spf_whatif_plan* p, spf_whatif_digest* d_out, spf_
   HIP_TRY(c, hipEventRecord(p->l_ev[0], s));
   if (const spf_status st = pass(true); st != SPF_OK) return st;
   HIP_TRY(c, hipEventRecord(p->l_ev[1], s));
-  HIP_TRY(c, whatif_scan(p->l_cnt.p, 1, nf, p->l_ptr.p, s));
+  HIP_TRY(c, whatif_scan(p->l_cnt.p, 1, nf, L.ptr.p, s));
   HIP_TRY(c, hipEventRecord(p->l_ev[2], s));
-  // the pools are sized from the scan's total
+  // the pool is sized from the scan's total
   unsigned long long total = 0;
-  HIP_TRY(c, hipMemcpyAsync(&total, p->l_ptr.p + nf, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(&total, L.ptr.p + nf, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   if (const spf_status st = spf_device_check(c); st != SPF_OK) return st;
-  const size_t cap = std::max<size_t>(1, (size_t)total);
-  if (p->l_node.alloc(cap) != hipSuccess || p->l_dist.alloc(cap) != hipSuccess ||
-      p->l_nh.alloc(cap * p->W) != hipSuccess) {  // (kept while they are large enough)
-    (void)hipGetLastError();
-    p->l_node.reset();
-    p->l_dist.reset();
-    p->l_nh.reset();
-    return fail(c, SPF_E_NOMEM, "spf_whatif_changes: no memory for %llu entries of %u bytes", total,
-                12u + 4u * p->W);
-  }
+  if (const spf_status st = pool_size(c, &L, total, p->W, "spf_whatif_changes"); st != SPF_OK) return st;
   // fill: the repairs again, entries to cptr[f] + k
-  em.cptr = p->l_ptr.p;
-  em.cnode = p->l_node.p;
-  em.cdist = p->l_dist.p;
-  em.cnh = p->l_nh.p;
+  em.cptr = L.ptr.p;
+  em.cnode = L.key.p;
+  em.cdist = L.val.p;
+  em.cnh = L.rows.p;
   if (const spf_status st = pass(false); st != SPF_OK) return st;
   HIP_TRY(c, hipEventRecord(p->l_ev[3], s));
   if (d_base && !p->exact) {
@@ -1394,18 +1381,22 @@ spf_status spf_whatif_changes(spf_whatif_plan* p, spf_whatif_digest* d_out, spf_
   HIP_TRY(c, hipStreamSynchronize(s));
   if (const spf_status st = spf_device_check(c); st != SPF_OK) return st;
   for (int k = 0; k < 3; ++k) HIP_TRY(c, hipEventElapsedTime(&p->l_ms[k], p->l_ev[k], p->l_ev[k + 1]));
-  p->l_total = total;
-  p->has_lists = true;
+  L.n_owners = nf;
+  L.total = total;
+  L.valid = true;
   c->solves += 1ull + nf;
   if (n_entries) *n_entries = total;
-  if (pool_bytes) *pool_bytes = 8ull * ((uint64_t)nf + 1) + total * (12ull + 4ull * p->W);
+  if (pool_bytes) *pool_bytes = spfi::pool_bytes(L);
   if (kernel_ms) *kernel_ms = (double)p->l_ms[0] + p->l_ms[1] + p->l_ms[2];
   return SPF_OK;
 }
 
 spf_status spf_whatif_changes_timing(const spf_whatif_plan* p, double* ms) {
   if (!p || !ms) return SPF_E_INVALID;
-  if (!p->has_lists) return fail(p->ctx, SPF_E_STATE, "spf_whatif_changes_timing: the plan holds no lists");
+  WiListsView v;
+  if (const spf_status st = pool_held(const_cast<spf_whatif_plan*>(p), kPoolChanges,
+                                      "spf_whatif_changes_timing", &v); st != SPF_OK)
+    return st;
   for (int k = 0; k < 3; ++k) ms[k] = p->l_ms[k];
   return SPF_OK;
 }
@@ -1413,62 +1404,18 @@ spf_status spf_whatif_changes_timing(const spf_whatif_plan* p, double* ms) {
 spf_status spf_whatif_changes_buffers(spf_whatif_plan* p, const uint64_t** d_ptr, const uint32_t** d_node,
                                       const uint64_t** d_dist, const uint32_t** d_nh, uint32_t* W,
                                       uint64_t* n_entries) {
-  if (!p) return fail(nullptr, SPF_E_INVALID, "spf_whatif_changes_buffers: NULL plan");
-  if (!p->has_lists) return fail(p->ctx, SPF_E_STATE, "spf_whatif_changes_buffers: the plan holds no lists");
-  if (d_ptr) *d_ptr = reinterpret_cast<const uint64_t*>(p->l_ptr.p);
-  if (d_node) *d_node = p->l_node.p;
-  if (d_dist) *d_dist = reinterpret_cast<const uint64_t*>(p->l_dist.p);
-  if (d_nh) *d_nh = p->l_nh.p;
-  if (W) *W = p->W;
-  if (n_entries) *n_entries = p->l_total;
-  return SPF_OK;
+  return pool_buffers(p, kPoolChanges, "spf_whatif_changes_buffers", d_ptr, d_node, d_dist, d_nh, nullptr,
+                      W, n_entries);
 }
 
 spf_status spf_whatif_changes_read(spf_whatif_plan* p, uint64_t* ptr, uint32_t* node, uint64_t* dist,
                                    uint32_t* nh) {
-  if (!p) return fail(nullptr, SPF_E_INVALID, "spf_whatif_changes_read: NULL plan");
-  spf_ctx* c = p->ctx;
-  if (!p->has_lists) return fail(c, SPF_E_STATE, "spf_whatif_changes_read: the plan holds no lists");
-  HIP_TRY(c, hipSetDevice(c->device));
-  const size_t t = (size_t)p->l_total;
-  if (ptr) HIP_TRY(c, hipMemcpy(ptr, p->l_ptr.p, 8ull * ((size_t)p->n_fail + 1), hipMemcpyDeviceToHost));
-  if (node && t) HIP_TRY(c, hipMemcpy(node, p->l_node.p, 4ull * t, hipMemcpyDeviceToHost));
-  if (dist && t) HIP_TRY(c, hipMemcpy(dist, p->l_dist.p, 8ull * t, hipMemcpyDeviceToHost));
-  if (nh && t) HIP_TRY(c, hipMemcpy(nh, p->l_nh.p, 4ull * t * p->W, hipMemcpyDeviceToHost));
-  return SPF_OK;
+  return pool_read(p, kPoolChanges, "spf_whatif_changes_read", ptr, node, dist, nh);
 }
 
 spf_status spf_whatif_changes_db(spf_whatif_plan* p, uint32_t i, uint32_t* node, uint64_t* dist,
                                  uint32_t* nh, uint64_t cap, uint64_t* n) {
-  if (!p) return fail(nullptr, SPF_E_INVALID, "spf_whatif_changes_db: NULL plan");
-  spf_ctx* c = p->ctx;
-  if (!p->has_lists) return fail(c, SPF_E_STATE, "spf_whatif_changes_db: the plan holds no lists");
-  if (i >= p->n_fail) return fail(c, SPF_E_INVALID, "spf_whatif_changes_db: failure %u of %u", i, p->n_fail);
-  HIP_TRY(c, hipSetDevice(c->device));
-  unsigned long long r[2] = {0, 0};
-  HIP_TRY(c, hipMemcpy(r, p->l_ptr.p + i, 16, hipMemcpyDeviceToHost));
-  if (r[1] < r[0] || r[1] > p->l_total) return fail(c, SPF_E_HIP, "spf_whatif_changes_db: offsets not monotone");
-  const size_t m = (size_t)(r[1] - r[0]), W = p->W;
-  if (n) *n = m;
-  if (!node && !dist && !nh) return SPF_OK;
-  if (cap < m) return fail(c, SPF_E_NOMEM, "spf_whatif_changes_db: %zu entries, room for %llu", m,
-                           (unsigned long long)cap);
-  if (!m) return SPF_OK;
-  std::vector<uint32_t> hn(m), hw(m * W);
-  std::vector<uint64_t> hd(m);
-  HIP_TRY(c, hipMemcpy(hn.data(), p->l_node.p + r[0], 4 * m, hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(hd.data(), p->l_dist.p + r[0], 8 * m, hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(hw.data(), p->l_nh.p + r[0] * W, 4 * m * W, hipMemcpyDeviceToHost));
-  std::vector<size_t> order(m);  // the device order is the teams' atomics': ascending by node here
-  for (size_t k = 0; k < m; ++k) order[k] = k;
-  std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return hn[a] < hn[b]; });
-  for (size_t k = 0; k < m; ++k) {
-    const size_t q = order[k];
-    if (node) node[k] = hn[q];
-    if (dist) dist[k] = hd[q];
-    if (nh) std::memcpy(nh + k * W, hw.data() + q * W, 4 * W);
-  }
-  return SPF_OK;
+  return pool_db(p, kPoolChanges, "spf_whatif_changes_db", i, node, dist, nh, cap, n);
 }
 
 spf_status spf_whatif_base(spf_whatif_plan* p, uint64_t* dist, uint32_t* nh, uint32_t* W) {

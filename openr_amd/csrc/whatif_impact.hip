@@ -26,7 +26,7 @@
 #include "whatif_owner.h"
 
 #include <cstddef>
-#include <numeric>
+#include <string>
 
 using namespace spfi;
 
@@ -156,22 +156,10 @@ __global__ __launch_bounds__(kThreads) void wi_finish_kernel(WiArgs a) {
   if (w & kBaseWidth) a.imp[k].min_width = w & ~kBaseWidth;
 }
 
-uint32_t blocks_for(unsigned long long items, uint32_t per_block) {
-  return (uint32_t)((items + per_block - 1) / per_block);
-}
-
 const char* const kCall[2] = {"spf_whatif_by_node", "spf_whatif_by_set"};
-
-// The plan's view when it holds flavour `which`, the call named as
-// spf_whatif_by_<flavour><suffix> in the messages.
-spf_status held(spf_whatif_plan* p, int which, const char* suffix, WiListsView* v) {
-  if (!p) return fail(nullptr, SPF_E_INVALID, "%s%s: NULL plan", kCall[which], suffix);
-  whatif_lists_view(p, v);
-  if (!v->imp[which]->valid)
-    return fail(v->ctx, SPF_E_STATE, "%s%s: the plan holds no impact lists (%s first)", kCall[which],
-                suffix, kCall[which]);
-  return SPF_OK;
-}
+WiPoolId pool_id(int which) { return WiPoolId(kPoolByNode + which); }
+// spf_whatif_by_<flavour><suffix>, as the messages name the call
+std::string call(int which, const char* suffix) { return std::string(kCall[which]) + suffix; }
 
 spf_status by_key(spf_whatif_plan* p, int which, uint64_t* n_entries, uint64_t* pool_bytes,
                   double* kernel_ms, void* stream) {
@@ -180,40 +168,36 @@ spf_status by_key(spf_whatif_plan* p, int which, uint64_t* n_entries, uint64_t* 
   whatif_lists_view(p, &v);
   spf_ctx* c = v.ctx;
   WiImpact& m = *v.imp[which];
-  m.valid = false;  // after a failed call the plan holds none
+  WiPool& T = m.pool;
+  T.valid = false;  // after a failed call the plan holds none
   if (!c->loaded) return fail(c, SPF_E_STATE, "graph no longer loaded");
   if (v.epoch != c->epoch)
     return fail(c, SPF_E_STATE, "graph changed since the plan was created: recreate it");
-  if (!v.has_lists)
+  if (!v.changes->valid)
     return fail(c, SPF_E_STATE, "%s: the plan holds no lists (spf_whatif_changes first)", kCall[which]);
   const bool sets = which == SPF_WHATIF_BY_SET;
-  if (sets && !v.rt->valid)
+  const WiRoutes& r = *v.rt;
+  if (sets && !r.pool.valid)
     return fail(c, SPF_E_STATE, "%s: the plan holds no route lists (spf_whatif_routes first)",
                 kCall[which]);
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  const WiRoutes& r = *v.rt;
+  const WiPool& L = sets ? r.pool : *v.changes;  // the lists to transpose
   const uint32_t n_keys = sets ? r.n_sets : c->N;
-  const unsigned long long total = sets ? r.total : v.total;
+  const unsigned long long total = L.total;
 
   for (hipEvent_t& e : m.ev)
     if (!e) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
-  const size_t room = std::max<size_t>(1, (size_t)total);
-  HIP_TRY(c, m.d_tptr.alloc((size_t)n_keys + 1));
+  HIP_TRY(c, T.ptr.alloc((size_t)n_keys + 1));
   HIP_TRY(c, m.d_cur.alloc(std::max<uint32_t>(1, n_keys)));
   HIP_TRY(c, m.d_imp.alloc(std::max<uint32_t>(1, n_keys)));
-  if (m.d_tfail.alloc(room) != hipSuccess || m.d_tent.alloc(room) != hipSuccess) {
-    (void)hipGetLastError();
-    m.d_tfail.reset();
-    m.d_tent.reset();
-    return fail(c, SPF_E_NOMEM, "%s: no memory for %llu entries of 12 bytes", kCall[which], total);
-  }
+  if (const spf_status st = pool_size(c, &T, total, 0, kCall[which]); st != SPF_OK) return st;
 
   WiArgs a{};
-  a.key = sets ? r.d_rset.p : v.cnode;
-  a.dist = sets ? r.d_rmet.p : v.cdist;
-  a.nh = sets ? r.d_rnh.p : v.cnh;
-  a.optr = sets ? r.d_rptr.p : v.cptr;
+  a.key = L.key.p;
+  a.dist = L.val.p;
+  a.nh = L.rows.p;
+  a.optr = L.ptr.p;
   a.n_own = v.n_fail;
   if (sets) {  // base routes: u64, zero rows where there is no route
     a.b64 = r.d_rbm.p;
@@ -229,9 +213,9 @@ spf_status by_key(spf_whatif_plan* p, int which, uint64_t* n_entries, uint64_t* 
   a.total = total;
   a.imp = m.d_imp.p;
   a.cur = m.d_cur.p;
-  a.tptr = m.d_tptr.p;
-  a.tfail = m.d_tfail.p;
-  a.tent = m.d_tent.p;
+  a.tptr = T.ptr.p;
+  a.tfail = T.key.p;
+  a.tent = T.val.p;
   a.fault = c->d_fault.p;
 
   const dim3 by_keys(blocks_for(n_keys, kThreads)), by_entries(blocks_for(total, kThreads));
@@ -245,7 +229,7 @@ spf_status by_key(spf_whatif_plan* p, int which, uint64_t* n_entries, uint64_t* 
     HIP_TRY(c, hipGetLastError());
   }
   HIP_TRY(c, hipEventRecord(m.ev[1], s));
-  HIP_TRY(c, whatif_scan(&m.d_imp.p->n_changed, sizeof(spf_whatif_impact) / 4, n_keys, m.d_tptr.p, s));
+  HIP_TRY(c, whatif_scan(&m.d_imp.p->n_changed, sizeof(spf_whatif_impact) / 4, n_keys, T.ptr.p, s));
   HIP_TRY(c, hipEventRecord(m.ev[2], s));
   if (total && n_keys) {
     hipLaunchKernelGGL(wi_fill_kernel, by_entries, dim3(kThreads), 0, s, a);
@@ -257,7 +241,7 @@ spf_status by_key(spf_whatif_plan* p, int which, uint64_t* n_entries, uint64_t* 
   }
   HIP_TRY(c, hipEventRecord(m.ev[3], s));
   unsigned long long placed = 0;
-  HIP_TRY(c, hipMemcpyAsync(&placed, m.d_tptr.p + n_keys, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(&placed, T.ptr.p + n_keys, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   if (const spf_status st = spf_device_check(c); st != SPF_OK) return st;
   if (placed != total)
@@ -268,88 +252,48 @@ spf_status by_key(spf_whatif_plan* p, int which, uint64_t* n_entries, uint64_t* 
     HIP_TRY(c, hipEventElapsedTime(&ms, m.ev[k], m.ev[k + 1]));
     m.ms[k] = ms;
   }
-  m.n_keys = n_keys;
-  m.total = total;
-  m.valid = true;
+  T.n_owners = n_keys;
+  T.total = total;
+  T.valid = true;
   if (n_entries) *n_entries = total;
-  if (pool_bytes) *pool_bytes = 8ull * ((uint64_t)n_keys + 1) + 12ull * total + 32ull * n_keys;
+  if (pool_bytes) *pool_bytes = spfi::pool_bytes(T) + 32ull * n_keys;
   if (kernel_ms) *kernel_ms = m.ms[0] + m.ms[1] + m.ms[2];
   return SPF_OK;
 }
 
 spf_status impact_of(spf_whatif_plan* p, int which, spf_whatif_impact* out) {
   WiListsView v;
-  if (const spf_status st = held(p, which, "_impact", &v); st != SPF_OK) return st;
+  if (const spf_status st = pool_held(p, pool_id(which), call(which, "_impact").c_str(), &v); st != SPF_OK)
+    return st;
   spf_ctx* c = v.ctx;
   const WiImpact& m = *v.imp[which];
   HIP_TRY(c, hipSetDevice(c->device));
-  if (out && m.n_keys)
-    HIP_TRY(c, hipMemcpy(out, m.d_imp.p, sizeof(spf_whatif_impact) * m.n_keys, hipMemcpyDeviceToHost));
+  if (out && m.pool.n_owners)
+    HIP_TRY(c, hipMemcpy(out, m.d_imp.p, sizeof(spf_whatif_impact) * m.pool.n_owners, hipMemcpyDeviceToHost));
   return SPF_OK;
 }
 
 spf_status read_of(spf_whatif_plan* p, int which, uint64_t* ptr, uint32_t* failure, uint64_t* ent,
                    spf_whatif_impact* imp) {
-  WiListsView v;
-  if (const spf_status st = held(p, which, "_read", &v); st != SPF_OK) return st;
-  spf_ctx* c = v.ctx;
-  const WiImpact& m = *v.imp[which];
-  HIP_TRY(c, hipSetDevice(c->device));
-  const size_t t = (size_t)m.total, nk = m.n_keys;
-  if (ptr) HIP_TRY(c, hipMemcpy(ptr, m.d_tptr.p, 8 * (nk + 1), hipMemcpyDeviceToHost));
-  if (failure && t) HIP_TRY(c, hipMemcpy(failure, m.d_tfail.p, 4 * t, hipMemcpyDeviceToHost));
-  if (ent && t) HIP_TRY(c, hipMemcpy(ent, m.d_tent.p, 8 * t, hipMemcpyDeviceToHost));
-  if (imp && nk) HIP_TRY(c, hipMemcpy(imp, m.d_imp.p, sizeof(spf_whatif_impact) * nk, hipMemcpyDeviceToHost));
-  return SPF_OK;
+  const spf_status st = pool_read(p, pool_id(which), call(which, "_read").c_str(), ptr, failure, ent, nullptr);
+  return st == SPF_OK && imp ? impact_of(p, which, imp) : st;
 }
 
 spf_status buffers_of(spf_whatif_plan* p, int which, const uint64_t** d_ptr, const uint32_t** d_fail,
                       const uint64_t** d_ent, const spf_whatif_impact** d_imp, uint32_t* n_keys,
                       uint64_t* n_entries) {
+  const spf_status st = pool_buffers(p, pool_id(which), call(which, "_buffers").c_str(), d_ptr, d_fail,
+                                     d_ent, nullptr, n_keys, nullptr, n_entries);
+  if (st != SPF_OK || !d_imp) return st;
   WiListsView v;
-  if (const spf_status st = held(p, which, "_buffers", &v); st != SPF_OK) return st;
-  const WiImpact& m = *v.imp[which];
-  if (d_ptr) *d_ptr = reinterpret_cast<const uint64_t*>(m.d_tptr.p);
-  if (d_fail) *d_fail = m.d_tfail.p;
-  if (d_ent) *d_ent = reinterpret_cast<const uint64_t*>(m.d_tent.p);
-  if (d_imp) *d_imp = m.d_imp.p;
-  if (n_keys) *n_keys = m.n_keys;
-  if (n_entries) *n_entries = m.total;
+  whatif_lists_view(p, &v);
+  *d_imp = v.imp[which]->d_imp.p;
   return SPF_OK;
 }
 
 spf_status db_of(spf_whatif_plan* p, int which, uint32_t key, uint32_t* failure, uint64_t* ent,
                  uint64_t cap, uint64_t* n) {
-  WiListsView v;
-  if (const spf_status st = held(p, which, "_db", &v); st != SPF_OK) return st;
-  spf_ctx* c = v.ctx;
-  const WiImpact& m = *v.imp[which];
-  if (key >= m.n_keys) return fail(c, SPF_E_INVALID, "%s_db: key %u of %u", kCall[which], key, m.n_keys);
-  HIP_TRY(c, hipSetDevice(c->device));
-  unsigned long long at[2] = {0, 0};
-  HIP_TRY(c, hipMemcpy(at, m.d_tptr.p + key, 16, hipMemcpyDeviceToHost));
-  if (at[1] < at[0] || at[1] > m.total) return fail(c, SPF_E_HIP, "%s_db: offsets not monotone", kCall[which]);
-  const size_t cnt = (size_t)(at[1] - at[0]);
-  if (n) *n = cnt;
-  if (!failure && !ent) return SPF_OK;
-  if (cap < cnt)
-    return fail(c, SPF_E_NOMEM, "%s_db: %zu entries, room for %llu", kCall[which], cnt,
-                (unsigned long long)cap);
-  if (!cnt) return SPF_OK;
-  std::vector<uint32_t> hf(cnt);
-  std::vector<uint64_t> he(cnt);
-  HIP_TRY(c, hipMemcpy(hf.data(), m.d_tfail.p + at[0], 4 * cnt, hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(he.data(), m.d_tent.p + at[0], 8 * cnt, hipMemcpyDeviceToHost));
-  std::vector<size_t> order(cnt);  // the device order is the cursor's: ascending by failure here
-  std::iota(order.begin(), order.end(), (size_t)0);
-  std::sort(order.begin(), order.end(), [&](size_t x, size_t y) {
-    return hf[x] != hf[y] ? hf[x] < hf[y] : he[x] < he[y];
-  });
-  for (size_t k = 0; k < cnt; ++k) {
-    if (failure) failure[k] = hf[order[k]];
-    if (ent) ent[k] = he[order[k]];
-  }
-  return SPF_OK;
+  return pool_db(p, pool_id(which), call(which, "_db").c_str(), key, failure, ent, nullptr, cap, n);
 }
 
 }  // namespace
@@ -407,7 +351,7 @@ spf_status spf_whatif_impact_timing(const spf_whatif_plan* p, uint32_t which, do
   whatif_lists_view(const_cast<spf_whatif_plan*>(p), &v);
   if (which > SPF_WHATIF_BY_SET || !ms)
     return fail(v.ctx, SPF_E_INVALID, "spf_whatif_impact_timing: which = %u, ms = %p", which, (void*)ms);
-  if (!v.imp[which]->valid)
+  if (!v.imp[which]->pool.valid)
     return fail(v.ctx, SPF_E_STATE, "spf_whatif_impact_timing: the plan holds no impact lists (%s first)",
                 kCall[which]);
   for (int k = 0; k < 3; ++k) ms[k] = v.imp[which]->ms[k];

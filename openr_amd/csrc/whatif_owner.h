@@ -1,12 +1,18 @@
-// The failure that owns entry e of a failure-major list (the change lists'
-// cptr, the route lists' rptr): shared by the lists' device-side consumers,
-// whatif_routes.hip and whatif_impact.hip.
+// What the device-side consumers of the failure-major lists share,
+// whatif_routes.hip and whatif_impact.hip: their launch arithmetic and the
+// failure that owns entry e of a list (the change lists' or the route lists'
+// offsets).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 namespace spfi {
+
+// blocks of per_block threads for a thread per item
+inline uint32_t blocks_for(unsigned long long items, uint32_t per_block) {
+  return (uint32_t)((items + per_block - 1) / per_block);
+}
 
 // ptr[0 .. n_fail] ascending, ptr[0] = 0, e < ptr[n_fail], n_fail >= 1: the
 // last i with ptr[i] <= e.  Cold failures own nothing (ptr[i] == ptr[i + 1]),

@@ -63,14 +63,11 @@ struct spf_whatif_plan {
   hipStream_t last = nullptr;  // stream of the last execute (spf_whatif_stats waits on it)
   // zero / negative metrics or u64 labels: every failure on the exact kernel
   std::unique_ptr<spfi::ExactWhatIf> exact;
-  // change lists of the last spf_whatif_changes: counts, scanned offsets and
-  // the exactly sized pools (kept while they are large enough), the digests
-  // when the caller passes none, events around count / scan / fill
-  DevBuf<uint32_t> l_cnt, l_node, l_nh;
-  DevBuf<unsigned long long> l_ptr, l_dist;
+  // change lists of the last spf_whatif_changes: the pool and its counts, the
+  // digests when the caller passes none, events around count / scan / fill
+  spfi::WiPool lists;
+  DevBuf<uint32_t> l_cnt;
   DevBuf<spf_whatif_digest> l_dig;
-  uint64_t l_total = 0;
-  bool has_lists = false;
   hipEvent_t l_ev[4] = {nullptr, nullptr, nullptr, nullptr};
   float l_ms[3] = {0, 0, 0};
   // route lists of the last spf_whatif_routes (whatif_routes.hip), a consumer

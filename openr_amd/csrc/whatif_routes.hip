@@ -309,46 +309,6 @@ __global__ __launch_bounds__(kThreads) void wr_routes_kernel(WrArgs a) {
   }
 }
 
-// rptr[0 .. n] = the exclusive scan of cnt[0 .. n) and the total: one
-// workgroup, a count per thread and tile, the DPP wave scan over the two
-// halves of a count (64 halves stay below 2^32).
-__global__ __launch_bounds__(1024) void wr_scan_kernel(const uint32_t* __restrict__ cnt, uint32_t n,
-                                                      unsigned long long* __restrict__ rptr) {
-  __shared__ unsigned long long s_wave[16];
-  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  unsigned long long carry = 0;
-  for (uint64_t t0 = 0; t0 < n; t0 += 1024) {  // block-uniform
-    const uint64_t t = t0 + threadIdx.x;
-    const uint32_t x = t < n ? cnt[t] : 0u;
-    uint32_t tl = 0, th = 0;
-    const uint32_t el = wave_excl_scan(x & 0xFFFFu, &tl);
-    const uint32_t eh = wave_excl_scan(x >> 16, &th);
-    if (lane == 0) s_wave[wv] = tl + ((unsigned long long)th << 16);
-    __syncthreads();
-    unsigned long long run = carry + el + ((unsigned long long)eh << 16);
-    for (uint32_t w = 0; w < 16; ++w) {
-      const unsigned long long sum = s_wave[w];
-      if (w < wv) run += sum;
-      carry += sum;
-    }
-    if (t < n) rptr[t] = run;
-    __syncthreads();  // s_wave is rewritten by the next tile
-  }
-  if (threadIdx.x == 0) rptr[n] = carry;
-}
-
-uint32_t blocks_for(unsigned long long items, uint32_t per_block) {
-  return (uint32_t)((items + per_block - 1) / per_block);
-}
-
-spf_status no_routes(spf_whatif_plan* p, const char* who) {
-  if (!p) return fail(nullptr, SPF_E_INVALID, "%s: NULL plan", who);
-  WiListsView v;
-  whatif_lists_view(p, &v);
-  if (!v.rt->valid) return fail(v.ctx, SPF_E_STATE, "%s: the plan holds no route lists", who);
-  return SPF_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -361,18 +321,20 @@ spf_status spf_whatif_routes(spf_whatif_plan* p, const uint32_t* set_ptr, const 
   whatif_lists_view(p, &v);
   spf_ctx* c = v.ctx;
   WiRoutes& r = *v.rt;
-  r.valid = false;  // after a failed call the plan holds no route lists
-  v.imp[SPF_WHATIF_BY_SET]->valid = false;  // ... and none transposed from the old ones
+  WiPool& R = r.pool;
+  const WiPool& L = *v.changes;
+  R.valid = false;  // after a failed call the plan holds no route lists
+  v.imp[SPF_WHATIF_BY_SET]->pool.valid = false;  // ... and none transposed from the old ones
   if (const char* why = route_sets_check(c->N, set_ptr, set_nodes, n_sets))
     return fail(c, SPF_E_INVALID, "spf_whatif_routes: %s", why);
   if (!c->loaded) return fail(c, SPF_E_STATE, "graph no longer loaded");
   if (v.epoch != c->epoch)
     return fail(c, SPF_E_STATE, "graph changed since the plan was created: recreate it");
-  if (!v.has_lists)
+  if (!L.valid)
     return fail(c, SPF_E_STATE, "spf_whatif_routes: the plan holds no lists (spf_whatif_changes first)");
-  if (v.total >> 31)
+  if (L.total >> 31)
     return fail(c, SPF_E_NOMEM, "spf_whatif_routes: %llu list entries, the table indexes 2^31",
-                (unsigned long long)v.total);
+                (unsigned long long)L.total);
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   const uint32_t N = c->N, W = v.W, nf = v.n_fail;
@@ -394,14 +356,14 @@ spf_status spf_whatif_routes(spf_whatif_plan* p, const uint32_t* set_ptr, const 
   HIP_TRY(c, r.d_rbnh.alloc(std::max<size_t>(1, (size_t)n_sets * W)));
   HIP_TRY(c, r.d_cnt.alloc(std::max<uint32_t>(1, nf)));
   HIP_TRY(c, r.d_cur.alloc(std::max<uint32_t>(1, nf)));
-  HIP_TRY(c, r.d_rptr.alloc((size_t)nf + 1));
+  HIP_TRY(c, R.ptr.alloc((size_t)nf + 1));
   // the table: a power of two >= 2 x entries, so a probe always meets an empty slot
   size_t cap = 64;
-  while (cap < 2 * (size_t)v.total) cap <<= 1;
-  if (v.total) {
+  while (cap < 2 * (size_t)L.total) cap <<= 1;
+  if (L.total) {
     HIP_TRY(c, r.d_keys.alloc(cap));
     HIP_TRY(c, r.d_vals.alloc(cap));
-    HIP_TRY(c, r.d_efail.alloc((size_t)v.total));
+    HIP_TRY(c, r.d_efail.alloc((size_t)L.total));
   }
 
   WrArgs a{};
@@ -418,7 +380,7 @@ spf_status spf_whatif_routes(spf_whatif_plan* p, const uint32_t* set_ptr, const 
   a.W = W;
   a.src = v.src;
   a.n_sets = n_sets;
-  a.total = v.total;
+  a.total = L.total;
 
   // base: the unfailed result in the lists' layout, the sets' base routes, the table
   HIP_TRY(c, hipEventRecord(r.ev[0], s));
@@ -432,17 +394,17 @@ spf_status spf_whatif_routes(spf_whatif_plan* p, const uint32_t* set_ptr, const 
                        0, s, a);
     HIP_TRY(c, hipGetLastError());
   }
-  const bool work = v.total && !ix.set.empty();  // else: nothing can be listed
+  const bool work = L.total && !ix.set.empty();  // else: nothing can be listed
   if (work) {
     HIP_TRY(c, hipMemsetAsync(r.d_keys.p, 0xFF, 8 * cap, s));
-    hipLaunchKernelGGL(wr_table_kernel, dim3(blocks_for(v.total, kThreads)), dim3(kThreads), 0, s,
-                       v.cptr, v.cnode, nf, (unsigned long long)v.total, r.d_keys.p, r.d_vals.p,
+    hipLaunchKernelGGL(wr_table_kernel, dim3(blocks_for(L.total, kThreads)), dim3(kThreads), 0, s,
+                       L.ptr.p, L.key.p, nf, (unsigned long long)L.total, r.d_keys.p, r.d_vals.p,
                        (uint32_t)(cap - 1), r.d_efail.p);
     HIP_TRY(c, hipGetLastError());
   }
-  a.cnode = v.cnode;
-  a.cdist = v.cdist;
-  a.cnh = v.cnh;
+  a.cnode = L.key.p;
+  a.cdist = L.val.p;
+  a.cnh = L.rows.p;
   a.efail = r.d_efail.p;
   a.keys = r.d_keys.p;
   a.vals = r.d_vals.p;
@@ -454,35 +416,25 @@ spf_status spf_whatif_routes(spf_whatif_plan* p, const uint32_t* set_ptr, const 
   HIP_TRY(c, hipMemsetAsync(r.d_cur.p, 0, 4ull * std::max<uint32_t>(1, nf), s));
   HIP_TRY(c, hipEventRecord(r.ev[1], s));
   if (work) {
-    hipLaunchKernelGGL(wr_routes_kernel<false>, dim3(blocks_for(v.total, kThreads)), dim3(kThreads), 0,
+    hipLaunchKernelGGL(wr_routes_kernel<false>, dim3(blocks_for(L.total, kThreads)), dim3(kThreads), 0,
                        s, a);
     HIP_TRY(c, hipGetLastError());
   }
   HIP_TRY(c, hipEventRecord(r.ev[2], s));
-  hipLaunchKernelGGL(wr_scan_kernel, dim3(1), dim3(1024), 0, s, r.d_cnt.p, nf, r.d_rptr.p);
-  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, whatif_scan(r.d_cnt.p, 1, nf, R.ptr.p, s));
   HIP_TRY(c, hipEventRecord(r.ev[3], s));
-  // the pools are sized from the scan's total
+  // the pool is sized from the scan's total
   unsigned long long total = 0;
-  HIP_TRY(c, hipMemcpyAsync(&total, r.d_rptr.p + nf, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(&total, R.ptr.p + nf, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
-  const size_t room = std::max<size_t>(1, (size_t)total);
-  if (r.d_rset.alloc(room) != hipSuccess || r.d_rmet.alloc(room) != hipSuccess ||
-      r.d_rnh.alloc(room * W) != hipSuccess) {  // (kept while they are large enough)
-    (void)hipGetLastError();
-    r.d_rset.reset();
-    r.d_rmet.reset();
-    r.d_rnh.reset();
-    return fail(c, SPF_E_NOMEM, "spf_whatif_routes: no memory for %llu entries of %u bytes", total,
-                12u + 4u * W);
-  }
+  if (const spf_status st = pool_size(c, &R, total, W, "spf_whatif_routes"); st != SPF_OK) return st;
   // fill
-  a.rptr = r.d_rptr.p;
-  a.rset = r.d_rset.p;
-  a.rmet = r.d_rmet.p;
-  a.rnh = r.d_rnh.p;
+  a.rptr = R.ptr.p;
+  a.rset = R.key.p;
+  a.rmet = R.val.p;
+  a.rnh = R.rows.p;
   if (work && total) {
-    hipLaunchKernelGGL(wr_routes_kernel<true>, dim3(blocks_for(v.total, kThreads)), dim3(kThreads), 0,
+    hipLaunchKernelGGL(wr_routes_kernel<true>, dim3(blocks_for(L.total, kThreads)), dim3(kThreads), 0,
                        s, a);
     HIP_TRY(c, hipGetLastError());
   }
@@ -495,20 +447,21 @@ spf_status spf_whatif_routes(spf_whatif_plan* p, const uint32_t* set_ptr, const 
     r.ms[k] = ms;
   }
   r.n_sets = n_sets;
-  r.total = total;
-  r.valid = true;
+  R.n_owners = nf;
+  R.total = total;
+  R.valid = true;
   if (n_entries) *n_entries = total;
-  if (pool_bytes) *pool_bytes = 8ull * ((uint64_t)nf + 1) + total * (12ull + 4ull * W);
+  if (pool_bytes) *pool_bytes = spfi::pool_bytes(R);
   if (kernel_ms) *kernel_ms = std::accumulate(r.ms, r.ms + 4, 0.0);
   return SPF_OK;
 }
 
 spf_status spf_whatif_routes_timing(const spf_whatif_plan* p, double* ms) {
   if (!p || !ms) return SPF_E_INVALID;
-  if (const spf_status st = no_routes(const_cast<spf_whatif_plan*>(p), "spf_whatif_routes_timing"); st != SPF_OK)
-    return st;
   WiListsView v;
-  whatif_lists_view(const_cast<spf_whatif_plan*>(p), &v);
+  if (const spf_status st = pool_held(const_cast<spf_whatif_plan*>(p), kPoolRoutes,
+                                      "spf_whatif_routes_timing", &v); st != SPF_OK)
+    return st;
   for (int k = 0; k < 4; ++k) ms[k] = v.rt->ms[k];
   return SPF_OK;
 }
@@ -516,23 +469,13 @@ spf_status spf_whatif_routes_timing(const spf_whatif_plan* p, double* ms) {
 spf_status spf_whatif_routes_buffers(spf_whatif_plan* p, const uint64_t** d_ptr, const uint32_t** d_set,
                                      const uint64_t** d_metric, const uint32_t** d_nh, uint32_t* W,
                                      uint64_t* n_entries) {
-  if (const spf_status st = no_routes(p, "spf_whatif_routes_buffers"); st != SPF_OK) return st;
-  WiListsView v;
-  whatif_lists_view(p, &v);
-  const WiRoutes& r = *v.rt;
-  if (d_ptr) *d_ptr = reinterpret_cast<const uint64_t*>(r.d_rptr.p);
-  if (d_set) *d_set = r.d_rset.p;
-  if (d_metric) *d_metric = reinterpret_cast<const uint64_t*>(r.d_rmet.p);
-  if (d_nh) *d_nh = r.d_rnh.p;
-  if (W) *W = v.W;
-  if (n_entries) *n_entries = r.total;
-  return SPF_OK;
+  return pool_buffers(p, kPoolRoutes, "spf_whatif_routes_buffers", d_ptr, d_set, d_metric, d_nh, nullptr,
+                      W, n_entries);
 }
 
 spf_status spf_whatif_routes_base(spf_whatif_plan* p, uint64_t* min_metric, uint32_t* nh) {
-  if (const spf_status st = no_routes(p, "spf_whatif_routes_base"); st != SPF_OK) return st;
   WiListsView v;
-  whatif_lists_view(p, &v);
+  if (const spf_status st = pool_held(p, kPoolRoutes, "spf_whatif_routes_base", &v); st != SPF_OK) return st;
   spf_ctx* c = v.ctx;
   const WiRoutes& r = *v.rt;
   HIP_TRY(c, hipSetDevice(c->device));
@@ -544,53 +487,12 @@ spf_status spf_whatif_routes_base(spf_whatif_plan* p, uint64_t* min_metric, uint
 
 spf_status spf_whatif_routes_read(spf_whatif_plan* p, uint64_t* ptr, uint32_t* set, uint64_t* min_metric,
                                   uint32_t* nh) {
-  if (const spf_status st = no_routes(p, "spf_whatif_routes_read"); st != SPF_OK) return st;
-  WiListsView v;
-  whatif_lists_view(p, &v);
-  spf_ctx* c = v.ctx;
-  const WiRoutes& r = *v.rt;
-  HIP_TRY(c, hipSetDevice(c->device));
-  const size_t t = (size_t)r.total;
-  if (ptr) HIP_TRY(c, hipMemcpy(ptr, r.d_rptr.p, 8ull * ((size_t)v.n_fail + 1), hipMemcpyDeviceToHost));
-  if (set && t) HIP_TRY(c, hipMemcpy(set, r.d_rset.p, 4ull * t, hipMemcpyDeviceToHost));
-  if (min_metric && t) HIP_TRY(c, hipMemcpy(min_metric, r.d_rmet.p, 8ull * t, hipMemcpyDeviceToHost));
-  if (nh && t) HIP_TRY(c, hipMemcpy(nh, r.d_rnh.p, 4ull * t * v.W, hipMemcpyDeviceToHost));
-  return SPF_OK;
+  return pool_read(p, kPoolRoutes, "spf_whatif_routes_read", ptr, set, min_metric, nh);
 }
 
 spf_status spf_whatif_routes_db(spf_whatif_plan* p, uint32_t i, uint32_t* set, uint64_t* min_metric,
                                 uint32_t* nh, uint64_t cap, uint64_t* n) {
-  if (const spf_status st = no_routes(p, "spf_whatif_routes_db"); st != SPF_OK) return st;
-  WiListsView v;
-  whatif_lists_view(p, &v);
-  spf_ctx* c = v.ctx;
-  const WiRoutes& r = *v.rt;
-  if (i >= v.n_fail) return fail(c, SPF_E_INVALID, "spf_whatif_routes_db: failure %u of %u", i, v.n_fail);
-  HIP_TRY(c, hipSetDevice(c->device));
-  unsigned long long at[2] = {0, 0};
-  HIP_TRY(c, hipMemcpy(at, r.d_rptr.p + i, 16, hipMemcpyDeviceToHost));
-  if (at[1] < at[0] || at[1] > r.total) return fail(c, SPF_E_HIP, "spf_whatif_routes_db: offsets not monotone");
-  const size_t m = (size_t)(at[1] - at[0]), W = v.W;
-  if (n) *n = m;
-  if (!set && !min_metric && !nh) return SPF_OK;
-  if (cap < m) return fail(c, SPF_E_NOMEM, "spf_whatif_routes_db: %zu entries, room for %llu", m,
-                           (unsigned long long)cap);
-  if (!m) return SPF_OK;
-  std::vector<uint32_t> hs(m), hw(m * W);
-  std::vector<uint64_t> hm(m);
-  HIP_TRY(c, hipMemcpy(hs.data(), r.d_rset.p + at[0], 4 * m, hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(hm.data(), r.d_rmet.p + at[0], 8 * m, hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(hw.data(), r.d_rnh.p + at[0] * W, 4 * m * W, hipMemcpyDeviceToHost));
-  std::vector<size_t> order(m);  // the device order is the cursor's: ascending by set here
-  std::iota(order.begin(), order.end(), (size_t)0);
-  std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return hs[x] < hs[y]; });
-  for (size_t k = 0; k < m; ++k) {
-    const size_t q = order[k];
-    if (set) set[k] = hs[q];
-    if (min_metric) min_metric[k] = hm[q];
-    if (nh) std::memcpy(nh + k * W, hw.data() + q * W, 4 * W);
-  }
-  return SPF_OK;
+  return pool_db(p, kPoolRoutes, "spf_whatif_routes_db", i, set, min_metric, nh, cap, n);
 }
 
 }  // extern "C"

@@ -384,6 +384,30 @@ def _flat_sets(sets) -> Tuple[np.ndarray, np.ndarray]:
     return ptr, np.ascontiguousarray(flat, np.uint32)
 
 
+def _pool_read(err, read, h, n_owners: int, n_entries: int, last: np.ndarray):
+    """A list pool's ``_read`` call: (ptr[n_owners + 1] u64, key[n_entries] u32,
+    val[n_entries] u64) and `last`, the call's fourth array (the rows, or the
+    impact summaries), filled in place."""
+    ptr = np.zeros(n_owners + 1, np.uint64)
+    key, val = np.zeros(n_entries, np.uint32), np.zeros(n_entries, np.uint64)
+    err(read(h, N.ptr(ptr, C.c_uint64), N.ptr(key), N.ptr(val, C.c_uint64), N.ptr(last)))
+    return ptr, key, val, last
+
+
+def _pool_of(err, db, h, i: int, W: Optional[int] = None):
+    """A list pool's ``_db`` call for owner i, asking for the size first:
+    (key[n] u32, val[n] u64) and, for a pool with rows, rows[n, W]."""
+    n = C.c_uint64()
+    err(db(h, i, *([None] * (2 if W is None else 3)), 0, C.byref(n)))
+    m = int(n.value)
+    out = [np.zeros(m, np.uint32), np.zeros(m, np.uint64)]
+    out += [] if W is None else [np.zeros((m, W), np.uint32)]
+    if m:
+        err(db(h, i, N.ptr(out[0]), N.ptr(out[1], C.c_uint64), *[N.ptr(x) for x in out[2:]], m,
+               C.byref(n)))
+    return tuple(out)
+
+
 class WhatIfPlan(NativeHandle):
     """One source and a list of failures (``spf_whatif_plan``): single links
     (``kind == "link"``, ``links``), or nodes down / drained (``"down"`` /
@@ -528,12 +552,9 @@ class WhatIfChanges:
         w = C.c_uint32()
         eng._err(N.lib.spf_whatif_changes_buffers(plan._h, None, None, None, None, C.byref(w), None))
         self.W = int(w.value)
-        self.ptr = np.zeros(self.n_fail + 1, np.uint64)
-        self.node = np.zeros(self.n_entries, np.uint32)
-        self.dist = np.zeros(self.n_entries, np.uint64)
-        self.nh = np.zeros((self.n_entries, self.W), np.uint32)
-        eng._err(N.lib.spf_whatif_changes_read(plan._h, N.ptr(self.ptr, C.c_uint64), N.ptr(self.node),
-                                               N.ptr(self.dist, C.c_uint64), N.ptr(self.nh)))
+        self.ptr, self.node, self.dist, self.nh = _pool_read(
+            eng._err, N.lib.spf_whatif_changes_read, plan._h, self.n_fail, self.n_entries,
+            np.zeros((self.n_entries, self.W), np.uint32))
 
     def timing(self) -> Tuple[float, float, float]:
         """(count, scan, fill) ms of the call."""
@@ -543,16 +564,7 @@ class WhatIfChanges:
 
     def of(self, i: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Failure i's (node[n], dist[n], nh[n, W]), ascending by node."""
-        n = C.c_uint64()
-        err = self.plan._eng._err
-        err(N.lib.spf_whatif_changes_db(self.plan._h, i, None, None, None, 0, C.byref(n)))
-        m = int(n.value)
-        node, dist = np.zeros(m, np.uint32), np.zeros(m, np.uint64)
-        nh = np.zeros((m, self.W), np.uint32)
-        if m:
-            err(N.lib.spf_whatif_changes_db(self.plan._h, i, N.ptr(node), N.ptr(dist, C.c_uint64),
-                                            N.ptr(nh), m, C.byref(n)))
-        return node, dist, nh
+        return _pool_of(self.plan._eng._err, N.lib.spf_whatif_changes_db, self.plan._h, i, self.W)
 
     def routes(self, sets, stream: int = 0) -> "WhatIfRoutes":
         """Every failure's changed routes over the destination sets `sets`
@@ -597,12 +609,9 @@ class WhatIfRoutes:
                                          self.n_sets, C.byref(n), C.byref(nbytes), C.byref(ms),
                                          C.c_void_p(stream) if stream else None))
         self.n_entries, self.pool_bytes, self.kernel_ms = int(n.value), int(nbytes.value), ms.value
-        self.ptr = np.zeros(self.n_fail + 1, np.uint64)
-        self.set = np.zeros(self.n_entries, np.uint32)
-        self.min_metric = np.zeros(self.n_entries, np.uint64)
-        self.nh = np.zeros((self.n_entries, self.W), np.uint32)
-        eng._err(N.lib.spf_whatif_routes_read(h, N.ptr(self.ptr, C.c_uint64), N.ptr(self.set),
-                                              N.ptr(self.min_metric, C.c_uint64), N.ptr(self.nh)))
+        self.ptr, self.set, self.min_metric, self.nh = _pool_read(
+            eng._err, N.lib.spf_whatif_routes_read, h, self.n_fail, self.n_entries,
+            np.zeros((self.n_entries, self.W), np.uint32))
         self.base_metric = np.zeros(self.n_sets, np.uint64)
         self.base_nh = np.zeros((self.n_sets, self.W), np.uint32)
         eng._err(N.lib.spf_whatif_routes_base(h, N.ptr(self.base_metric, C.c_uint64),
@@ -616,16 +625,7 @@ class WhatIfRoutes:
 
     def of(self, i: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Failure i's (set[n], min_metric[n], nh[n, W]), ascending by set id."""
-        n = C.c_uint64()
-        err = self.plan._eng._err
-        err(N.lib.spf_whatif_routes_db(self.plan._h, i, None, None, None, 0, C.byref(n)))
-        m = int(n.value)
-        sets, metric = np.zeros(m, np.uint32), np.zeros(m, np.uint64)
-        nh = np.zeros((m, self.W), np.uint32)
-        if m:
-            err(N.lib.spf_whatif_routes_db(self.plan._h, i, N.ptr(sets), N.ptr(metric, C.c_uint64),
-                                           N.ptr(nh), m, C.byref(n)))
-        return sets, metric, nh
+        return _pool_of(self.plan._eng._err, N.lib.spf_whatif_routes_db, self.plan._h, i, self.W)
 
     def by_set(self, stream: int = 0) -> "WhatIfImpact":
         """These lists by destination set (``spf_whatif_by_set``): per set the
@@ -656,12 +656,9 @@ class WhatIfImpact:
         k = C.c_uint32()
         eng._err(self._call("_buffers")(h, None, None, None, None, C.byref(k), None))
         self.n_keys = int(k.value)
-        self.ptr = np.zeros(self.n_keys + 1, np.uint64)
-        self.fail = np.zeros(self.n_entries, np.uint32)
-        self.ent = np.zeros(self.n_entries, np.uint64)
-        self.impact = np.zeros(self.n_keys, IMPACT_DTYPE)
-        eng._err(self._call("_read")(h, N.ptr(self.ptr, C.c_uint64), N.ptr(self.fail),
-                                     N.ptr(self.ent, C.c_uint64), C.c_void_p(self.impact.ctypes.data)))
+        self.ptr, self.fail, self.ent, self.impact = _pool_read(
+            eng._err, self._call("_read"), h, self.n_keys, self.n_entries,
+            np.zeros(self.n_keys, IMPACT_DTYPE))
 
     def timing(self) -> Tuple[float, float, float]:
         """(count, scan, fill) ms of the call."""
@@ -672,14 +669,7 @@ class WhatIfImpact:
 
     def of(self, key: int) -> Tuple[np.ndarray, np.ndarray]:
         """Key `key`'s (fail[n], ent[n]), ascending by failure index."""
-        n = C.c_uint64()
-        err = self.plan._eng._err
-        err(self._call("_db")(self.plan._h, key, None, None, 0, C.byref(n)))
-        m = int(n.value)
-        fail, ent = np.zeros(m, np.uint32), np.zeros(m, np.uint64)
-        if m:
-            err(self._call("_db")(self.plan._h, key, N.ptr(fail), N.ptr(ent, C.c_uint64), m, C.byref(n)))
-        return fail, ent
+        return _pool_of(self.plan._eng._err, self._call("_db"), self.plan._h, key)
 
 
 class SpfEngine(NativeHandle):
@@ -915,17 +905,38 @@ class SpfEngine(NativeHandle):
                                          out.ctypes.data, base.ctypes.data))
         return arr, out[: len(arr)], base[0]
 
-    def whatif_changes(self, src: int, links: Optional[Sequence[int]] = None) -> WhatIfChanges:
-        """What each failure changes: the nodes whose metric or next hops
-        move under runSpf(src, true, {l}), with their new values, for each
-        failed link l (every up link when `links` is None).  close() the
-        result (it owns its plan)."""
-        plan = self.whatif_plan(src, links)
+    def _digests_of(self, plan: WhatIfPlan):
+        """(digests[n], base digest) of one execute of `plan`, which is closed."""
+        from .hiprt import DeviceArray, set_device
+
+        try:
+            set_device(self.device)
+            d_out = DeviceArray(max(1, plan.n_fail), DIGEST_DTYPE)
+            d_base = DeviceArray(1, DIGEST_DTYPE)
+            try:
+                plan.execute(d_out.ptr, d_base.ptr)
+                plan.stats()  # waits for the execute, checks the device's fault word
+                return d_out.numpy()[: plan.n_fail], d_base.numpy()[0]
+            finally:
+                d_out.free()
+                d_base.free()
+        finally:
+            plan.close()
+
+    def _owned_changes(self, plan: WhatIfPlan) -> WhatIfChanges:
+        """The change lists of `plan`, which they own (closed if they fail)."""
         try:
             return WhatIfChanges(plan, own_plan=True)
         except BaseException:
             plan.close()
             raise
+
+    def whatif_changes(self, src: int, links: Optional[Sequence[int]] = None) -> WhatIfChanges:
+        """What each failure changes: the nodes whose metric or next hops
+        move under runSpf(src, true, {l}), with their new values, for each
+        failed link l (every up link when `links` is None).  close() the
+        result (it owns its plan)."""
+        return self._owned_changes(self.whatif_plan(src, links))
 
     def whatif_routes(self, plan_or_changes, sets) -> WhatIfRoutes:
         """Which routes of the plan's source each failure changes, over the
@@ -955,33 +966,14 @@ class SpfEngine(NativeHandle):
     def whatif_nodes(self, src: int, nodes: Optional[Sequence[int]] = None, kind: str = "down"):
         """Digests of the SPF of `src` with each node of the list down or
         drained: (nodes, digests[n], base digest)."""
-        from .hiprt import DeviceArray, set_device
-
         plan = self.whatif_node_plan(src, nodes, kind)
-        try:
-            set_device(self.device)
-            d_out = DeviceArray(max(1, plan.n_fail), DIGEST_DTYPE)
-            d_base = DeviceArray(1, DIGEST_DTYPE)
-            try:
-                plan.execute(d_out.ptr, d_base.ptr)
-                plan.stats()  # waits for the execute, checks the device's fault word
-                return plan.nodes, d_out.numpy()[: plan.n_fail], d_base.numpy()[0]
-            finally:
-                d_out.free()
-                d_base.free()
-        finally:
-            plan.close()
+        return (plan.nodes, *self._digests_of(plan))
 
     def whatif_node_changes(self, src: int, nodes: Optional[Sequence[int]] = None,
                             kind: str = "down") -> WhatIfChanges:
         """What each node failure changes (``whatif_changes`` for nodes down
         or drained).  close() the result (it owns its plan)."""
-        plan = self.whatif_node_plan(src, nodes, kind)
-        try:
-            return WhatIfChanges(plan, own_plan=True)
-        except BaseException:
-            plan.close()
-            raise
+        return self._owned_changes(self.whatif_node_plan(src, nodes, kind))
 
     def whatif_set_plan(self, src: int, sets: Sequence[Sequence[int]]) -> WhatIfPlan:
         """A what-if plan whose failures are sets of links that fail together
@@ -991,32 +983,12 @@ class SpfEngine(NativeHandle):
     def whatif_sets(self, src: int, sets: Sequence[Sequence[int]]):
         """Digests of runSpf(src, true, set) for each set of links:
         (digests[n], base digest)."""
-        from .hiprt import DeviceArray, set_device
-
-        plan = self.whatif_set_plan(src, sets)
-        try:
-            set_device(self.device)
-            d_out = DeviceArray(max(1, plan.n_fail), DIGEST_DTYPE)
-            d_base = DeviceArray(1, DIGEST_DTYPE)
-            try:
-                plan.execute(d_out.ptr, d_base.ptr)
-                plan.stats()  # waits for the execute, checks the device's fault word
-                return d_out.numpy()[: plan.n_fail], d_base.numpy()[0]
-            finally:
-                d_out.free()
-                d_base.free()
-        finally:
-            plan.close()
+        return self._digests_of(self.whatif_set_plan(src, sets))
 
     def whatif_set_changes(self, src: int, sets: Sequence[Sequence[int]]) -> WhatIfChanges:
         """What each link-set failure changes (``whatif_changes`` for sets).
         close() the result (it owns its plan)."""
-        plan = self.whatif_set_plan(src, sets)
-        try:
-            return WhatIfChanges(plan, own_plan=True)
-        except BaseException:
-            plan.close()
-            raise
+        return self._owned_changes(self.whatif_set_plan(src, sets))
 
     def whatif_metric_plan(self, src: int, changes: Sequence[Sequence[int]]) -> WhatIfPlan:
         """A what-if plan whose failures are link metric changes (cost-out,
@@ -1028,32 +1000,12 @@ class SpfEngine(NativeHandle):
     def whatif_metrics(self, src: int, changes: Sequence[Sequence[int]]):
         """Digests of runSpf(src) under each metric change:
         (digests[n], base digest)."""
-        from .hiprt import DeviceArray, set_device
-
-        plan = self.whatif_metric_plan(src, changes)
-        try:
-            set_device(self.device)
-            d_out = DeviceArray(max(1, plan.n_fail), DIGEST_DTYPE)
-            d_base = DeviceArray(1, DIGEST_DTYPE)
-            try:
-                plan.execute(d_out.ptr, d_base.ptr)
-                plan.stats()  # waits for the execute, checks the device's fault word
-                return d_out.numpy()[: plan.n_fail], d_base.numpy()[0]
-            finally:
-                d_out.free()
-                d_base.free()
-        finally:
-            plan.close()
+        return self._digests_of(self.whatif_metric_plan(src, changes))
 
     def whatif_metric_changes(self, src: int, changes: Sequence[Sequence[int]]) -> WhatIfChanges:
         """What each link metric change changes (``whatif_changes`` for
         metric changes).  close() the result (it owns its plan)."""
-        plan = self.whatif_metric_plan(src, changes)
-        try:
-            return WhatIfChanges(plan, own_plan=True)
-        except BaseException:
-            plan.close()
-            raise
+        return self._owned_changes(self.whatif_metric_plan(src, changes))
 
     def sssp(self, src: int, hop: bool = False,
              ignore_links: Optional[Sequence[int]] = None) -> np.ndarray:
