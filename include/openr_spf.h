@@ -470,6 +470,120 @@ spf_status spf_ksp2_route_buffers(spf_ksp2_plan* plan, const uint64_t** d_rptr, 
                                   const uint64_t** d_lptr, const int32_t** d_lab, uint64_t* n_hops,
                                   uint64_t* n_label_words);
 
+/* ---- KSP2 route databases: snapshot, delta and update payload -------------- */
+/* DecisionRouteDb::calculateUpdate (Decision.cpp:111-146) over the routes of
+ * spf_ksp2_routes, for every source of a plan at once: the old generation held
+ * by an spf_ksp2_snapshot, the new one by a plan; the three calls mirror
+ * spf_mplan_route_snapshot / _delta / _update.
+ *
+ * spf_ksp2_route_snapshot: the device pools of the last successful
+ * spf_ksp2_routes on `plan` (rptr, rec, lptr, lab) move into *out -- nothing is
+ * copied -- and the plan holds no routes, exactly as after a failed call
+ * (spf_ksp2_route_db / _buffers: SPF_E_STATE; the next spf_ksp2_routes
+ * allocates afresh).  Kept by value: the plan's srcs, n_nodes, n_sets, the
+ * totals, and on the device key_old[e] = link_hash[link_id[e]] for every CSR
+ * edge of the graph as it is now.  link_hash[id] (n_links entries) names link
+ * `id` by value (LinkState.linkValueHashes()): records name CSR edges, row
+ * patches reorder slots and a reload may re-issue link ids, so only this key
+ * compares across generations.  The snapshot belongs to the plan's spf_ctx and
+ * outlives the plan, row patches and reloads; it is destroyed by
+ * spf_ksp2_route_snapshot_destroy or, at the latest, with the context.
+ * spf_ksp2_route_snapshot_bytes: the device memory it holds.  Waits.
+ * SPF_E_INVALID: a NULL argument, or n_links not covering every link id
+ * loaded.  SPF_E_STATE: the plan holds no routes, or the graph changed since
+ * the plan was created.  A refused call moves nothing. */
+typedef struct spf_ksp2_snapshot spf_ksp2_snapshot;
+spf_status spf_ksp2_route_snapshot(spf_ksp2_plan* plan, const uint64_t* link_hash, uint32_t n_links,
+                                   spf_ksp2_snapshot** out);
+void spf_ksp2_route_snapshot_destroy(spf_ksp2_snapshot* snap);
+uint64_t spf_ksp2_route_snapshot_bytes(const spf_ksp2_snapshot* snap);
+/* spf_ksp2_route_delta: the plan's current routes (new; the last
+ * spf_ksp2_routes) against the snapshot's (old).  A route's value is its set
+ * of next hops, a next hop the triple (key of its first-hop CSR edge in its
+ * own generation -- key_new is built by this call from link_hash and the
+ * current link ids --, cost, label stack as a sequence): what a NextHopThrift
+ * of the route is a function of.  spf_ksp2_routes de-duplicates within a
+ * generation, so each side is a set.  Route (i, p) is
+ *   unchanged  both sides have no next hop, or the sets are equal whatever
+ *              their order in the pools;
+ *   DELETE     only the old side has next hops;
+ *   UPDATE     the new side has next hops and the route is new or its set
+ *              differs.
+ * Node labels, prepend labels and set membership may differ between the
+ * generations: they show only through the stacks and next hops.
+ * Output on the device, resident until the next call (count, exclusive scan,
+ * fill as ordinary launches on the context's stream; no atomic per route):
+ *   dptr[n_src + 1] u64   source slot i's entries are dset[dptr[i] .. dptr[i + 1])
+ *   dset[total]     u32   the set index, | SPF_DELTA_DELETE on a delete,
+ *                         ascending within a source
+ * totals[3] = updates, deletes, routes decided by matching the next hops as
+ * sets (equal counts, but not equal position by position) -- optional, as is
+ * *kernel_ms = the three passes together.  The snapshot is only read: a second
+ * call gives byte-identical lists.  Waits.
+ * SPF_E_INVALID: a NULL plan / snap / link_hash, n_links not covering every
+ * link id loaded, the snapshot is another context's, the plan's srcs (same
+ * ids, same order), n_nodes or n_sets differ from the snapshot's (a changed
+ * node set shifts ids: out of scope, as for spf_mplan_route_delta), or n_sets
+ * >= 2^31.  SPF_E_STATE: the plan holds no routes, or the graph changed since
+ * they were built.  All checked before anything is launched; after a failed
+ * call the plan holds no delta (the _db / _buffers / update calls below:
+ * SPF_E_STATE). */
+spf_status spf_ksp2_route_delta(spf_ksp2_plan* plan, const spf_ksp2_snapshot* snap,
+                                const uint64_t* link_hash, uint32_t n_links, uint64_t* totals /* [3] */,
+                                double* kernel_ms);
+/* Source slot i's entries of the last spf_ksp2_route_delta: *n their number,
+ * set[cap] the entries (SPF_E_NOMEM with *n set when cap < *n; set may be NULL
+ * to ask for *n).  SPF_E_STATE without a delta.  Waits. */
+spf_status spf_ksp2_route_delta_db(spf_ksp2_plan* plan, uint32_t i, uint32_t* set, uint64_t cap,
+                                   uint64_t* n);
+/* The device lists of the last spf_ksp2_route_delta (valid until the next
+ * call on the plan); every output may be NULL.  SPF_E_STATE without a delta. */
+spf_status spf_ksp2_route_delta_buffers(spf_ksp2_plan* plan, const uint64_t** d_dptr,
+                                        const uint32_t** d_dset, uint64_t* n_entries);
+/* spf_ksp2_route_update: the payload of the last spf_ksp2_route_delta gathered
+ * out of the plan's current pools into contiguous, exactly sized pools
+ * parallel to dset (count, scan, fill; ordinary launches, no atomics):
+ *   uptr[total + 1]    u64  entry j's records are urec[uptr[j] .. uptr[j + 1])
+ *                           (a DELETE owns none)
+ *   urec[n_urec]       u64  the records as the database holds them (CSR edge |
+ *                           cost << 32), in pool order
+ *   ulptr[n_urec + 1]  u64  record k's stack is ulab[ulptr[k] .. ulptr[k + 1])
+ *   ulab[n_words]      i32
+ * totals[3] = update entries, records, label words; *pool_bytes = 8 (total +
+ * 1) + 8 n_urec + 8 (n_urec + 1) + 4 n_words; *kernel_ms = the passes
+ * together; all optional.  Waits.  SPF_E_STATE without a delta, or when the
+ * plan's routes are no longer the ones the delta compared (a later
+ * spf_ksp2_routes, or a snapshot that moved them away). */
+spf_status spf_ksp2_route_update(spf_ksp2_plan* plan, uint64_t* totals /* [3] */, uint64_t* pool_bytes,
+                                 double* kernel_ms);
+/* ms[6] = count, scan, fill of the last spf_ksp2_route_delta, then of the
+ * spf_ksp2_route_update of that delta (zeros while there is none).
+ * SPF_E_STATE without a delta. */
+spf_status spf_ksp2_route_delta_timing(const spf_ksp2_plan* plan, double* ms /* [6] */);
+/* Source slot i's payload of the last spf_ksp2_route_update, rebased to 0 and
+ * parallel to spf_ksp2_route_delta_db's entries (m of them): uptr = [m + 1],
+ * urec = its *n_rec records (rec_cap entries; SPF_E_NOMEM when fewer), ulptr =
+ * [*n_rec + 1] (needs rec_cap >= *n_rec as well), ulab = its *n_lab label
+ * words (lab_cap entries; SPF_E_NOMEM when fewer).  Any output may be NULL.
+ * SPF_E_STATE without an update.  Waits. */
+spf_status spf_ksp2_route_update_db(spf_ksp2_plan* plan, uint32_t i, uint64_t* uptr, uint64_t* urec,
+                                    uint64_t rec_cap, uint64_t* n_rec, uint64_t* ulptr, int32_t* ulab,
+                                    uint64_t lab_cap, uint64_t* n_lab);
+/* The whole payload in one copy per array: n[4] = source slots, entries,
+ * records, label words (ask with the arrays NULL first), then dptr[n[0] + 1],
+ * dset[n[1]], uptr[n[1] + 1], urec[n[2]], ulptr[n[2] + 1], ulab[n[3]].  Every
+ * output may be NULL.  SPF_E_STATE without an update.  Waits. */
+spf_status spf_ksp2_route_update_read(spf_ksp2_plan* plan, uint64_t* n /* [4] */, uint64_t* dptr,
+                                      uint32_t* dset, uint64_t* uptr, uint64_t* urec, uint64_t* ulptr,
+                                      int32_t* ulab);
+/* The device pools of the last spf_ksp2_route_update (valid until the next
+ * call on the plan); every output may be NULL.  SPF_E_STATE without an
+ * update. */
+spf_status spf_ksp2_route_update_buffers(spf_ksp2_plan* plan, const uint64_t** d_uptr,
+                                         const uint64_t** d_urec, const uint64_t** d_ulptr,
+                                         const int32_t** d_ulab, uint64_t* n_records,
+                                         uint64_t* n_label_words);
+
 /* ---- what-if batches: one source, every single-link failure -------------- */
 /* For each failed link l of the list: the reference's
  * runSpf(src, true, {l}) (LinkState.cpp:808-882 with linksToIgnore = {l}),

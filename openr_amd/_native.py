@@ -252,6 +252,19 @@ PROTOTYPES = {
                                     C.c_uint64, _u64p]),
     "spf_ksp2_route_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
                                          C.POINTER(_vp), _u64p, _u64p]),
+    "spf_ksp2_route_snapshot": (C.c_int, [_vp, _u64p, C.c_uint32, C.POINTER(_vp)]),
+    "spf_ksp2_route_snapshot_destroy": (None, [_vp]),
+    "spf_ksp2_route_snapshot_bytes": (C.c_uint64, [_vp]),
+    "spf_ksp2_route_delta": (C.c_int, [_vp, _vp, _u64p, C.c_uint32, _u64p, C.POINTER(C.c_double)]),
+    "spf_ksp2_route_delta_db": (C.c_int, [_vp, C.c_uint32, _u32p, C.c_uint64, _u64p]),
+    "spf_ksp2_route_delta_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
+    "spf_ksp2_route_update": (C.c_int, [_vp, _u64p, _u64p, C.POINTER(C.c_double)]),
+    "spf_ksp2_route_delta_timing": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "spf_ksp2_route_update_db": (C.c_int, [_vp, C.c_uint32, _u64p, _u64p, C.c_uint64, _u64p, _u64p, _i32p,
+                                           C.c_uint64, _u64p]),
+    "spf_ksp2_route_update_read": (C.c_int, [_vp, _u64p, _u64p, _u32p, _u64p, _u64p, _u64p, _i32p]),
+    "spf_ksp2_route_update_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
+                                                C.POINTER(_vp), _u64p, _u64p]),
     "spf_whatif_plan_create":(C.c_int, [_vp, C.c_uint32, _u32p, C.c_uint32, C.POINTER(_vp)]),
     "spf_whatif_plan_destroy": (None, [_vp]),
     "spf_whatif_plan_failures": (C.c_uint32, [_vp]),

@@ -148,6 +148,7 @@ void spf_ctx_destroy(spf_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   spf_plan_destroy(c->rt.plan);  // spf_routes' cached plan, before its context goes
   c->rt.plan = nullptr;
+  while (!c->ksp2_snaps.empty()) spf_ksp2_route_snapshot_destroy(c->ksp2_snaps.back());  // (each takes itself off the list)
   if (c->stream) {
     (void)hipStreamSynchronize(c->stream);
     (void)hipStreamDestroy(c->stream);

@@ -275,6 +275,8 @@ struct spf_ctx : spfi::GraphHost {
   // buffer, copies queued on `stream`, reused once `stream` has synchronised
   spfi::PinBuf<uint8_t> stage;
   size_t stage_used = 0;
+  // the open spf_ksp2_snapshot of this context (destroyed with it at the latest)
+  std::vector<spf_ksp2_snapshot*> ksp2_snaps;
   // spf_routes' (routes.hip) last plan, kept while its sources and the graph
   // shape hold (executes re-derive it after in-place patches), and its
   // buffers, which only grow: a route build per publication allocates nothing
@@ -415,6 +417,7 @@ constexpr uint32_t kKsp2Grab = 256;  // pool words a KSP2 wave reserves at a tim
 // pools (kept while they are large enough) and the last call's totals.
 struct Ksp2Routes {
   bool valid = false;  // a call succeeded and nothing failed since
+  uint64_t gen = 0;    // bumped by every spf_ksp2_routes and by a snapshot: which pools a delta compared
   uint32_t n_sets = 0;
   uint64_t hops = 0, words = 0;
   double ms[3] = {0, 0, 0};  // count, scan, fill of the last call
@@ -431,7 +434,43 @@ struct Ksp2Routes {
       if (e) (void)hipEventDestroy(e);
   }
 };
+
+// spf_ksp2_route_delta's and spf_ksp2_route_update's state
+// (ksp2_route_delta.hip): the lists and the payload pools of the last calls
+// (kept while they are large enough) and their scratch.
+struct Ksp2Delta {
+  bool valid = false;     // a delta succeeded and nothing failed since
+  bool up_valid = false;  // ... and an update of that delta
+  uint64_t gen = 0;       // Ksp2Routes::gen of the pools the delta compared
+  uint64_t entries = 0, tot[3] = {0, 0, 0};  // delta: updates, deletes, routes matched as sets
+  uint64_t up_tot[3] = {0, 0, 0};            // update: update entries, records, label words
+  double ms[6] = {0, 0, 0, 0, 0, 0};         // count, scan, fill of the delta, then of the update
+  DevBuf<unsigned long long> d_key;   // [E] key_new
+  DevBuf<uint8_t> d_kind;             // [n_routes]
+  DevBuf<unsigned long long> d_blk, d_sums, d_dptr, d_cnt;  // block counts, scan scratch, [n_src + 1], {deletes, matched, fault}
+  DevBuf<uint32_t> d_dset;            // [entries]
+  DevBuf<unsigned long long> d_uptr, d_usrc, d_urec, d_ulptr, d_ulsrc;  // [entries + 1], [entries], [records], [records + 1], [records]
+  DevBuf<int32_t> d_ulab;             // [label words]
+  hipEvent_t ev[13] = {};  // 0-4: the delta's marks; 5-12: the update's
+  ~Ksp2Delta() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
 }  // namespace spfi
+
+// A generation of KSP2 routes moved out of its plan (spf_ksp2_route_snapshot,
+// ksp2_route_delta.hip): the pools, their sizes, what the plan was over, and
+// key_old[e] = link_hash[link_id[e]] of the graph as it was.
+struct spf_ksp2_snapshot {
+  spf_ctx* ctx = nullptr;
+  std::vector<uint32_t> srcs;
+  uint32_t n_nodes = 0, n_sets = 0, n_edges = 0;
+  uint64_t hops = 0, words = 0;
+  spfi::DevBuf<unsigned long long> rptr, rec, lptr, key;
+  spfi::DevBuf<int32_t> lab;
+  ~spf_ksp2_snapshot();
+};
 
 struct spf_ksp2_plan {
   spf_ctx* ctx = nullptr;
@@ -456,6 +495,7 @@ struct spf_ksp2_plan {
   // than 65535 nodes or a working set past the LDS): the exact kernel
   std::unique_ptr<spfi::ExactKsp2> exact;
   spfi::Ksp2Routes rt;  // spf_ksp2_routes (ksp2_routes.hip)
+  spfi::Ksp2Delta dl;   // spf_ksp2_route_delta / _update (ksp2_route_delta.hip)
   ~spf_ksp2_plan() {
     for (hipEvent_t e : ev) (void)hipEventDestroy(e);
   }

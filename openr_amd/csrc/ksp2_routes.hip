@@ -326,6 +326,7 @@ spf_status spf_ksp2_routes(spf_ksp2_plan* p, const spf_ksp2_pair* d_pairs, const
   spf_ctx* c = p->ctx;
   Ksp2Routes& rt = p->rt;
   rt.valid = false;
+  ++rt.gen;  // (a delta of the previous pools has no payload to gather any more)
   if (!d_pairs || !d_pool || !set_ptr || !node_label)
     return fail(c, SPF_E_INVALID, "spf_ksp2_routes: NULL argument");
   if (!c->loaded) return fail(c, SPF_E_STATE, "graph no longer loaded");

@@ -316,6 +316,119 @@ class Ksp2Plan(NativeHandle):
                                                     C.byref(hops), C.byref(words)))
         return tuple(int(x.value or 0) for x in p) + (hops.value, words.value)
 
+    # ---- snapshot, delta and update payload of the routes (ksp2_route_delta.hip) ----
+    def route_snapshot(self, link_hash) -> "Ksp2RouteSnapshot":
+        """The routes of the last routes() kept as the old generation of a
+        later route_delta (spf_ksp2_route_snapshot): the device pools move into
+        the snapshot, nothing is copied, and the plan holds no routes until the
+        next routes().  link_hash: u64 per link id, the link's identity by
+        value (LinkState.linkValueHashes())."""
+        lh = np.ascontiguousarray(link_hash, np.uint64)
+        h = C.c_void_p()
+        self._eng._err(N.lib.spf_ksp2_route_snapshot(self._h, N.ptr(lh, C.c_uint64), len(lh), C.byref(h)))
+        self._rt_sets = None
+        return self._eng._track(Ksp2RouteSnapshot(self._eng, h, self.srcs.copy()))
+
+    def route_delta(self, snap: "Ksp2RouteSnapshot", link_hash):
+        """The routes of the last routes() against `snap`
+        (spf_ksp2_route_delta): (dptr u64 [n_src + 1], dset u32 -- source slot
+        i's entries are dset[dptr[i]:dptr[i + 1]], the set index |
+        SPF_DELTA_DELETE on a delete, ascending --, totals [updates, deletes,
+        routes matched as sets], kernel ms)."""
+        lh = np.ascontiguousarray(link_hash, np.uint64)
+        tot, ms = np.zeros(3, np.uint64), C.c_double()
+        self._eng._err(N.lib.spf_ksp2_route_delta(self._h, snap._h, N.ptr(lh, C.c_uint64), len(lh),
+                                                  N.ptr(tot, C.c_uint64), C.byref(ms)))
+        from .hiprt import read_device
+
+        d_dptr, d_dset, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        self._eng._err(N.lib.spf_ksp2_route_delta_buffers(self._h, C.byref(d_dptr), C.byref(d_dset),
+                                                          C.byref(n)))
+        # (the call has waited for the context's stream)
+        dptr = read_device(int(d_dptr.value), len(self.srcs) + 1, np.uint64)
+        dset = read_device(int(d_dset.value), n.value, np.uint32)
+        return dptr, dset, [int(v) for v in tot], ms.value
+
+    def route_delta_db(self, i: int) -> np.ndarray:
+        """Source slot i's entries of the last route_delta (spf_ksp2_route_delta_db)."""
+        n = C.c_uint64()
+        self._eng._err(N.lib.spf_ksp2_route_delta_db(self._h, int(i), None, 0, C.byref(n)))
+        out = np.zeros(max(1, n.value), np.uint32)
+        self._eng._err(N.lib.spf_ksp2_route_delta_db(self._h, int(i), N.ptr(out), n.value, None))
+        return out[: n.value]
+
+    def route_delta_timing(self) -> Tuple[float, ...]:
+        """(count, scan, fill) ms of the last route_delta, then of its
+        route_update (spf_ksp2_route_delta_timing)."""
+        ms = (C.c_double * 6)()
+        self._eng._err(N.lib.spf_ksp2_route_delta_timing(self._h, ms))
+        return tuple(ms)
+
+    def route_update(self):
+        """The payload of the last route_delta gathered on the GPU
+        (spf_ksp2_route_update) and read back in one copy per array: (dptr,
+        dset, uptr u64 [entries + 1], urec u64, ulptr u64 [records + 1], ulab
+        i32, totals [update entries, records, label words], pool bytes, kernel
+        ms): entry j's records are urec[uptr[j]:uptr[j + 1]] (a delete owns
+        none), record k's label stack is ulab[ulptr[k]:ulptr[k + 1]]."""
+        tot, nbytes, ms = np.zeros(3, np.uint64), C.c_uint64(), C.c_double()
+        self._eng._err(N.lib.spf_ksp2_route_update(self._h, N.ptr(tot, C.c_uint64), C.byref(nbytes),
+                                                   C.byref(ms)))
+        n = np.zeros(4, np.uint64)
+        self._eng._err(N.lib.spf_ksp2_route_update_read(self._h, N.ptr(n, C.c_uint64), *([None] * 6)))
+        ns, ne, nr, nw = (int(v) for v in n)
+        dptr, dset = np.zeros(ns + 1, np.uint64), np.zeros(max(1, ne), np.uint32)
+        uptr, urec = np.zeros(ne + 1, np.uint64), np.zeros(max(1, nr), np.uint64)
+        ulptr, ulab = np.zeros(nr + 1, np.uint64), np.zeros(max(1, nw), np.int32)
+        self._eng._err(N.lib.spf_ksp2_route_update_read(
+            self._h, None, N.ptr(dptr, C.c_uint64), N.ptr(dset), N.ptr(uptr, C.c_uint64),
+            N.ptr(urec, C.c_uint64), N.ptr(ulptr, C.c_uint64), N.ptr(ulab, C.c_int32)))
+        return (dptr, dset[:ne], uptr, urec[:nr], ulptr, ulab[:nw], [int(v) for v in tot],
+                int(nbytes.value), ms.value)
+
+    def route_update_db(self, i: int):
+        """Source slot i's payload of the last route_update, rebased to 0 and
+        parallel to route_delta_db(i): (uptr, urec, ulptr, ulab)
+        (spf_ksp2_route_update_db)."""
+        m = len(self.route_delta_db(i))
+        n_rec, n_lab = C.c_uint64(), C.c_uint64()
+        uptr = np.zeros(m + 1, np.uint64)
+        self._eng._err(N.lib.spf_ksp2_route_update_db(self._h, int(i), N.ptr(uptr, C.c_uint64), None, 0,
+                                                      C.byref(n_rec), None, None, 0, C.byref(n_lab)))
+        urec = np.zeros(max(1, n_rec.value), np.uint64)
+        ulptr = np.zeros(n_rec.value + 1, np.uint64)
+        ulab = np.zeros(max(1, n_lab.value), np.int32)
+        self._eng._err(N.lib.spf_ksp2_route_update_db(self._h, int(i), None, N.ptr(urec, C.c_uint64),
+                                                      n_rec.value, None, N.ptr(ulptr, C.c_uint64),
+                                                      N.ptr(ulab, C.c_int32), n_lab.value, None))
+        return uptr, urec[: n_rec.value], ulptr, ulab[: n_lab.value]
+
+    def route_update_buffers(self) -> Tuple[int, int, int, int, int, int]:
+        """Device addresses (uptr, urec, ulptr, ulab) of the last route_update
+        and its (records, label words) (spf_ksp2_route_update_buffers)."""
+        p = [C.c_void_p() for _ in range(4)]
+        nr, nw = C.c_uint64(), C.c_uint64()
+        self._eng._err(N.lib.spf_ksp2_route_update_buffers(self._h, *[C.byref(x) for x in p],
+                                                           C.byref(nr), C.byref(nw)))
+        return tuple(int(x.value or 0) for x in p) + (nr.value, nw.value)
+
+
+class Ksp2RouteSnapshot(NativeHandle):
+    """One generation of KSP2 routes moved out of its plan
+    (``spf_ksp2_snapshot``, from Ksp2Plan.route_snapshot): owned by the engine
+    context, it outlives the plan, row patches and reloads; ``close()`` (or
+    the engine's) releases its device pools."""
+
+    _destroy = "spf_ksp2_route_snapshot_destroy"
+
+    def __init__(self, eng: "SpfEngine", h: C.c_void_p, srcs: np.ndarray) -> None:
+        self._eng = eng
+        self.srcs = srcs
+        self._adopt(h)
+
+    def bytes(self) -> int:
+        return int(N.lib.spf_ksp2_route_snapshot_bytes(self._h))
+
 
 class Ksp2Routes:
     """Every source's KSP2_ED_ECMP next hops (SpfEngine.ksp2_routes): the plan
@@ -345,6 +458,47 @@ class Ksp2Routes:
             out.append((r & 0xFFFFFFFF, r >> 32,
                         tuple(int(x) for x in lab[int(lptr[h]): int(lptr[h + 1])])))
         return out
+
+    def snapshot(self, link_hash) -> "Ksp2RouteSnapshot":
+        """These routes kept as the old generation of a later delta
+        (Ksp2Plan.route_snapshot): the pools move into the snapshot and db() /
+        nexthops() of this object raise SPF_E_STATE from then on."""
+        self._dbs = {}
+        return self.plan.route_snapshot(link_hash)
+
+    def delta(self, snap: "Ksp2RouteSnapshot", link_hash, update: bool = True):
+        """These routes (new) against `snap` (old): per source slot a tuple
+        (updated sets, deleted sets, {updated set: [(CSR edge, cost, label
+        stack)]}) -- ascending int lists; the dict is empty with update=False
+        --, the delta's totals [updates, deletes, routes matched as sets], and
+        a dict of figures (kernel ms of both calls, phase ms, pool bytes, the
+        update's totals)."""
+        D, M = N.SPF_DELTA_DELETE, N.SPF_DELTA_DELETE - 1
+        dptr, dset, totals, ms = self.plan.route_delta(snap, link_hash)
+        info = {"delta_ms": ms}
+        payload = None
+        if update:
+            dptr, dset, uptr, urec, ulptr, ulab, utot, nbytes, ums = self.plan.route_update()
+            info.update(update_ms=ums, pool_bytes=nbytes, update_totals=utot)
+            payload = (uptr.tolist(), urec.tolist(), ulptr.tolist(), ulab.tolist())
+        info["phase_ms"] = list(self.plan.route_delta_timing())
+        out = []
+        ent = dset.tolist()
+        at = dptr.tolist()
+        for i in range(len(self.srcs)):
+            up, dele, pay = [], [], {}
+            for j in range(int(at[i]), int(at[i + 1])):
+                v = ent[j]
+                if v & D:
+                    dele.append(v & M)
+                    continue
+                up.append(v)
+                if payload is not None:
+                    uptr, urec, ulptr, ulab = payload
+                    pay[v] = [(urec[k] & 0xFFFFFFFF, urec[k] >> 32, tuple(ulab[ulptr[k]: ulptr[k + 1]]))
+                              for k in range(uptr[j], uptr[j + 1])]
+            out.append((up, dele, pay))
+        return out, totals, info
 
     def close(self) -> None:
         self.plan.close()

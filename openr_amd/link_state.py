@@ -850,20 +850,89 @@ class LinkState(N.NativeHandle):
         the node, PUSH of the label stack unless it is empty -- what
         ``SpfSolver._ksp2NextHops`` returns for the same node, advertisers and
         prefix entries."""
-        from .spf_solver import MplsAction, createNextHop
-
         if self._k2r is None or self._k2r[4] != self._gen:
             raise RuntimeError("allSourcesKsp2NextHops: no routes (call allSourcesKsp2Routes)")
         r, mes, names, lid, _ = self._k2r
-        me = names[mes[int(t)]]
+        return self._ksp2_thrift(names[mes[int(t)]], lid, r.nexthops(int(t), int(p)), isV4)
+
+    def _ksp2_thrift(self, me: str, lid, hops, isV4: bool):
+        """[(CSR edge, cost, label stack)] of one of me's KSP2 routes as its
+        set of NextHopThrift."""
+        from .spf_solver import MplsAction, createNextHop
+
         nhs = set()
-        for e, cost, labels in r.nexthops(int(t), int(p)):
+        for e, cost, labels in hops:
             link = self._link(int(lid[e]))
             addr = link.getNhV4FromNode(me) if isV4 else link.getNhV6FromNode(me)
             action = MplsAction("PUSH", None, tuple(labels)) if labels else None
             nhs.add(createNextHop(addr, link.getIfaceFromNode(me), cost, action, link.getArea(),
                                   link.getOtherNodeName(me)))
         return nhs
+
+    def _ksp2_current(self, who: str, snapshot):
+        if self._k2r is None or self._k2r[4] != self._gen:
+            raise RuntimeError(f"{who}: no routes (call allSourcesKsp2Routes)")
+        if snapshot is not None and (snapshot.closed or snapshot not in self._snaps):
+            raise ValueError(f"{who}: not an open snapshot of this LinkState")
+        return self._k2r[0]
+
+    def allSourcesKsp2RouteSnapshot(self) -> "Ksp2RouteSnapshot":
+        """The routes of the last allSourcesKsp2Routes kept as the old
+        generation of a later allSourcesKsp2RouteDelta
+        (spf_ksp2_route_snapshot): the device pools move into the snapshot,
+        nothing is copied, and allSourcesKsp2RouteDb / NextHops raise
+        SPF_E_STATE until the next allSourcesKsp2Routes.  Links are identified
+        by linkValueHashes() as of now.  The snapshot survives this LinkState
+        dropping its routes (a row patch, a reload, the next
+        allSourcesKsp2Routes); it is closed with the LinkState at the latest,
+        before the engine context."""
+        r = self._ksp2_current("allSourcesKsp2RouteSnapshot", None)
+        snap = r.snapshot(self.linkValueHashes())
+        self._snaps.add(snap)
+        return snap
+
+    def allSourcesKsp2RouteDelta(self, snapshot: "Ksp2RouteSnapshot"):
+        """What changed since `snapshot` in every node's KSP2 routes
+        (spf_ksp2_route_delta: DecisionRouteDb::calculateUpdate,
+        Decision.cpp:111-146, for every node on the GPU): the current routes --
+        allSourcesKsp2Routes called again with the snapshot's node list and as
+        many sets -- against the snapshot's.  A route's value is its set of
+        next hops (link by value, cost, label stack).  Returns (per node t a
+        pair (updated sets, deleted sets) of ascending int lists, totals
+        [updates, deletes, routes compared as sets], kernel ms)."""
+        r = self._ksp2_current("allSourcesKsp2RouteDelta", snapshot)
+        out, totals, info = r.delta(snapshot, self.linkValueHashes(), update=False)
+        return [(u, d) for u, d, _ in out], totals, info["delta_ms"]
+
+    def allSourcesKsp2RouteUpdate(self, snapshot: "Ksp2RouteSnapshot"):
+        """allSourcesKsp2RouteDelta(snapshot) with its payload
+        (spf_ksp2_route_update: what a DecisionRouteUpdate carries besides the
+        routes' names): returns the delta's (lists, totals, kernel ms), then
+        per node t a dict {updated set: [(CSR edge, cost, label stack)]} -- the
+        next hops as allSourcesKsp2RouteDb holds them, gathered on the GPU into
+        one exactly sized pool, read back in one copy per array and split
+        here -- and a dict of the update's own figures: update_totals [update
+        entries, records, label words], pool_bytes, update_ms, phase_ms [count,
+        scan, fill of the delta, then of the update].
+        allSourcesKsp2DecisionRouteUpdate turns a node's part into
+        NextHopThrift values."""
+        r = self._ksp2_current("allSourcesKsp2RouteUpdate", snapshot)
+        out, totals, info = r.delta(snapshot, self.linkValueHashes(), update=True)
+        self._k2u = ([p for _, _, p in out], [d for _, d, _ in out], self._gen)
+        return [(u, d) for u, d, _ in out], totals, info["delta_ms"], self._k2u[0], info
+
+    def allSourcesKsp2DecisionRouteUpdate(self, t: int, isV4: bool = False):
+        """Node mes[t]'s part of the last allSourcesKsp2RouteUpdate as the
+        pieces of a DecisionRouteUpdate: ({updated set: set of NextHopThrift},
+        the deleted sets) -- the next hops as allSourcesKsp2NextHops builds
+        them."""
+        k2u = getattr(self, "_k2u", None)
+        if k2u is None or k2u[2] != self._gen or self._k2r is None:
+            raise RuntimeError("allSourcesKsp2DecisionRouteUpdate: no update (call allSourcesKsp2RouteUpdate)")
+        _, mes, names, lid, _ = self._k2r
+        me = names[mes[int(t)]]
+        return ({p: self._ksp2_thrift(me, lid, hops, isV4) for p, hops in k2u[0][int(t)].items()},
+                list(k2u[1][int(t)]))
 
     def _close_ksp2_routes(self) -> None:
         k2r = getattr(self, "_k2r", None)
