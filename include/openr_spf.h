@@ -1213,7 +1213,8 @@ spf_status spf_label_groups(const int32_t* node_label, uint32_t n_nodes, int32_t
  *          finite distance in me's row; SPF_UNREACHABLE: none, no route.  (The
  *          reference's collision loop, :605-618 with the no-route skip at
  *          :641-647, gives this whatever order it visits the nodes in: a
- *          smaller name replaces the holder only when it has a route.)
+ *          smaller name replaces the holder only when it has a route.  The
+ *          host SpfSolvers' buildRouteDb resolves a collision the same way.)
  *   owner == me: POP_AND_LOOKUP (:620-633), no records.
  *   otherwise the next hops of getNextHopsWithMetric(me, {owner}) +
  *          getNextHopsThrift (:635-668; the selection of spf_mplan_route_records

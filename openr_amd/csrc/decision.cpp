@@ -1263,16 +1263,22 @@ spf_status dc_build_route_db(dc_solver* s, const char* const* area_names, ls_sta
 
   phase(1);
   // ---- node labels (:583-664) ----
-  // label -> (node, area), the collision rule of :605-617 (the smaller name wins)
+  // label -> its candidates (node, area) in walk order: areas in map order,
+  // names ascending within an area.  The collision rule of :605-668 is
+  // resolved per label below, once each candidate's route is known: a
+  // candidate installs only if it is me or has next hops.
   struct LabelOwner {
     uint32_t node;  // name id in `area`
     Area* area;
-    std::string name() const { return ls_name(area->ls, node); }
+    uint32_t next;  // the label's next candidate in `more`, ~0u = none
+    uint32_t last;  // (a label's first candidate only) the chain's end in `more`, ~0u = itself
+    const char* name() const { return ls_name(area->ls, node); }
   };
-  // labels in first-seen order with their owners; label -> position by open
-  // addressing (one slot per label, no node allocation per label)
+  // labels in first-seen order with their first candidates; label -> position
+  // by open addressing (one slot per label, no node allocation per label).
+  // Further candidates of a shared label chain through `more`.
   std::vector<int32_t> label_order;
-  std::vector<LabelOwner> owner;
+  std::vector<LabelOwner> owner, more;
   std::vector<uint32_t> lpos;  // position + 1, 0 = empty
   auto lslot = [&](int32_t top) {
     const size_t mask = lpos.size() - 1;
@@ -1301,15 +1307,38 @@ spf_status dc_build_route_db(dc_solver* s, const char* const* area_names, ls_sta
       uint32_t& pos = lpos[lslot(top)];
       if (!pos) {
         label_order.push_back(top);
-        owner.push_back({ids[i], &a});
+        owner.push_back({ids[i], &a, ~0u, ~0u});
         pos = (uint32_t)label_order.size();
-      } else {
-        LabelOwner& o = owner[pos - 1];
-        if (!(std::strcmp(ls_name(o.area->ls, o.node), ls_name(a.ls, ids[i])) < 0))
-          o = {ids[i], &a};  // the collision's smaller name wins (a tie: the later area)
+      } else {  // a shared label (rare): appended to the label's chain
+        LabelOwner& first = owner[pos - 1];
+        const uint32_t at = (uint32_t)more.size();
+        (first.last == ~0u ? first.next : more[first.last].next) = at;
+        first.last = at;
+        more.push_back({ids[i], &a, ~0u, ~0u});
       }
     }
   }
+  // One label's walk (:609-668) over its candidates.  route(c) answers
+  // whether a candidate that is not me has next hops, and keeps them when it
+  // has; it is asked for every such candidate the reference would ask for.
+  // Returns the entry left standing, nullptr when there is none.
+  auto resolve_label = [&](const LabelOwner& first, auto&& is_me, auto&& skip,
+                           auto&& route) -> const LabelOwner* {
+    const LabelOwner* cur = nullptr;
+    for (const LabelOwner* c = &first;; c = &more[c->next]) {
+      bool visit = true;
+      if (cur) {
+        s->bump("decision.duplicate_node_label");
+        visit = !(std::strcmp(cur->name(), c->name()) < 0);  // (a tie: the later area's entry)
+      }
+      if (!visit) skip(*c);
+      else if (is_me(*c)) cur = c;
+      else if (route(*c)) cur = c;
+      else s->bump("decision.no_route_to_label");
+      if (c->next == ~0u) break;
+    }
+    return cur;
+  };
 
   if (single) {
     // ---- one batched selection: IP prefixes, then node labels ----
@@ -1317,8 +1346,8 @@ spf_status dc_build_route_db(dc_solver* s, const char* const* area_names, ls_sta
     GraphCache* g = nullptr;
     if (const spf_status c = graph_cache(s, a.ls, g); c != SPF_OK) return c;
     std::vector<uint32_t> set_ptr{0}, set_nodes;
-    set_ptr.reserve(uni.size() + label_order.size() + 1);
-    set_nodes.reserve(uni.size() + label_order.size());
+    set_ptr.reserve(uni.size() + label_order.size() + more.size() + 1);
+    set_nodes.reserve(uni.size() + label_order.size() + more.size());
     auto add_node = [&](uint32_t id) {
       if (id < g->csr_of.size() && g->csr_of[id] != ~0u) set_nodes.push_back(g->csr_of[id]);
     };
@@ -1326,10 +1355,17 @@ spf_status dc_build_route_db(dc_solver* s, const char* const* area_names, ls_sta
       for (EntryRef r : u.res->refs) add_node(a.id(*r));
       set_ptr.push_back((uint32_t)set_nodes.size());
     }
-    for (const LabelOwner& o : owner) {  // labels needing a selection, in set order
-      if (o.node == a.me_id) continue;
-      add_node(o.node);
-      set_ptr.push_back((uint32_t)set_nodes.size());
+    // labels needing a selection, in set order: one set per candidate that is
+    // not me (never one set of all candidates: that would select the nearest
+    // one, and the rule wants the smallest routed name)
+    for (const LabelOwner& first : owner) {
+      for (const LabelOwner* o = &first;; o = &more[o->next]) {
+        if (o->node != a.me_id) {
+          add_node(o->node);
+          set_ptr.push_back((uint32_t)set_nodes.size());
+        }
+        if (o->next == ~0u) break;
+      }
     }
     const uint32_t n_sets = (uint32_t)set_ptr.size() - 1;
     phase(2);
@@ -1461,29 +1497,38 @@ spf_status dc_build_route_db(dc_solver* s, const char* const* area_names, ls_sta
     db->mpls.reserve(db->mpls.size() + 3 * label_order.size());
     for (size_t li = 0; li < label_order.size(); ++li) {
       const int32_t top = label_order[li];
-      const LabelOwner& own = owner[li];
-      if (own.node == a.me_id) {
+      // every candidate that is not me owns the next selection set, whether
+      // the walk asks for it or passes it by
+      uint32_t won = 0;  // the standing entry's set (unused for me)
+      const LabelOwner* own = resolve_label(
+          owner[li], [&](const LabelOwner& c) { return c.node == a.me_id; },
+          [&](const LabelOwner& c) { k += c.node != a.me_id; },
+          [&](const LabelOwner&) {
+            const uint32_t i = k++;
+            if (!sel.cnt[i]) return false;
+            won = i;
+            return true;
+          });
+      if (!own) continue;
+      if (own->node == a.me_id) {
         NH h;  // POP_AND_LOOKUP, address "::"
         h.action = DC_MPLS_POP_AND_LOOKUP;
-        h.area = own.area->name;
+        h.area = own->area->name;
         std::vector<NH> v{h};
         db->add_mpls(top, db->add_set(v));
         continue;
       }
-      const uint32_t i = k++;
-      const uint32_t c = sel.cnt[i];
-      if (!c) {
-        s->bump("decision.no_route_to_label");
-        continue;
-      }
-      const size_t o = (size_t)i * sel.deg;
+      // (only the standing entry's selection becomes records: a passed-by
+      // candidate's edges reach no route)
+      const uint32_t c = sel.cnt[won];
+      const size_t o = (size_t)won * sel.deg;
       recs.clear();
       for (uint32_t q = 0; q < c; ++q) {
         const LinkRec* r = edge_rec(sel.edge[o + q]);
         if (!r) return sfail(s, SPF_E_INVALID, "selected edge %u is not a link of %s", sel.edge[o + q], me.c_str());
         dc_nexthop x = r->v6;
         x.metric = i32_metric(sel.metric[o + q]);
-        if (r->nb_id == own.node) {
+        if (r->nb_id == own->node) {
           x.mpls_action = DC_MPLS_PHP;
         } else {
           x.mpls_action = DC_MPLS_SWAP;
@@ -1496,25 +1541,27 @@ spf_status dc_build_route_db(dc_solver* s, const char* const* area_names, ls_sta
   } else {
     for (size_t li = 0; li < label_order.size(); ++li) {
       const int32_t top = label_order[li];
-      const LabelOwner& own = owner[li];
-      const std::string node = own.name();
-      if (node == me) {
+      // the route is computed before the candidate is recorded: one without
+      // next hops leaves the earlier entry standing (:641-647)
+      std::vector<NH> v;
+      const LabelOwner* own = resolve_label(
+          owner[li], [&](const LabelOwner& c) { return me == c.name(); }, [](const LabelOwner&) {},
+          [&](const LabelOwner& c) {
+            if (!b.ok()) return false;
+            const std::vector<NodeArea> dst{{c.name(), c.area->name}};
+            auto [mn, nhn] = b.nexthops_with_metric(dst, false);
+            if (!b.ok() || nhn.empty()) return false;
+            v = b.nexthops_thrift(dst, false, false, mn, nhn, top, nullptr);
+            return b.ok();
+          });
+      if (!b.ok()) return b.st;
+      if (!own) continue;
+      if (me == own->name()) {
         NH h;
         h.action = DC_MPLS_POP_AND_LOOKUP;
-        h.area = own.area->name;
-        std::vector<NH> v{h};
-        db->add_mpls(top, db->add_set(v));
-        continue;
+        h.area = own->area->name;
+        v.assign(1, h);
       }
-      const std::vector<NodeArea> dst{{node, own.area->name}};
-      auto [mn, nhn] = b.nexthops_with_metric(dst, false);
-      if (!b.ok()) return b.st;
-      if (nhn.empty()) {
-        s->bump("decision.no_route_to_label");
-        continue;
-      }
-      std::vector<NH> v = b.nexthops_thrift(dst, false, false, mn, nhn, top, nullptr);
-      if (!b.ok()) return b.st;
       db->add_mpls(top, db->add_set(v));
     }
   }

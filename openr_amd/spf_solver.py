@@ -661,7 +661,8 @@ class NativeRouteDb(N.NativeHandle):
 
 
 _COUNTERS = ("decision.no_route_to_prefix", "decision.skipped_unicast_route",
-             "decision.no_route_to_label", "decision.incompatible_forwarding_type")
+             "decision.no_route_to_label", "decision.incompatible_forwarding_type",
+             "decision.duplicate_node_label")
 
 
 class SpfSolver:
@@ -1299,8 +1300,10 @@ class SpfSolver:
                     if top == 0 or not isMplsLabelValid(top):
                         continue
                     cur = labelToNode.get(top)
-                    if cur is not None and cur[0] < node:
-                        continue
+                    if cur is not None:
+                        self._bump("decision.duplicate_node_label")
+                        if cur[0] < node:
+                            continue
                     if node == me:
                         labelToNode[top] = (node, RibMplsEntry(top, {NextHopThrift(
                             bytes(16), None, 0, MplsAction("POP_AND_LOOKUP"), area, None)}))
@@ -1335,17 +1338,18 @@ class SpfSolver:
         kernel call (spf_routes), SR_MPLS prefixes over the memoised SPF /
         one batched KSP2 launch."""
         labels = ls.getAdjacencyDatabaseLabels()
-        # ---- node labels (collisions: Decision.cpp:605-617) ----
-        label_to_node: Dict[int, str] = {}
+        # ---- node labels: each label's candidates in walk order (names
+        # ascending), labels in first-seen order.  Every candidate gets a
+        # selection set of its own (one set of all candidates would select the
+        # nearest, not the smallest routed name); the collision rule of
+        # Decision.cpp:605-668 is resolved below, once the counts are known
+        label_to_nodes: Dict[int, List[str]] = {}
         for node, label in labels.items():
             if label == 0 or not isMplsLabelValid(label):
                 continue
-            prev = label_to_node.get(label)
-            if prev is not None and prev < node:
-                continue
-            label_to_node[label] = node
+            label_to_nodes.setdefault(label, []).append(node)
 
-        sets = [u[2] for u in uni] + [[n] for n in label_to_node.values()]
+        sets = [u[2] for u in uni] + [[n] for cands in label_to_nodes.values() for n in cands]
         sel = self._select(ls, me, sets)
 
         # IP routes with the same (link, metric) selection share one frozen
@@ -1414,15 +1418,30 @@ class SpfSolver:
         info = self._link_fields(ls, me)
         mk = tuple.__new__
         mpls = db.mplsRoutes
-        for k, (label, node) in enumerate(label_to_node.items()):
+        k0 = 0
+        for label, cands in label_to_nodes.items():
+            # the walk of :609-668 over this label's candidates: one installs
+            # only if it is me or has next hops, a larger name than the
+            # standing entry's is passed by (only the standing entry's
+            # selection is read: a passed-by candidate's reaches no route)
+            node, k = None, k0
+            for j, cand in enumerate(cands, k0):
+                if node is not None:
+                    self._bump("decision.duplicate_node_label")
+                    if node < cand:
+                        continue
+                if cand == me or cnt_l[j]:
+                    node, k = cand, j
+                else:
+                    self._bump("decision.no_route_to_label")
+            k0 += len(cands)
+            if node is None:
+                continue
             if node == me:
                 db.addMplsRoute(RibMplsEntry(label, {NextHopThrift(
                     bytes(16), None, 0, MplsAction("POP_AND_LOOKUP"), area, None)}))
                 continue
             c, b = cnt_l[k], k * deg
-            if not c:
-                self._bump("decision.no_route_to_label")
-                continue
             if not fast:  # the generic getNextHopsThrift restatement (tests)
                 db.addMplsRoute(RibMplsEntry(label, self._next_hops(
                     ls, me, area, zip(edge[first + b:first + b + c].tolist(),

@@ -230,3 +230,41 @@ def route_db_digest(hdr, rec, link_id, link_hash) -> int:
         h = _mix64(_mix64(np.uint64(0x9e3779b97f4a7c15) * (p + np.uint64(1)) + shortest) + sums + p)
         total = h.sum(dtype=np.uint64)
     return int(total)
+
+
+def label_candidates(label_of):
+    """{label: candidates in ascending name} over the valid, non-zero labels."""
+    from openr_amd.spf_solver import MPLS_LABEL_MAX, MPLS_LABEL_MIN
+
+    out = {}
+    for node in sorted(label_of):
+        lab = label_of[node]
+        if lab != 0 and MPLS_LABEL_MIN <= lab <= MPLS_LABEL_MAX:
+            out.setdefault(lab, []).append(node)
+    return dict(sorted(out.items()))
+
+
+def expected_from(orc, label_of, mes, lfa):
+    """{(me, label): (owner name, {(ifName, metric, neighbour, action, swap)})}
+    for the pairs with a route, from the oracle alone (mes: names; None =
+    every node): per me and label the candidates are walked in ascending
+    name; the first that is me owns the label (POP_AND_LOOKUP, no rows),
+    otherwise the first with a non-empty next-hop set owns it."""
+    from oracle import nexthops
+
+    cands = label_candidates(label_of)
+    mes = sorted(label_of) if mes is None else mes
+    out = {}
+    for me in mes:
+        for lab, cs in cands.items():
+            for c in cs:
+                if c == me:
+                    out[(me, lab)] = (me, set())
+                    break
+                rows = nexthops(orc, me, [c], lfa, swap_label=lab)["nh"]
+                if rows:
+                    out[(me, lab)] = (c, {(r[0], r[1], r[2], r[4], r[5]) for r in rows})
+                    break
+    # the inputs are chosen so that most pairs have a route
+    assert 2 * len(out) >= len(mes) * len(cands), (len(out), len(mes), len(cands))
+    return out

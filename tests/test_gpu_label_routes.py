@@ -7,9 +7,10 @@ getNextHopsThrift (oracle.nexthops), never from the code under test: per me
 and label the candidates are walked in ascending name; the first that is me
 owns the label (POP_AND_LOOKUP), otherwise the first with a non-empty next-hop
 set owns it and those rows are the route.  The reference resolves a label
-collision this way (the smaller name wins only when it has a route); the two
-host solvers pick the owner before they look at reachability, which is why
-the comparison with SpfSolver.buildRouteDb runs on labels without collisions.
+collision this way (the smaller name wins only when it has a route), and so
+do the two host solvers: the comparison with SpfSolver.buildRouteDb runs on
+shared labels too (tests/test_gpu_label_collisions.py pins the host solvers
+themselves to the oracle).
 """
 
 import ctypes as C
@@ -18,12 +19,13 @@ import functools
 import numpy as np
 import pytest
 
-from oracle import OracleLinkState, nexthops
+from helpers import expected_from, label_candidates
+from oracle import OracleLinkState
 from openr_amd import _native as N
 from openr_amd import topology as T
 from openr_amd.link_state import LinkState
 from openr_amd.lsdb import create_adj_db, create_adjacency, pack, pack_fast
-from openr_amd.spf_solver import MPLS_LABEL_MAX, MPLS_LABEL_MIN, PrefixState, SpfSolver
+from openr_amd.spf_solver import MPLS_LABEL_MAX, PrefixState, SpfSolver
 
 pytestmark = pytest.mark.gpu
 
@@ -127,38 +129,6 @@ GRAPHS = {"A": graph_a, "B": graph_b, "C": graph_c, "D": graph_d}
 @functools.lru_cache(maxsize=None)
 def graph(key):
     return GRAPHS[key]()
-
-
-def label_candidates(label_of):
-    """{label: candidates in ascending name} over the valid, non-zero labels."""
-    out = {}
-    for node in sorted(label_of):
-        lab = label_of[node]
-        if lab != 0 and MPLS_LABEL_MIN <= lab <= MPLS_LABEL_MAX:
-            out.setdefault(lab, []).append(node)
-    return dict(sorted(out.items()))
-
-
-def expected_from(orc, label_of, mes, lfa):
-    """{(me, label): (owner name, {(ifName, metric, neighbour, action, swap)})}
-    for the pairs with a route, from the oracle alone (mes: names; None =
-    every node)."""
-    cands = label_candidates(label_of)
-    mes = sorted(label_of) if mes is None else mes
-    out = {}
-    for me in mes:
-        for lab, cs in cands.items():
-            for c in cs:
-                if c == me:
-                    out[(me, lab)] = (me, set())
-                    break
-                rows = nexthops(orc, me, [c], lfa, swap_label=lab)["nh"]
-                if rows:
-                    out[(me, lab)] = (c, {(r[0], r[1], r[2], r[4], r[5]) for r in rows})
-                    break
-    # the inputs are chosen so that most pairs have a route
-    assert 2 * len(out) >= len(mes) * len(cands), (len(out), len(mes), len(cands))
-    return out
 
 
 @functools.lru_cache(maxsize=None)
@@ -280,22 +250,25 @@ def test_graph_a_covers_the_collision_cases():
 def test_mpls_routes_equal_build_route_db():
     """allSourcesMplsRoutes(t) (the records expanded, adjacency labels from
     the host) equals SpfSolver.buildRouteDb(me).mplsRoutes for every me, on
-    graph B without shared labels (the host solvers resolve collisions
-    differently), shortest paths only."""
-    lsdb, _label_of, _ = graph_b(shared=False)
+    graph B without and with shared labels and on graph A (two components,
+    shared labels with an unreachable smaller name), shortest paths only."""
     ps = PrefixState()
-    with LinkState(devices=[0, 0]) as ls:
-        ls.updateAdjacencyDatabases(lsdb)
-        ls.prefetchAllSources()
-        names = list(ls.flatten()[0])
-        ls.allSourcesLabelRoutes(False)
-        routes = 0
-        for t, me in enumerate(names):
-            got = ls.allSourcesMplsRoutes(t)
-            want = SpfSolver(me, False, False).buildRouteDb(me, {"0": ls}, ps).mplsRoutes
-            assert got == want, me
-            routes += len(got)
-    assert routes > 10 * len(names)  # (most of the ~54 labels are routable from most nodes)
+    # (graph, routes per me at least: most of B's ~54 labels are routable from
+    # most nodes; A has 9 node labels, about half of them routable per me, and
+    # its adjacency labels)
+    for lsdb, least in ((graph_b(shared=False)[0], 10), (graph("B")[0], 10), (graph("A")[0], 4)):
+        with LinkState(devices=[0, 0]) as ls:
+            ls.updateAdjacencyDatabases(lsdb)
+            ls.prefetchAllSources()
+            names = list(ls.flatten()[0])
+            ls.allSourcesLabelRoutes(False)
+            routes = 0
+            for t, me in enumerate(names):
+                got = ls.allSourcesMplsRoutes(t)
+                want = SpfSolver(me, False, False).buildRouteDb(me, {"0": ls}, ps).mplsRoutes
+                assert got == want, me
+                routes += len(got)
+        assert routes > least * len(names)
 
 
 def test_label_routes_error_paths():

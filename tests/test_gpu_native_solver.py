@@ -58,10 +58,41 @@ def build_both(me, areas, ps, flags=(True, True), static=None):
     return out
 
 
-def labelled(topo, base):
+def labelled(topo, base, share=None):
+    """Every node its own label; with `share` (a seed) five seeded pairs share
+    one label each, and the smallest-named node is cut off (every adjacency
+    of its database overloaded: its links are down both ways) and shares its
+    label with the largest-named one."""
     dbs = topo.lsdb.dbs.copy()
-    dbs["node_label"] = base + np.arange(len(dbs), dtype=np.int32)
-    return PackedLsdb(topo.lsdb.blob, dbs, topo.lsdb.adjs)
+    adjs = topo.lsdb.adjs
+    lab = base + np.arange(len(dbs), dtype=np.int32)
+    if share is not None:
+        rng = np.random.default_rng(share)
+        pick = rng.choice(len(dbs), 10, replace=False)
+        lab[pick[5:]] = lab[pick[:5]]
+        cut, far = (topo.nodes.index(f(topo.nodes)) for f in (min, max))
+        lab[far] = lab[cut]
+        adjs = adjs.copy()
+        b = int(dbs["adj_begin"][cut])
+        adjs["is_overloaded"][b: b + int(dbs["adj_count"][cut])] = 1
+    dbs["node_label"] = lab
+    return PackedLsdb(topo.lsdb.blob, dbs, adjs)
+
+
+def assert_collision_with_unreachable_candidate(lsdb, nodes, mes, area="0"):
+    """On the oracle: the cut-off smallest name shares its label with a node
+    that some me of `mes` reaches, while that me does not reach the cut-off
+    one -- the case where picking the owner first drops the label."""
+    from oracle import OracleLinkState, nexthops
+
+    orc = OracleLinkState(area)
+    orc.update_packed(lsdb)
+    cut, far = min(nodes), max(nodes)
+    lab = dict(zip(nodes, lsdb.dbs["node_label"].tolist()))
+    assert lab[cut] == lab[far] and sum(lab[n] == lab[cut] for n in nodes) >= 2
+    assert any(me not in (cut, far) and not nexthops(orc, me, [cut])["nh"] and nexthops(orc, me, [far])["nh"]
+               for me in mes), mes
+    return orc, cut
 
 
 def random_prefixes(ps, names, area, rng, n, tag, bgp=False, ksp2=True):
@@ -93,6 +124,9 @@ GRAPHS = [
     ("rand1", lambda: T.random_graph(40, 110, 62, max_metric=3, parallel_frac=0.3, overload_frac=0.15)),
     ("wan60", lambda: T.wan(60, 30, seed=4)),
     ("fabric1000", lambda: T.fabric(1000, full=True)),
+    # rand0 again, with shared node labels (labelled(share=...))
+    ("rand0-shared-labels", lambda: T.random_graph(30, 80, 61, max_metric=5, parallel_frac=0.2,
+                                                   overload_frac=0.1, link_overload_frac=0.05)),
 ]
 
 
@@ -101,8 +135,10 @@ GRAPHS = [
 @pytest.mark.parametrize("brs", [False, True], ids=["openr", "best_route"])
 def test_native_equals_restatement_one_area(name, make, lfa, brs):
     topo = make()
+    share = 7 if name.endswith("shared-labels") else None
     with LinkState() as ls:
-        ls.updateAdjacencyDatabases(labelled(topo, 70000))
+        lsdb = labelled(topo, 70000, share)
+        ls.updateAdjacencyDatabases(lsdb)
         names = topo.nodes
         rng = np.random.default_rng(11)
         ps = PrefixState()
@@ -110,9 +146,14 @@ def test_native_equals_restatement_one_area(name, make, lfa, brs):
         static = {300001: [NextHopThrift(bytes(16), "eth9", 0, None, None, None)],
                   150: [NextHopThrift(bytes([1] * 16), None, 0, MplsAction("PUSH", None, (5, 6)),
                                       None, None)]}
-        for me in [names[int(i)] for i in rng.choice(len(names), 3, replace=False)]:
+        mes = [names[int(i)] for i in rng.choice(len(names), 3, replace=False)]
+        if share is not None:
+            assert_collision_with_unreachable_candidate(lsdb, names, mes, ls.getArea())
+        for me in mes:
             nat, py = build_both(me, {ls.getArea(): ls}, ps, (True, lfa, False, False, brs), static)
             assert nat == py, me
+            if share is not None:  # both counted the collisions (one pair at the least)
+                assert nat[2].get("decision.duplicate_node_label", 0) >= 1
 
 
 def test_native_equals_restatement_several_areas():
@@ -120,13 +161,32 @@ def test_native_equals_restatement_several_areas():
     areas, node labels from both areas (a node present in both).  No
     KSP2_ED_ECMP prefixes: with several areas the reference's
     prefixEntries.at({node, area}) throws for a path's destination in another
-    area (Decision.cpp:982), as both implementations do."""
+    area (Decision.cpp:982), as both implementations do.  Run once with every
+    label shared across the two areas only, and once more with labels shared
+    within each area too, a cut-off smallest name among their candidates."""
+    for share in (None, 5):
+        _several_areas(share)
+
+
+def _several_areas(share):
     ta, tb = T.random_graph(25, 60, 71, max_metric=4, parallel_frac=0.2), T.random_graph(
         25, 60, 72, max_metric=4, overload_frac=0.1)
     la, lb = LinkState("A"), LinkState("B")
     with la, lb:
-        la.updateAdjacencyDatabases(labelled(ta, 80000))
-        lb.updateAdjacencyDatabases(labelled(tb, 80000))
+        lsdb_a = labelled(ta, 80000, share)
+        la.updateAdjacencyDatabases(lsdb_a)
+        lsdb_b = labelled(tb, 80000, None if share is None else share + 1)
+        lb.updateAdjacencyDatabases(lsdb_b)
+        if share is not None:
+            _orc, cut = assert_collision_with_unreachable_candidate(lsdb_a, ta.nodes, ta.nodes[:4], "A")
+            # a destination is looked up by name in every area: the name cut off
+            # in "A" is cut off in "B" as well, so no me reaches it through "B"
+            from oracle import OracleLinkState, nexthops
+
+            orc_b = OracleLinkState("B")
+            orc_b.update_packed(lsdb_b)
+            assert cut in tb.nodes
+            assert not any(nexthops(orc_b, me, [cut])["nh"] for me in tb.nodes if me != cut)
         rng = np.random.default_rng(3)
         ps = PrefixState()
         random_prefixes(ps, ta.nodes, "A", rng, 20, 2, ksp2=False)

@@ -7,8 +7,8 @@ Two expectations, neither from the code under test:
   primary    DecisionRouteDb.calculateUpdate (the restatement next to the
              solver) over SpfSolver.buildRouteDb(me) taken before and after the
              change, prefix i = the loopback of node i = destination set i (a
-             mapping fixed across the two passes); labels without collision
-             (the host solvers resolve collisions differently);
+             mapping fixed across the two passes), shared labels included
+             (777 on a0 and b0, 778 on r25 and w0);
   secondary  the two full read-backs (allSourcesRouteDb / allSourcesLabelRouteDb
              of every me, taken before the snapshot and after the second
              pass), translated to {(link by value, metric)} sets and compared
@@ -41,7 +41,8 @@ def world():
       z0    a leaf of r05 (cut off when that link goes down);
       a0,b0 leaves of r10 at equal metrics sharing label 777: from anywhere
             else the next hops towards either are the same;
-      w0    a leaf of r20.
+      w0    a leaf of r20, sharing label 778 with r25 (the smaller name,
+            reachable: it owns the label from everywhere, w0 included).
     Returns {name: AdjacencyDatabase} (no adjacency labels: the MPLS routes
     are the node-label ones)."""
     ring = [f"r{i:02d}" for i in range(RING)]
@@ -65,6 +66,7 @@ def world():
                                         f"10.0.{i}.2", mv, 0))
     label = {n: 100 + i for i, n in enumerate(names)}
     label["a0"] = label["b0"] = SHARED
+    label["r25"] = label["w0"] = SHARED + 1
     return {n: create_adj_db(n, adjs[n], label[n]) for n in names}
 
 
@@ -138,7 +140,7 @@ def secondary(g0, g1):
     return out
 
 
-def primary(g0, g1, prefix_set, skip_labels=()):
+def primary(g0, g1, prefix_set):
     """The same from calculateUpdate over buildRouteDb before / after."""
     out = {}
     for t, old in g0.dbs.items():
@@ -149,8 +151,7 @@ def primary(g0, g1, prefix_set, skip_labels=()):
         assert applied == new
         out[t] = (sorted(prefix_set[p] for p in d.unicastRoutesToUpdate),
                   sorted(prefix_set[p] for p in d.unicastRoutesToDelete),
-                  sorted(r.label for r in d.mplsRoutesToUpdate if r.label not in skip_labels),
-                  sorted(l for l in d.mplsRoutesToDelete if l not in skip_labels))
+                  sorted(r.label for r in d.mplsRoutesToUpdate), sorted(d.mplsRoutesToDelete))
     return out
 
 
@@ -167,16 +168,27 @@ def loopbacks(ls, names, sets=None):
     return ps, prefix_set
 
 
-def check(delta, want, skip_labels=()):
+def moved_only(g0, g1, t):
+    """Labels of me t whose owner changed while the next hops stayed the same
+    (a shared label's owner moving between two nodes behind the same links):
+    the GPU's delta lists them, its record carrying the owner; a RibMplsEntry
+    does not hold the owner, so calculateUpdate does not."""
+    return [l for l in sorted(g1.lb[t]) if l in g0.lb[t] and g0.lb[t][l][0] != g1.lb[t][l][0]
+            and g0.lb[t][l][1] == g1.lb[t][l][1]]
+
+
+def check(delta, want, owner_moves=None):
+    """owner_moves: {me: moved_only(...)} when `want` is calculateUpdate's --
+    exactly those labels are listed on top of its updates."""
     lists, totals, ms = delta
     assert ms >= 0
     for t, w in want.items():
         got = lists[t]
-        if skip_labels:
-            got = (got[0], got[1], [l for l in got[2] if l not in skip_labels],
-                   [l for l in got[3] if l not in skip_labels])
+        if owner_moves is not None:
+            assert not set(owner_moves[t]) & set(w[2]), (t, owner_moves[t], w[2])
+            w = (w[0], w[1], sorted(list(w[2]) + owner_moves[t]), w[3])
         assert tuple(got) == tuple(w), (t, got, w)
-    if len(want) == len(lists) and not skip_labels:
+    if len(want) == len(lists) and owner_moves is None:
         assert totals[:4] == [sum(len(w[k]) for w in want.values()) for k in range(4)]
 
 
@@ -196,7 +208,8 @@ def step(ls, dbs, change, lfa, with_primary=True, sets=None, set_lists=None, sol
     delta = ls.allSourcesRouteDelta(snap)
     check(delta, secondary(g0, g1))
     if with_primary:
-        check(delta, primary(g0, g1, prefix_set, (SHARED,)), (SHARED,))
+        want = primary(g0, g1, prefix_set)
+        check(delta, want, {t: moved_only(g0, g1, t) for t in want})
     again = ls.allSourcesRouteDelta(snap)  # the snapshot is only read
     assert again[0] == delta[0] and again[1] == delta[1]
     snap.close()

@@ -13,9 +13,8 @@ Two expectations, neither from the code under test, both compared by equality:
              is the header's formula;
   reference  old.calculateUpdate(new) over SpfSolver.buildRouteDb(me) before and
              after: the updated unicast routes' next hops and the updated
-             RibMplsEntry's (label 777 aside: the host solvers resolve the
-             collision differently), and old.update(delta) rebuilt from the
-             GPU's payload gives new.
+             RibMplsEntry's, the shared labels' included, and old.update(delta)
+             rebuilt from the GPU's payload gives new.
 """
 
 import copy
@@ -29,8 +28,8 @@ from openr_amd import topology as T
 from openr_amd.link_state import LinkState
 from openr_amd.lsdb import create_adj_db, create_adjacency
 from openr_amd.spf_solver import DecisionRouteUpdate, PrefixEntry, RibUnicastEntry
-from test_gpu_route_delta import (LFA, MEMBERS, SHARED, Gen, adj, loopbacks, push, single_sets, tile_sets,
-                                  world)
+from test_gpu_route_delta import (LFA, MEMBERS, SHARED, Gen, adj, loopbacks, moved_only, push, single_sets,
+                                  tile_sets, world)
 
 pytestmark = pytest.mark.gpu
 
@@ -116,7 +115,7 @@ def by_value(ls, g1, upd, members, every=True):
     return n_ip, r_ip, n_lb, r_lb
 
 
-def reference(ls, g0, g1, prefix_set, skip=(SHARED,)):
+def reference(ls, g0, g1, prefix_set, owner_moves=None):
     """calculateUpdate over buildRouteDb before / after against the expanded
     payload, for every me the generations hold solver databases of."""
     prefix_of = {p: s for s, p in prefix_set.items()}
@@ -126,9 +125,15 @@ def reference(ls, g0, g1, prefix_set, skip=(SHARED,)):
         uni, dele, mpls, ldel = ls.allSourcesDecisionRouteUpdate(t)
         assert {prefix_set[p]: e.nexthops for p, e in d.unicastRoutesToUpdate.items()} == uni, t
         assert sorted(prefix_set[p] for p in d.unicastRoutesToDelete) == dele
-        want = {r.label: r for r in d.mplsRoutesToUpdate if r.label not in skip}
-        assert want == {r.label: r for r in mpls if r.label not in skip}, t
-        assert [l for l in d.mplsRoutesToDelete if l not in skip] == [l for l in ldel if l not in skip]
+        # (a label whose owner moved behind unchanged next hops is in the GPU's
+        # update, the owner being part of its record, and not in calculateUpdate's:
+        # its entry is the one the old database holds)
+        moved = moved_only(g0, g1, t) if owner_moves is None else owner_moves[t]
+        got = {r.label: r for r in mpls}
+        assert len(got) == len(mpls)
+        assert all(got[l] == old.mplsRoutes[l] == new.mplsRoutes[l] for l in moved), t
+        assert {r.label: r for r in d.mplsRoutesToUpdate} == {l: r for l, r in got.items() if l not in moved}, t
+        assert list(d.mplsRoutesToDelete) == list(ldel)
         # old.update(the GPU's delta) gives new
         gpu = DecisionRouteUpdate()
         for p, nhs in uni.items():
@@ -140,8 +145,7 @@ def reference(ls, g0, g1, prefix_set, skip=(SHARED,)):
         applied.update(gpu)
         assert {p: e.nexthops for p, e in applied.unicastRoutes.items()} == \
             {p: e.nexthops for p, e in new.unicastRoutes.items()}, t
-        assert {l: e for l, e in applied.mplsRoutes.items() if l not in skip} == \
-            {l: e for l, e in new.mplsRoutes.items() if l not in skip}, t
+        assert applied.mplsRoutes == new.mplsRoutes, t
 
 
 def step(ls, dbs, change, lfa, members, with_primary=True, sets=None, set_lists=None, solver_mes=None):
