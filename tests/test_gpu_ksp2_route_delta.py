@@ -80,8 +80,9 @@ def hub_dbs(leaves=70):
     return dbs_from_links([("hub", l, 1, 1, False) for l in nodes[1:]], {n: 1 + i for i, n in enumerate(nodes)})
 
 
-def random_dbs(seed=5, n=20, extra=18):
-    """A connected multigraph: a ring, random chords, a quarter of them doubled."""
+def random_dbs(seed=5, n=20, extra=18, more=()):
+    """A connected multigraph: a ring, random chords, a quarter of them doubled;
+    then the links of `more`, whose new nodes are labelled after the others."""
     rng = np.random.default_rng(seed)
     nodes = [f"n{i:02d}" for i in range(n)]
     links = [(nodes[i], nodes[(i + 1) % n], int(rng.integers(1, 5)), int(rng.integers(1, 5)), False)
@@ -92,6 +93,9 @@ def random_dbs(seed=5, n=20, extra=18):
         links.append((nodes[min(u, v)], nodes[max(u, v)], m, m, False))
         if rng.random() < 0.25:
             links.append((nodes[min(u, v)], nodes[max(u, v)], m, int(rng.integers(1, 5)), False))
+    for link in more:
+        links.append(link)
+        nodes += [x for x in link[:2] if x not in nodes]
     return dbs_from_links(links, {s: 300 + i for i, s in enumerate(nodes)})
 
 
