@@ -869,9 +869,9 @@ spf_status spf_whatif_base(spf_whatif_plan* plan, uint64_t* dist, uint32_t* nh, 
  * were counted drops them, as the lists do.  After a failed call the plan
  * holds no route lists, and a new spf_whatif_changes on the plan invalidates
  * them.
- * Node-level next hops are the deliberate scope: the expansion over src's own
- * links (getNextHopsThrift), LFA and SpfSolver's prefix bookkeeping stay with
- * the caller. */
+ * These lists are node-level: the expansion over src's own links
+ * (getNextHopsThrift) is spf_whatif_route_update's, below; LFA and SpfSolver's
+ * prefix bookkeeping stay with the caller. */
 spf_status spf_whatif_routes(spf_whatif_plan* plan, const uint32_t* set_ptr /* [n_sets + 1] */,
                              const uint32_t* set_nodes /* [set_ptr[n_sets]] */, uint32_t n_sets,
                              uint64_t* n_entries, uint64_t* pool_bytes, double* kernel_ms,
@@ -898,6 +898,97 @@ spf_status spf_whatif_routes_buffers(spf_whatif_plan* plan, const uint64_t** d_p
 /* ms[4] = base routes + table, count pass, scan, fill pass of the last
  * spf_whatif_routes. */
 spf_status spf_whatif_routes_timing(const spf_whatif_plan* plan, double* ms);
+/* ---- what-if route updates: each failure's LINK-LEVEL next hops.
+ * What a FIB would be told under failure i: for a set s of the last
+ * spf_whatif_routes, with (min', nh') its route under failure i (the route-list
+ * entry when (i, s) is listed, the base route otherwise) and d'(x) the metric of
+ * node x under failure i (the change-list entry when listed, the unfailed metric
+ * otherwise), the slots q of src's CSR row, in row order (linksFromNode order),
+ * that are
+ *   live      not a dead self-loop (a link that is not up);
+ *   surviving link plans: link_id[q] != l_i; node down: col[q] != x_i; node
+ *             drain: always; link sets: link_id[q] not in set i; metric changes:
+ *             always, weighing w'(q) = the substituted metric of its direction
+ *             when link_id[q] == l_i and that direction is not kept;
+ *   wanted    the bit of col[q] is set in nh';
+ *   tight     w'(q) == d'(col[q])  (getNextHopsThrift's distOverLink ==
+ *             minMetric, Decision.cpp:1198-1305, without LFA).
+ * A record is q | min' << 32, the record of spf_routes and
+ * spf_mplan_route_records; a withdrawn route (min' == UINT64_MAX) has none.
+ * The update list of failure i holds every set whose record sequence under
+ * failure i differs from its base sequence (no failure).  It is the route list
+ * plus what node-level lists cannot see: a failure that removes or re-weighs a
+ * slot of src's own row -- one member of a bundle, a member's metric raised, a
+ * heavier parallel link lowered onto the tie -- changes the records of every
+ * route through that neighbour while no node's metric or neighbour set moves.
+ * Empty sets, sets that hold src and sets unreachable in the base are never
+ * listed.  One exactly sized set per plan, on the device until the next call:
+ *   uptr[n_fail + 1]      u64  failure i owns entries uptr[i] .. uptr[i + 1]
+ *   uset[total]           u32  set id
+ *   umetric[total]        u64  min' (UINT64_MAX: withdrawn, no records)
+ *   urec_ptr[total + 1]   u64  entry e owns records urec_ptr[e] .. urec_ptr[e + 1]
+ *   urec[records]         u64  contiguous per entry, in slot order
+ * The order of a failure's entries on the device is unspecified (_db sorts).
+ * *n_entries = total, *n_records = records, *pool_bytes = 8 (n_fail + 1) +
+ * 12 total + 8 (total + 1) + 8 records, *kernel_ms = the phases of
+ * spf_whatif_route_update_timing together; the outputs are optional.  n_sets
+ * == 0 and zero failures are allowed.
+ *
+ * A device-side consumer of the change lists and the route lists: every set's
+ * base records; a pass over the failures that finds those touching src's row,
+ * each with the mask of the neighbours whose slots it changes; a count pass
+ * with a lane per route-list entry walking the row, and for the touched
+ * failures a sweep over the sets their route lists do not hold (the row is
+ * walked where a base route's words meet the mask); the pools' scan; a fill
+ * pass; the scan again over the entries' record counts; a pass that writes the
+ * records.  No buffer is n_fail x n_sets or n_fail x n_nodes.  Waits.
+ * SPF_E_INVALID: a NULL plan.  SPF_E_STATE: the plan holds no route lists
+ * (spf_whatif_changes, then spf_whatif_routes over the sets in question, first);
+ * the graph changed since the plan was created.  SPF_E_UNSUPPORTED: the plan
+ * runs on the exact path (a metric <= 0 or u64 labels), where a record could
+ * not hold the metric; nothing is launched.  SPF_E_NOMEM: the pools do not
+ * fit.  SPF_E_HIP: a fill that meets more than was counted drops the excess,
+ * as the lists do.  After a failed call the plan holds no update lists; a new
+ * spf_whatif_changes or spf_whatif_routes invalidates them; a new
+ * spf_whatif_route_update leaves the spf_whatif_by_set results valid. */
+spf_status spf_whatif_route_update(spf_whatif_plan* plan, uint64_t* n_entries, uint64_t* n_records,
+                                   uint64_t* pool_bytes, double* kernel_ms, void* stream);
+/* Failure i's entries, ascending by set id (sorted on the host): *n of them
+ * with *n_rec records; set[cap_entries], min_metric[cap_entries],
+ * rec_ptr[cap_entries + 1] (offsets into rec, from 0) and rec[cap_records] are
+ * filled when both capacities suffice, SPF_E_NOMEM (with *n and *n_rec set)
+ * otherwise.  Every output may be NULL.  This and the calls below: SPF_E_STATE
+ * when the plan holds no update lists. */
+spf_status spf_whatif_route_update_db(spf_whatif_plan* plan, uint32_t i, uint32_t* set,
+                                      uint64_t* min_metric, uint64_t* rec_ptr, uint64_t* rec,
+                                      uint64_t cap_entries, uint64_t cap_records, uint64_t* n,
+                                      uint64_t* n_rec);
+/* The whole set in one copy per array, in device order: ptr[n_fail + 1],
+ * set[total], min_metric[total], rec_ptr[total + 1], rec[records].  Every
+ * output may be NULL. */
+spf_status spf_whatif_route_update_read(spf_whatif_plan* plan, uint64_t* ptr, uint32_t* set,
+                                        uint64_t* min_metric, uint64_t* rec_ptr, uint64_t* rec);
+/* The device arrays, for device-side consumers (valid until the next
+ * spf_whatif_route_update, spf_whatif_routes or spf_whatif_changes on the
+ * plan); every output may be NULL. */
+spf_status spf_whatif_route_update_buffers(spf_whatif_plan* plan, const uint64_t** d_ptr,
+                                           const uint32_t** d_set, const uint64_t** d_metric,
+                                           const uint64_t** d_rec_ptr, const uint64_t** d_rec,
+                                           uint64_t* n_entries, uint64_t* n_records);
+/* Every set's base records: rec_ptr[n_sets + 1], rec[rec_ptr[n_sets]]; either
+ * may be NULL (read rec_ptr first to size rec). */
+spf_status spf_whatif_route_update_base(spf_whatif_plan* plan, uint64_t* rec_ptr, uint64_t* rec);
+/* ms[7] = base records, touch pass, count pass, scan, fill pass, the records'
+ * scan, record pass of the last spf_whatif_route_update. */
+spf_status spf_whatif_route_update_timing(const spf_whatif_plan* plan, double* ms);
+/* The failures of the plan that change a slot of src's row (the ones swept) and
+ * the number of base records; either may be NULL. */
+spf_status spf_whatif_route_update_stats(spf_whatif_plan* plan, uint32_t* n_touched,
+                                         uint64_t* base_records);
+/* Launch constants the tests cross: the sets a workgroup of the sweep takes per
+ * round, and the counts the pools' scan takes per round. */
+uint32_t spf_whatif_route_update_sweep_sets(void);
+uint32_t spf_whatif_scan_tile(void);
 /* ---- what-if impact by destination: the lists above, keyed by what is hit.
  * The change and route lists are keyed by the failure.  "Which failures touch
  * node v (or prefix s), which of them cut it off, which is the worst and how

@@ -299,6 +299,17 @@ PROTOTYPES = {
     "spf_whatif_routes_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
                                             C.POINTER(_vp), _u32p, _u64p]),
     "spf_whatif_routes_timing": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "spf_whatif_route_update": (C.c_int, [_vp, _u64p, _u64p, _u64p, C.POINTER(C.c_double), _vp]),
+    "spf_whatif_route_update_db": (C.c_int, [_vp, C.c_uint32, _u32p, _u64p, _u64p, _u64p, C.c_uint64,
+                                             C.c_uint64, _u64p, _u64p]),
+    "spf_whatif_route_update_read": (C.c_int, [_vp, _u64p, _u32p, _u64p, _u64p, _u64p]),
+    "spf_whatif_route_update_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
+                                                  C.POINTER(_vp), C.POINTER(_vp), _u64p, _u64p]),
+    "spf_whatif_route_update_base": (C.c_int, [_vp, _u64p, _u64p]),
+    "spf_whatif_route_update_timing": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "spf_whatif_route_update_stats": (C.c_int, [_vp, _u32p, _u64p]),
+    "spf_whatif_route_update_sweep_sets": (C.c_uint32, []),
+    "spf_whatif_scan_tile": (C.c_uint32, []),
     "spf_whatif_impact_timing": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_double)]),
     **{f"spf_whatif_by_{flavour}{call}": (C.c_int, list(args))
        for flavour in ("node", "set")

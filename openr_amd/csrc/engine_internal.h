@@ -163,6 +163,9 @@ struct WiRoutes {
   DevBuf<unsigned long long> d_keys;  // (failure << 32 | node), ~0: empty
   DevBuf<uint32_t> d_vals, d_efail;   // entry index per slot; failure per entry
   DevBuf<uint32_t> d_cnt, d_cur;      // [n_fail] counts, fill cursors
+  // the table as the last successful call left it, for spf_whatif_route_update:
+  // slots - 1, 0 when the call built none (no list entry, or no set to list)
+  uint32_t tab_mask = 0;
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   ~WiRoutes() {
     for (hipEvent_t e : ev)
@@ -186,20 +189,64 @@ struct WiImpact {
   }
 };
 
-// What whatif_routes.hip and whatif_impact.hip read of a plan (whatif.hip owns
-// spf_whatif_plan): the change lists of the last spf_whatif_changes, the
-// unfailed result as the plan holds it (u32 metrics with kInf and rows that
-// are undefined where unreachable, or the exact plan's u64 ones), the plan's
-// route lists and its two transpositions.
-enum WiPoolId { kPoolChanges, kPoolRoutes, kPoolByNode, kPoolBySet };  // kPoolByNode + SPF_WHATIF_BY_*
+// Route updates of a what-if batch (spf_whatif_route_update,
+// whatif_route_update.hip): every failure's sets whose link-level records
+// change, as two pools -- `ent` (owner = failure, key = set, val = min metric,
+// no rows) and `rec` (owner = entry, val = record, no key and no rows) -- the
+// source's row table, every set's base records and the pass's scratch (all
+// kept while they are large enough).
+struct WiUpdate {
+  WiPool ent, rec;  // valid together: ent.valid says so
+  uint32_t n_sets = 0, n_touch = 0;  // n_touch: failures that change a slot of src's row
+  uint64_t base_records = 0;
+  // base records, touch, count, scan, fill, the records' scan, records of the last call
+  double ms[7] = {0, 0, 0, 0, 0, 0, 0};
+  DevBuf<uint4> d_row;               // [slots of src] {neighbour bit, metric, link id, head}
+  DevBuf<uint2> d_row_link;          // the live slots' (link id, slot in row), ascending link id
+  DevBuf<unsigned long long> d_bptr, d_brec;  // [n_sets + 1], [base_records]
+  DevBuf<uint32_t> d_bcnt;                    // [n_sets]
+  DevBuf<uint32_t> d_tidx, d_tlist, d_tmask, d_tn;  // [n_fail], [n_touch], [n_touch][W], counters
+  DevBuf<uint2> d_trange;                     // [n_touch] first and last non-zero word of the mask
+  DevBuf<unsigned long long> d_mkeys;         // (failure << 32 | set) of the touched failures' route entries
+  DevBuf<uint32_t> d_cnt, d_cur, d_usrc, d_rcnt;  // [n_fail] x 2, [entries] x 2
+  hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  ~WiUpdate() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+// What whatif_routes.hip, whatif_impact.hip and whatif_route_update.hip read
+// of a plan (whatif.hip owns spf_whatif_plan): the change lists of the last
+// spf_whatif_changes, the unfailed result as the plan holds it (u32 metrics
+// with kInf and rows that are undefined where unreachable, or the exact
+// plan's u64 ones), the plan's route lists, its two transpositions and its
+// route updates, and the failures as the plan's kind describes them.
+// kPoolByNode + SPF_WHATIF_BY_*
+enum WiPoolId { kPoolChanges, kPoolRoutes, kPoolByNode, kPoolBySet, kPoolUpdate, kPoolUpdateRec };
 struct WiListsView {
   spf_ctx* ctx = nullptr;
   const WiPool* changes = nullptr;
   WiRoutes* rt = nullptr;
   WiImpact* imp[2] = {nullptr, nullptr};  // SPF_WHATIF_BY_NODE, SPF_WHATIF_BY_SET
+  WiUpdate* up = nullptr;
   const WiPool* pool(WiPoolId id) const {
-    return id == kPoolChanges ? changes : id == kPoolRoutes ? &rt->pool : &imp[id - kPoolByNode]->pool;
+    return id == kPoolChanges    ? changes
+           : id == kPoolRoutes   ? &rt->pool
+           : id == kPoolUpdate   ? &up->ent
+           : id == kPoolUpdateRec ? &up->rec
+                                  : &imp[id - kPoolByNode]->pool;
   }
+  // the failures: kind 0 / SPF_WHATIF_LINK_METRIC: fails = link ids;
+  // SPF_WHATIF_NODE_*: node ids; SPF_WHATIF_LINK_SET: fails = set_ptr
+  // [n_fail + 1] into set_links; met = the metric plan's uint4 changes
+  // {edge, reverse edge, their metrics under the change}
+  uint32_t kind = 0;
+  bool exact = false;  // the plan runs on the exact path
+  const uint32_t* fails = nullptr;
+  const uint32_t* set_links = nullptr;
+  const void* met = nullptr;
+  const uint32_t* nbr_bit = nullptr;  // [N] j if v is src's j-th distinct neighbour, else kInf
   bool no_nbr = false;  // src has no up neighbour (rows undefined)
   uint64_t epoch = 0;
   uint32_t src = 0, n_fail = 0, W = 1;
@@ -579,6 +626,7 @@ void whatif_lists_view(spf_whatif_plan* p, WiListsView* v);
 // stride is 1 (a plain array) or 8 (spf_whatif_impact::n_changed).
 hipError_t whatif_scan(const uint32_t* cnt, uint32_t stride, uint32_t n, unsigned long long* ptr,
                        hipStream_t s);
+constexpr uint32_t kWhatifScanTile = 8192;  // counts the scan's workgroup takes per round
 // What the pools share on the host (whatif_pool.cpp).  `who` is the C call's
 // name, in front of every message.
 // v = the view of plan p when it holds pool `id`; else "NULL plan" (p NULL) or

@@ -794,6 +794,7 @@ __global__ void classify_kernel(WiGraph g, const uint32_t* __restrict__ dist,
 // STRIDE]: 1 for the lists' own arrays, 8 for the counts inside the impact
 // summaries (spfi::whatif_scan).
 constexpr uint32_t kListScanPer = 8;
+static_assert(1024 * kListScanPer == spfi::kWhatifScanTile, "the tile the tests cross");
 template <uint32_t STRIDE>
 __global__ __launch_bounds__(1024) void whatif_scan_kernel(const uint32_t* __restrict__ cnt,
                                                            uint32_t n,
@@ -870,6 +871,13 @@ void whatif_lists_view(spf_whatif_plan* p, WiListsView* v) {
   v->rt = &p->rt;
   v->imp[SPF_WHATIF_BY_NODE] = &p->imp_node;
   v->imp[SPF_WHATIF_BY_SET] = &p->imp_set;
+  v->up = &p->up;
+  v->kind = p->kind;
+  v->exact = p->exact != nullptr;
+  v->fails = p->d_fails.p;
+  v->set_links = p->d_set_links.p;
+  v->met = p->d_met.p;
+  v->nbr_bit = p->d_nbr_bit.p;
   v->changes = &p->lists;
   v->no_nbr = p->src + 1 < c->nb_ptr.size() && c->nb_ptr[p->src + 1] == c->nb_ptr[p->src];
   v->epoch = p->epoch;
@@ -1325,6 +1333,7 @@ spf_status spf_whatif_changes(spf_whatif_plan* p, spf_whatif_digest* d_out, spf_
   L.valid = false;             // after a failed call the plan holds no lists
   p->rt.pool.valid = false;    // ... and the route lists were built from the old ones
   p->imp_node.pool.valid = p->imp_set.pool.valid = false;  // ... as were the transpositions
+  p->up.ent.valid = p->up.rec.valid = false;                // ... and the route updates
   if (!c->loaded) return fail(c, SPF_E_STATE, "graph no longer loaded");
   if (p->epoch != c->epoch)
     return fail(c, SPF_E_STATE, "graph changed since the plan was created: recreate it");

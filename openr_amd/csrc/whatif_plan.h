@@ -77,6 +77,9 @@ struct spf_whatif_plan {
   // (whatif_impact.hip): imp_node over the change lists, imp_set over the route
   // lists; spf_whatif_changes invalidates both, spf_whatif_routes imp_set
   spfi::WiImpact imp_node, imp_set;
+  // the route lists at link level (whatif_route_update.hip), a consumer of
+  // both lists: spf_whatif_changes and spf_whatif_routes invalidate them
+  spfi::WiUpdate up;
   ~spf_whatif_plan() {
     for (hipEvent_t e : ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : l_ev)

@@ -13,7 +13,9 @@ namespace spfi {
 spf_status pool_held(spf_whatif_plan* p, WiPoolId id, const char* who, WiListsView* v) {
   static const char* const kWhat[] = {"lists", "route lists",
                                       "impact lists (spf_whatif_by_node first)",
-                                      "impact lists (spf_whatif_by_set first)"};
+                                      "impact lists (spf_whatif_by_set first)",
+                                      "route updates (spf_whatif_route_update first)",
+                                      "route updates (spf_whatif_route_update first)"};
   if (!p) return fail(nullptr, SPF_E_INVALID, "%s: NULL plan", who);
   whatif_lists_view(p, v);
   if (!v->pool(id)->valid) return fail(v->ctx, SPF_E_STATE, "%s: the plan holds no %s", who, kWhat[id]);

@@ -325,6 +325,7 @@ spf_status spf_whatif_routes(spf_whatif_plan* p, const uint32_t* set_ptr, const 
   const WiPool& L = *v.changes;
   R.valid = false;  // after a failed call the plan holds no route lists
   v.imp[SPF_WHATIF_BY_SET]->pool.valid = false;  // ... and none transposed from the old ones
+  v.up->ent.valid = v.up->rec.valid = false;     // ... nor route updates
   if (const char* why = route_sets_check(c->N, set_ptr, set_nodes, n_sets))
     return fail(c, SPF_E_INVALID, "spf_whatif_routes: %s", why);
   if (!c->loaded) return fail(c, SPF_E_STATE, "graph no longer loaded");
@@ -447,6 +448,7 @@ spf_status spf_whatif_routes(spf_whatif_plan* p, const uint32_t* set_ptr, const 
     r.ms[k] = ms;
   }
   r.n_sets = n_sets;
+  r.tab_mask = work ? (uint32_t)(cap - 1) : 0u;
   R.n_owners = nf;
   R.total = total;
   R.valid = true;

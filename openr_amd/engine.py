@@ -786,6 +786,73 @@ class WhatIfRoutes:
         failures that list it and its summary."""
         return WhatIfImpact(self.plan, "set", stream)
 
+    def update(self, stream: int = 0) -> "WhatIfRouteUpdate":
+        """Every failure's sets whose link-level next hops change, with their
+        records (``spf_whatif_route_update``)."""
+        return WhatIfRouteUpdate(self, stream)
+
+
+class WhatIfRouteUpdate:
+    """The update lists of one ``spf_whatif_route_update`` call on the host:
+    failure i owns entries ``ptr[i] .. ptr[i + 1]`` of ``set`` / ``min_metric``
+    (``SPF_UNREACHABLE64``: withdrawn), entry e the records ``rec_ptr[e] ..
+    rec_ptr[e + 1]`` of ``rec`` (``edge | min_metric << 32``, the records of
+    ``spf_routes``, in the source's link order), all in device order;
+    ``of(i)`` returns a failure's entries ascending by set id.  The device
+    arrays stay with the plan until its next ``update()``, ``routes()`` or
+    ``changes()``, after which the calls here raise."""
+
+    def __init__(self, routes: WhatIfRoutes, stream: int = 0) -> None:
+        self.routes, self.plan = routes, routes.plan
+        eng, h = self.plan._eng, self.plan._h
+        self.n_fail, self.n_sets = routes.n_fail, routes.n_sets
+        n, nrec, nbytes, ms = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_double()
+        eng._err(N.lib.spf_whatif_route_update(h, C.byref(n), C.byref(nrec), C.byref(nbytes),
+                                               C.byref(ms), C.c_void_p(stream) if stream else None))
+        self.n_entries, self.n_records = int(n.value), int(nrec.value)
+        self.pool_bytes, self.kernel_ms = int(nbytes.value), ms.value
+        k, b = C.c_uint32(), C.c_uint64()
+        eng._err(N.lib.spf_whatif_route_update_stats(h, C.byref(k), C.byref(b)))
+        self.n_touched, self.base_records = int(k.value), int(b.value)
+        self.ptr = np.zeros(self.n_fail + 1, np.uint64)
+        self.set = np.zeros(self.n_entries, np.uint32)
+        self.min_metric = np.zeros(self.n_entries, np.uint64)
+        self.rec_ptr = np.zeros(self.n_entries + 1, np.uint64)
+        self.rec = np.zeros(self.n_records, np.uint64)
+        eng._err(N.lib.spf_whatif_route_update_read(
+            h, N.ptr(self.ptr, C.c_uint64), N.ptr(self.set), N.ptr(self.min_metric, C.c_uint64),
+            N.ptr(self.rec_ptr, C.c_uint64), N.ptr(self.rec, C.c_uint64)))
+
+    def timing(self) -> Tuple[float, ...]:
+        """(base records, touch, count, scan, fill, record scan, records) ms."""
+        ms = (C.c_double * 7)()
+        self.plan._eng._err(N.lib.spf_whatif_route_update_timing(self.plan._h, ms))
+        return tuple(ms)
+
+    def of(self, i: int) -> Tuple[np.ndarray, np.ndarray, List[np.ndarray]]:
+        """Failure i's (set[n], min_metric[n], [records of each entry]),
+        ascending by set id."""
+        err, h = self.plan._eng._err, self.plan._h
+        n, nrec = C.c_uint64(), C.c_uint64()
+        err(N.lib.spf_whatif_route_update_db(h, i, None, None, None, None, 0, 0, C.byref(n),
+                                             C.byref(nrec)))
+        m, r = int(n.value), int(nrec.value)
+        ids, met = np.zeros(m, np.uint32), np.zeros(m, np.uint64)
+        rp, rec = np.zeros(m + 1, np.uint64), np.zeros(r, np.uint64)
+        if m:
+            err(N.lib.spf_whatif_route_update_db(h, i, N.ptr(ids), N.ptr(met, C.c_uint64),
+                                                 N.ptr(rp, C.c_uint64), N.ptr(rec, C.c_uint64), m, r,
+                                                 C.byref(n), C.byref(nrec)))
+        return ids, met, [rec[int(a): int(b)] for a, b in zip(rp[:-1], rp[1:])]
+
+    def base(self) -> List[np.ndarray]:
+        """Every set's records on the unfailed graph."""
+        rp = np.zeros(self.n_sets + 1, np.uint64)
+        rec = np.zeros(self.base_records, np.uint64)
+        self.plan._eng._err(N.lib.spf_whatif_route_update_base(
+            self.plan._h, N.ptr(rp, C.c_uint64), N.ptr(rec, C.c_uint64)))
+        return [rec[int(a): int(b)] for a, b in zip(rp[:-1], rp[1:])]
+
 
 class WhatIfImpact:
     """A plan's change lists by node (``flavour == "node"``) or its route lists
@@ -1107,6 +1174,11 @@ class SpfEngine(NativeHandle):
         if isinstance(changes_or_routes, WhatIfRoutes):
             return changes_or_routes.by_set()
         return changes_or_routes.by_node()
+
+    def whatif_route_update(self, routes: WhatIfRoutes) -> "WhatIfRouteUpdate":
+        """Each failure's link-level next hops over the sets of a
+        ``WhatIfRoutes`` (``spf_whatif_route_update``)."""
+        return routes.update()
 
     def whatif_node_plan(self, src: int, nodes: Optional[Sequence[int]] = None,
                          kind: str = "down") -> WhatIfPlan:
