@@ -1,7 +1,8 @@
 // ============================================================================
 //  engine_ctx.cpp -- the context itself: the error buffer, spf_ctx_create /
-//  _destroy and the small accessors, the ignore-set upload, the process-wide
-//  order of resident launches, spf_debug_stamps.  No kernel lives here.
+//  _destroy and the small accessors, spf_device_check (the fault word of
+//  grid_ops.h decoded), the ignore-set upload, the process-wide order of
+//  resident launches, spf_debug_stamps.  No kernel lives here.
 // ============================================================================
 #include <hip/hip_runtime.h>
 
@@ -16,6 +17,7 @@
 #include <vector>
 
 #include "engine_internal.h"
+#include "grid_ops.h"
 
 namespace spfi {
 
@@ -160,6 +162,55 @@ void spf_ctx_destroy(spf_ctx* c) {
   if (c->side_fork) (void)hipEventDestroy(c->side_fork);
   if (c->side_join) (void)hipEventDestroy(c->side_join);
   delete c;
+}
+
+spf_status spf_device_check(spf_ctx* c) {
+  if (!c) return fail(c, SPF_E_INVALID, "spf_device_check: NULL context");
+  HIP_TRY(c, hipSetDevice(c->device));
+  // every launch of this context may be on a caller's stream: wait for the
+  // device, then read and clear THIS context's fault word only (another
+  // context's timeout stays for its own check)
+  HIP_TRY(c, hipDeviceSynchronize());
+  if (!c->d_fault.p) return SPF_OK;
+  uint32_t flag = 0;
+  HIP_TRY(c, hipMemcpy(&flag, c->d_fault.p, sizeof flag, hipMemcpyDeviceToHost));
+  if (!flag) return SPF_OK;
+  HIP_TRY(c, hipMemset(c->d_fault.p, 0, sizeof flag));
+  if (flag & kFaultListRoom) {
+    // a team's fill pass met more entries than its count pass allocated
+    // (spf_whatif_changes): the entry was dropped
+    return fail(c, SPF_E_HIP,
+                "what-if change lists on device %d: an entry past its failure's allocated count "
+                "(fault word 0x%08x); the results of this context's launches since the last check are "
+                "invalid", c->device, flag);
+  }
+  if (flag & (kFaultLoopBound | kFaultRange | kFaultProfRow)) {
+    // what-if repair diagnostics: a loop bound with its phase, a range check of
+    // the profiled instances with its site, or a team past its profile region
+    // with its kernel
+    return fail(c, SPF_E_HIP,
+                "what-if repair on device %d: %s%s%s (fault word 0x%08x: loop phase %u, check site %u, "
+                "profile kernel %u); the results of this context's launches since the last check are "
+                "invalid",
+                c->device, (flag & kFaultLoopBound) ? "a repair loop reached its iteration bound " : "",
+                (flag & kFaultRange) ? "a scratch index failed its range check " : "",
+                (flag & kFaultProfRow) ? "a team's profile row is outside the profile buffer" : "", flag,
+                (flag >> kFaultPhaseShift) & 0xFFu, (flag >> kFaultSiteShift) & 0xFFu,
+                flag >> kFaultKernelShift);
+  }
+  if (flag & kFaultTeamBarrier) {
+    // a team BFS gave up waiting for its members (another process's grid
+    // held CUs): this context's plans stop using teams -- each re-derives
+    // onto msbfs_kernel at its next execute -- instead of polling again
+    c->team_off = true;
+    return fail(c, SPF_E_HIP,
+                "a team BFS barrier timed out on device %d (workgroups not co-resident): the "
+                "results of this context's launches since the last check are invalid; its plans "
+                "run msbfs_kernel from their next execute", c->device);
+  }
+  return fail(c, SPF_E_HIP,
+              "a grid barrier timed out on device %d (blocks not co-resident?): the "
+              "results of this context's launches since the last check are invalid", c->device);
 }
 
 spf_status spf_src_neighbors(const spf_ctx* c, uint32_t src, uint32_t* out,

@@ -112,7 +112,7 @@ struct ExactScratch {
 // Change lists of a what-if batch (spf_whatif_changes; the EMIT instances of
 // the repair kernels and of exact_whatif_kernel).  Count pass (cnode NULL): a
 // team writes cnt[f] = the entries of failure f.  Fill pass: failure f's
-// entries go to cptr[f] .. cptr[f + 1]; an entry past cptr[f + 1] sets bit 6
+// entries go to cptr[f] .. cptr[f + 1]; an entry past cptr[f + 1] sets kFaultListRoom
 // of the context's fault word and is dropped.
 struct WiEmit {
   uint32_t* cnt = nullptr;                    // [n_fail], zeroed before the count pass
@@ -302,7 +302,7 @@ struct spf_ctx : spfi::GraphHost {
   spfi::DevBuf<uint32_t> d_pred_cnt, d_pred_edge, d_link, d_ign, d_one_src, d_row;
   spfi::DevBuf<unsigned long long> d_pred_key;
   spfi::DevBuf<uint32_t> d_gq, d_gq2, d_gbm, d_gctr;  // global-memory SSSP scratch
-  spfi::DevBuf<uint32_t> d_gbar;  // its grid-barrier counters (whatif.hip XGrid)
+  spfi::DevBuf<uint32_t> d_gbar;  // its grid-barrier counters (grid_ops.h XGrid)
   // ecc_estimate's and depth_bound's memory of the graph (plan_host.h)
   spfi::DepthCache depth;
   // mssp_kernel tables (mssp.hip), valid for graph epoch mp_epoch
@@ -429,7 +429,7 @@ struct spf_plan {
   spfi::DevBuf<uint32_t> d_csrc, d_crow_of;
   spfi::DevBuf<uint8_t> d_cfwd;
   spfi::DevBuf<uint16_t> d_Dc;
-  bool big = false;  // spf_big_kernel (whatif.hip): graphs beyond the LDS kernels
+  bool big = false;  // spf_big_kernel (grid_spf.hip): graphs beyond the LDS kernels
   spfi::DevBuf<uint32_t> b_q, b_q2, b_bm, b_ctr, b_nbr_bit, b_nhb, b_lvl, b_order, b_misc, b_parent;
   spfi::DevBuf<uint32_t> b_bar;  // spf_big_kernel's grid-barrier counters
   spfi::DevBuf<uint64_t> d_nh_off;
@@ -593,8 +593,8 @@ spf_status mssp_prepare(spf_ctx* c);
 spf_status mssp_set_lds_limits(spf_ctx* c);
 spf_status launch_mssp(spf_ctx* c, const uint32_t* rows_src, uint32_t rows, uint32_t* D,
                        uint8_t* Dn, uint32_t* redo, hipStream_t s, uint32_t* maxd = nullptr);
-// Single-source SSSP in global memory, one cooperative grid (any graph
-// size); scratch lives in the context.  dist = [N].
+// Single-source SSSP in global memory, one grid-resident launch (any graph
+// size, grid_spf.hip); scratch lives in the context.  dist = [N].
 spf_status launch_gsssp(spf_ctx* c, uint32_t src, bool hop, const uint32_t* ign, uint32_t* dist,
                         hipStream_t s);
 // The exact kernel (exact.hip) over n_src sources: dist rows (u32 or u64,
@@ -646,11 +646,34 @@ spf_status pool_buffers(spf_whatif_plan* p, WiPoolId id, const char* who, const 
                         uint32_t* n_owners, uint32_t* W, uint64_t* n_entries);
 spf_status pool_db(spf_whatif_plan* p, WiPoolId id, const char* who, uint32_t owner, uint32_t* key,
                    uint64_t* val, uint32_t* rows, uint64_t cap, uint64_t* n);
-// spf_big_kernel (whatif.hip): the plan's sources one after another on the
+// spf_big_kernel (grid_spf.hip): the plan's sources one after another on the
 // whole chip -- frontier SSSP into the dist rows, next hops in distance
 // order, transposed into the plan's bitmaps.  Positive metrics or hop counts.
 spf_status launch_big(spf_ctx* c, spf_plan* p, uint32_t* d_dist, uint32_t* d_nh, bool hop,
                       hipStream_t s);
+// The launch rule of every kernel whose blocks meet at barriers (grid_spf.hip):
+// launch_resident is a regular launch checked for co-residency, coop_blocks the
+// grid of a 512-thread grid-barrier kernel at `per_cu` blocks per CU.
+hipError_t launch_resident(const void* kernel, uint32_t blocks, uint32_t threads, void** args,
+                           uint32_t n_cu, hipStream_t s);
+uint32_t coop_blocks(spf_ctx* c, const void* kernel, uint32_t per_cu);
+// whatif_base_kernel (grid_spf.hip), the unfailed pass of a what-if batch --
+// SPF of `src`, next-hop rows of W words, parent subtree sizes, result hash --
+// over a plan's buffers (whatif.hip fills this from spf_whatif_plan).
+constexpr uint32_t kLevelCap = 1u << 16;  // distance values bucketed directly (lvl's size - 1)
+#pragma GCC visibility push(hidden)
+struct BaseBufs {
+  uint32_t src, W;
+  const uint32_t* nbr_bit;  // [N] j if v is src's j-th distinct neighbour, else kInf
+  uint32_t *dist, *q, *q2, *bm, *ctr;  // [N] x 3, [ceil(N / 32)], [4]
+  uint32_t* bar;                       // [kGridBarWords]
+  uint32_t *nhb, *lvl, *order, *misc;  // [N][W], [kLevelCap + 1], [N], [8]
+  unsigned long long* H;
+  uint32_t *parent, *sub;              // [N] x 2
+  unsigned long long *prof, *lprof;    // SPF_WHATIF_PROF: [16] phase clocks, [2 x 64] per level; or NULL
+};
+spf_status launch_base(spf_ctx* c, const BaseBufs& b, hipStream_t s);
+#pragma GCC visibility pop
 // Raise the dynamic-LDS limit of the engine's LDS-resident kernels (once per
 // process; each unit registers its own, spf_units.h).
 spf_status set_lds_limits(spf_ctx* c);

@@ -23,6 +23,7 @@
 //  pathLinks by it).
 // ============================================================================
 #include "engine_internal.h"
+#include "grid_ops.h"
 
 using namespace spfi;
 
@@ -402,7 +403,7 @@ __global__ __launch_bounds__(kExactThreads) void exact_whatif_kernel(ExactArgs a
               __builtin_nontemporal_store(done && x < Wk ? s.nh[(size_t)v * W + x] : 0u,
                                           &e.cnh[(at + q) * e.W + x]);
           } else if (e.fault) {
-            __hip_atomic_fetch_or(e.fault, 64u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_fetch_or(e.fault, kFaultListRoom, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
           }
         }
         kq += (uint32_t)__popcll(m);

@@ -47,6 +47,7 @@
 //  is used; a violation sets the fault word and the call fails.
 // ============================================================================
 #include "engine_internal.h"
+#include "list_owner.h"
 
 using namespace spfi;
 
@@ -175,20 +176,9 @@ __global__ __launch_bounds__(kKdThreads) void ksp2_delta_kernel(Gen o, Gen n, ui
 }
 
 // ---- the payload -----------------------------------------------------------
-// entry j of dset belongs to the source slot i with dptr[i] <= j < dptr[i + 1]
-__device__ __forceinline__ uint32_t owner_of(const unsigned long long* __restrict__ ptr, uint32_t n,
-                                             unsigned long long j) {
-  uint32_t lo = 0, hi = n;  // ptr[lo] <= j < ptr[hi]
-  while (hi - lo > 1) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (ptr[mid] <= j) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
 // uptr[j] = entry j's records (0 for a delete), usrc[j] = its first record in
-// the plan's pool.
+// the plan's pool; entry j of dset belongs to the source slot
+// list_owner(dptr, n_src, j).
 __global__ __launch_bounds__(kKdThreads) void ksp2_update_count_kernel(
     const unsigned long long* __restrict__ dptr, const uint32_t* __restrict__ dset, uint32_t n_src,
     unsigned long long entries, const unsigned long long* __restrict__ rptr, unsigned long long hops,
@@ -199,7 +189,7 @@ __global__ __launch_bounds__(kKdThreads) void ksp2_update_count_kernel(
   const uint32_t v = dset[j];
   unsigned long long c = 0, at = 0;
   if (!(v & SPF_DELTA_DELETE)) {
-    const uint32_t i = owner_of(dptr, n_src, j);
+    const uint32_t i = list_owner(dptr, n_src, j);
     if (v < S) {
       const unsigned long long r = (unsigned long long)i * S + v;
       const unsigned long long a = rptr[r], b = rptr[r + 1];
@@ -229,12 +219,7 @@ __global__ __launch_bounds__(kKdThreads) void ksp2_update_records_kernel(
   if (k >= n_urec) return;
   // (entries < 2^32: dset entries of n_src < 2^32 sources x n_sets < 2^31 are
   // bounded by the caller; the search runs over 64-bit positions)
-  unsigned long long lo = 0, hi = entries;  // uptr[lo] <= k < uptr[hi]
-  while (hi - lo > 1) {
-    const unsigned long long mid = lo + (hi - lo) / 2;
-    if (uptr[mid] <= k) lo = mid;
-    else hi = mid;
-  }
+  const unsigned long long lo = list_owner(uptr, entries, k);
   const unsigned long long h = usrc[lo] + (k - uptr[lo]);
   unsigned long long r = 0, l0 = 0, l1 = 0;
   if (h < hops) {

@@ -38,6 +38,7 @@
 //  counters run on across batches, so flags and barriers need no reset.
 // ============================================================================
 #include "engine_internal.h"
+#include "grid_ops.h"
 #include "wave_ops.h"
 
 #include <cstdio>
@@ -128,7 +129,7 @@ __device__ __forceinline__ uint32_t team_arrive(uint32_t* word, uint32_t G, uint
       __builtin_amdgcn_s_sleep(1);
     }
     // 2 = a team barrier: spf_device_check turns team plans off on the context
-    if (k == kTmSpin) __hip_atomic_fetch_or(fault, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (k == kTmSpin) __hip_atomic_fetch_or(fault, kFaultTeamBarrier, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     *bcast = w;
   }
   __syncthreads();
@@ -158,7 +159,7 @@ __global__ __launch_bounds__(kTmThreads) void msbfs_team_kernel(TeamArgs a,
   const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   // test hook (SPF_TEAM_FLUSH_DBG bit 32): report a team-barrier timeout
   if ((a.dbg & 32u) && blockIdx.x == 0 && tid == 0)
-    __hip_atomic_fetch_or(a.fault, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_fetch_or(a.fault, kFaultTeamBarrier, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   // block -> (XCD, team on it, member): blocks are dealt to the XCDs round
   // robin, so blockIdx % 8 is the XCD; members of a team share its L2
   const uint32_t xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;

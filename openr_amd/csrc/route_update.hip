@@ -23,6 +23,7 @@
 //  atomic, the launch boundaries order the passes.
 // ============================================================================
 #include "engine_internal.h"
+#include "list_owner.h"
 
 #include <cstdlib>
 
@@ -34,22 +35,7 @@ constexpr uint32_t kUpThreads = 256;
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr unsigned long long kSrcMask = (1ull << 48) - 1;  // src[j] = first record | stride << 48
 
-// the me slot whose entries [dptr[slot], dptr[slot + 1]) hold j: the last slot
-// with dptr[slot] <= j (slots without entries share their successor's start)
-__device__ __forceinline__ uint32_t slot_of(const unsigned long long* __restrict__ dptr, uint32_t n_me,
-                                            unsigned long long j) {
-  uint32_t lo = 0, hi = n_me;  // dptr[lo] <= j < dptr[hi]
-  while (hi - lo > 1) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (dptr[mid] <= j)
-      lo = mid;
-    else
-      hi = mid;
-  }
-  return lo;
-}
-
-// IP routes.  Entry j = dset[j]: a set index p of me slot_of(j), SPF_DELTA_DELETE
+// IP routes.  Entry j = dset[j]: a set index p of me slot list_owner(dptr, n_me, j), SPF_DELTA_DELETE
 // set on a delete.  Route (slot, p)'s header = offset | count << 32 | stride <<
 // 48 within me's region at base[slot]: record k at pool[base[slot] + offset +
 // k * stride] (the stride is the writing kernel's tile width).
@@ -63,7 +49,7 @@ __global__ __launch_bounds__(kUpThreads) void update_count_ip_kernel(
   const uint32_t v = dset[j];
   unsigned long long cnt = 0, from = 0;
   if (!(v & SPF_DELTA_DELETE)) {
-    const uint32_t slot = slot_of(dptr, n_me, j);
+    const uint32_t slot = list_owner(dptr, n_me, j);
     const unsigned long long h = hdr[(size_t)slot * S + v];
     cnt = (h >> 32) & 0xFFFFull;
     from = (base[slot] + (h & 0xFFFFFFFFull)) | (h >> 48) << 48;
@@ -99,7 +85,7 @@ __global__ __launch_bounds__(kUpThreads) void update_count_label_kernel(
     }
     const uint32_t g = lo < U && lab[lo] == v ? map_new[lo] : kNone;
     if (g != kNone && g < G) {  // (an update's label is advertised in the new generation)
-      const size_t at = (size_t)slot_of(dptr, n_me, j) * G + g;
+      const size_t at = (size_t)list_owner(dptr, n_me, j) * G + g;
       own = owner[at];
       from = ptr[at];
       cnt = ptr[at + 1] - from;

@@ -23,7 +23,8 @@
 //  No buffer is n_fail x n_keys.  Everything is device scope on one GPU.
 // ============================================================================
 #include "engine_internal.h"
-#include "whatif_owner.h"
+#include "grid_ops.h"
+#include "list_owner.h"
 
 #include <cstddef>
 #include <string>
@@ -115,7 +116,7 @@ __global__ __launch_bounds__(kThreads) void wi_count_kernel(WiArgs a) {
   if (e >= a.total) return;
   const uint32_t k = a.key[e];
   if (k >= a.n_keys) {  // not a key of this plan: nothing is touched
-    atomicOr(a.fault, 64u);
+    atomicOr(a.fault, kFaultListRoom);
     return;
   }
   const unsigned long long d = a.dist[e], bd = base_metric(a, k);
@@ -139,7 +140,7 @@ __global__ __launch_bounds__(kThreads) void wi_fill_kernel(WiArgs a) {
   const unsigned long long lo = a.tptr[k], hi = a.tptr[k + 1];
   const unsigned long long at = lo + atomicAdd(&a.cur[k], 1u);
   if (at >= hi || hi > a.total) {  // more entries than were counted: dropped
-    atomicOr(a.fault, 64u);
+    atomicOr(a.fault, kFaultListRoom);
     return;
   }
   a.tfail[at] = i;

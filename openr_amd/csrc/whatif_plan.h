@@ -89,9 +89,6 @@ struct spf_whatif_plan {
 
 namespace spfi {
 
-// (whatif.hip) A launch whose blocks meet at barriers, checked for co-residency.
-hipError_t launch_resident(const void* kernel, uint32_t blocks, uint32_t threads, void** args,
-                           uint32_t n_cu, hipStream_t s);
 // (whatif.hip) What the create calls of every kind start with: their NULL,
 // loaded-graph and source checks (`who` names the call in the NULL message).
 spf_status create_prologue(spf_ctx* c, spf_whatif_plan** out, uint32_t src, const char* who);

@@ -13,6 +13,7 @@
 #define OPENR_AMD_WHATIF_REPAIR_H
 
 #include "engine_internal.h"
+#include "grid_ops.h"
 #include "wave_ops.h"
 
 using namespace spfi;
@@ -151,139 +152,11 @@ __device__ __forceinline__ bool grows(const SetRef<KIND>& sr, uint32_t src, uint
     return dx + w == dc;
 }
 
-__device__ __forceinline__ uint32_t ld(const uint32_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st(uint32_t* p, uint32_t v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Wave-wide minimum with DPP moves (row shifts, then row broadcasts; lanes
-// with no source keep ~0u) -- __shfl compiles to ds_bpermute, an LDS round
-// trip per step.  Every lane of the wave must be active.
-__device__ __forceinline__ uint32_t wave_min32(uint32_t x) {
-  x = min(x, (uint32_t)__builtin_amdgcn_update_dpp(~0u, x, 0x111, 0xf, 0xf, false));  // row_shr:1
-  x = min(x, (uint32_t)__builtin_amdgcn_update_dpp(~0u, x, 0x112, 0xf, 0xf, false));  // row_shr:2
-  x = min(x, (uint32_t)__builtin_amdgcn_update_dpp(~0u, x, 0x114, 0xf, 0xf, false));  // row_shr:4
-  x = min(x, (uint32_t)__builtin_amdgcn_update_dpp(~0u, x, 0x118, 0xf, 0xf, false));  // row_shr:8
-  x = min(x, (uint32_t)__builtin_amdgcn_update_dpp(~0u, x, 0x142, 0xa, 0xf, false));  // row_bcast:15
-  x = min(x, (uint32_t)__builtin_amdgcn_update_dpp(~0u, x, 0x143, 0xc, 0xf, false));  // row_bcast:31
-  return __builtin_amdgcn_readlane(x, 63);
-}
-
-__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
-
-struct WiGraph {
-  const uint32_t* row_ptr;
-  const uint32_t* col;
-  const uint32_t* wt;
-  const uint32_t* rev;
-  const uint32_t* link;
-  const uint8_t* ovl;
-  const uint32_t* nbr_bit;  // [N] j if v is the src's j-th distinct neighbour, else kInf
-  uint32_t N, src, W;
-  uint32_t hop = 0;  // hop counts: every up link weighs 1 (useLinkMetric = false)
-  uint32_t* fault = nullptr;  // the context's barrier-timeout word (spf_device_check)
-  // per CSR edge, interleaved: {col, wt, link, wt of the reverse edge} -- one
-  // 16-byte load where the wave teams' repairs read four arrays (and the
-  // rev -> wt chain) at random nodes (what-if plans)
-  const uint4* ed = nullptr;
-};
-
-// directed weight of the edge reverse to e (tail -> head of the in-edge)
-__device__ __forceinline__ uint32_t in_w(const WiGraph& g, uint32_t e) {
-  return g.hop ? 1u : g.wt[g.rev[e]];
-}
-
 struct WiBase {
   const uint32_t* dist;  // [N] unfailed distances
   const uint32_t* nhb;   // [N][W] unfailed next-hop bitsets
   const unsigned long long* H;  // unfailed hash
 };
-
-constexpr uint32_t kBarSpin = 1u << 26;            // ~seconds: never a silent hang
-
-// A barrier spin that ran out (a member never arrived: not co-resident, or
-// a fault) sets the launching context's fault word and falls through; the
-// host reads and clears it (spf_device_check) and reports SPF_E_HIP instead
-// of the launch's output.  One word per context (spf_ctx::d_fault), so a
-// check on one context neither reports nor clears another's timeout.
-__device__ __forceinline__ void barrier_timed_out(uint32_t* fault) {
-  if (fault) __hip_atomic_fetch_or(fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// A repair loop that reached its iteration bound (it cannot, for a correct
-// kernel: every bound is the loop's worst case + 2) reports where instead of
-// spinning on: bit 3 of the fault word, the phase in bits 8-15
-// (spf_device_check names it).  1 D discovery, 2 label-correcting sweeps,
-// 3 next-hop fixed point.
-__device__ __forceinline__ void loop_bound_hit(uint32_t* fault, uint32_t phase) {
-  if (fault)
-    __hip_atomic_fetch_or(fault, 8u | (phase << 8), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// After one barrier timed out the launch's results are void; later barriers
-// must not each wait out their own spin (a desynchronised team would cross
-// thousands of them): a spin polls the fault word every 1024 polls and gives
-// up once it is set.
-__device__ __forceinline__ bool fault_set(const uint32_t* fault) {
-  return fault && __hip_atomic_load(fault, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
-}
-
-// inclusive prefix sum over the wave (DPP row shifts + row broadcasts)
-__device__ __forceinline__ uint32_t wave_incl_scan32(uint32_t x) {
-  x += __builtin_amdgcn_update_dpp(0u, x, 0x111, 0xf, 0xf, true);   // row_shr:1
-  x += __builtin_amdgcn_update_dpp(0u, x, 0x112, 0xf, 0xf, true);   // row_shr:2
-  x += __builtin_amdgcn_update_dpp(0u, x, 0x114, 0xf, 0xf, true);   // row_shr:4
-  x += __builtin_amdgcn_update_dpp(0u, x, 0x118, 0xf, 0xf, true);   // row_shr:8
-  x += __builtin_amdgcn_update_dpp(0u, x, 0x142, 0xa, 0xf, false);  // row_bcast:15
-  x += __builtin_amdgcn_update_dpp(0u, x, 0x143, 0xc, 0xf, false);  // row_bcast:31
-  return x;
-}
-
-// ---------------------------------------------------------------------------
-//  wave helpers of the repairs: lanes over flattened edges
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t lane_pull(uint32_t x, uint32_t k) {
-  return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(k << 2), (int)x);
-}
-__device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
-// The edges of up to 64 nodes (lane k holds node v, `valid`), flattened:
-// chunks of 64 (node slot, edge) pairs.  f(k, e, act) runs on every lane of
-// the wave (so it may ballot / pull); `act` marks the lanes holding an edge,
-// k is the node slot (lane) that edge belongs to.  All 64 lanes must be
-// active.
-template <class F>
-__device__ __forceinline__ void wave_edges(const uint32_t* __restrict__ row_ptr, uint32_t v,
-                                           bool valid, F&& f) {
-  const uint32_t lane = threadIdx.x & 63;
-  uint32_t b0 = 0, deg = 0;
-  if (valid) {
-    b0 = row_ptr[v];
-    deg = row_ptr[v + 1] - b0;
-  }
-  const uint32_t incl = wave_incl_scan32(deg);
-  const uint32_t total = __builtin_amdgcn_readlane(incl, 63);
-  const uint32_t excl = incl - deg;
-  for (uint32_t base = 0; base < total; base += 64) {
-    const uint32_t s = base + lane;
-    // owner: the last slot whose first edge is <= s (slots with no edges
-    // share their successor's offset and lose to it)
-    uint32_t k = 0;
-#pragma unroll
-    for (uint32_t step = 32; step; step >>= 1)
-      if (lane_pull(excl, k + step) <= s) k += step;
-    const uint32_t e = lane_pull(b0, k) + s - lane_pull(excl, k);
-    f(k, e, s < total);
-  }
-}
 
 // ---------------------------------------------------------------------------
 //  repair of one hot failure by a team (a wave, or a whole workgroup)
@@ -419,7 +292,7 @@ __device__ __forceinline__ bool entry_changed(const WiBase& B, const uint32_t* n
 // when unreachable, not the stale row).  Rows of up to 4 words are copied by
 // the entry's own lane, wider ones by the wave, lane = word.  Nothing reads
 // the pools again on the device: streaming stores.  An entry past the
-// failure's allocated count (`room`) is dropped and sets bit 6 of the fault
+// failure's allocated count (`room`) is dropped and sets kFaultListRoom in the fault
 // word.  Every lane of the wave must be active.
 template <bool GROUP>
 __device__ __forceinline__ void emit_entries(const WiEmit& em, uint64_t at, uint32_t room,
@@ -430,7 +303,7 @@ __device__ __forceinline__ void emit_entries(const WiEmit& em, uint64_t at, uint
   const uint32_t q = q0 + lanes_below(m);
   const bool put = changed && q < room;
   if (changed && !put && em.fault)
-    __hip_atomic_fetch_or(em.fault, 64u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_fetch_or(em.fault, kFaultListRoom, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   if (put) {
     __builtin_nontemporal_store(v, &em.cnode[at + q]);
     __builtin_nontemporal_store(d1 == kInf ? ~0ull : (unsigned long long)d1, &em.cdist[at + q]);
@@ -609,7 +482,7 @@ __device__ bool repair(const WiGraph& g, const WiBase& B, uint32_t* mark, uint32
     if constexpr (CHK) {
       if (!(x < lim || (inf_ok && x == kInf))) {
         if (g.fault)
-          __hip_atomic_fetch_or(g.fault, 16u | (site << 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          __hip_atomic_fetch_or(g.fault, kFaultRange | (site << kFaultSiteShift), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         return safe;
       }
     }
@@ -1152,7 +1025,7 @@ __device__ bool repair_wave(const WiGraph& g, const WiBase& B, const WaveSet& hs
     if constexpr (CHK) {
       if (!(x < lim || (inf_ok && x == kInf))) {
         if (g.fault)
-          __hip_atomic_fetch_or(g.fault, 16u | (site << 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          __hip_atomic_fetch_or(g.fault, kFaultRange | (site << kFaultSiteShift), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         return safe;
       }
     }
@@ -1424,14 +1297,14 @@ __device__ bool repair_wave(const WiGraph& g, const WiBase& B, const WaveSet& hs
 }
 
 // The profiled instances' phase-counter row of `team` (16 slots) in a
-// region of `rows` rows: a team past the region sets bit 5 of the fault word
+// region of `rows` rows: a team past the region sets kFaultProfRow in the fault word
 // (kernel in bits 24-31) and counts nothing -- the layout of the prof buffer
 // ([block / group teams][base][wave teams] x 16, spf_whatif_plan_create) is
 // checked, not assumed.
 __device__ __forceinline__ uint64_t* prof_row(unsigned long long* prof, size_t team, uint32_t rows,
                                               uint32_t kernel, uint32_t* fault) {
   if (team < rows) return reinterpret_cast<uint64_t*>(prof + 16 * team);
-  if (fault) __hip_atomic_fetch_or(fault, 32u | (kernel << 24), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (fault) __hip_atomic_fetch_or(fault, kFaultProfRow | (kernel << kFaultKernelShift), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   return nullptr;
 }
 

@@ -40,7 +40,8 @@
 //  meet T.  The walk itself decides, T only selects.
 // ============================================================================
 #include "engine_internal.h"
-#include "whatif_owner.h"
+#include "grid_ops.h"
+#include "list_owner.h"
 #include "whatif_pool_host.h"
 #include "whatif_route_update_host.h"
 
@@ -251,7 +252,7 @@ __global__ __launch_bounds__(kThreads) void wu_base_kernel(WuArgs a) {
     if (m == kNoRoute || !bn) return;
     wu_walk<LDS>(a, kNone, f, nh, [&](uint32_t k, uint32_t t) {
       if (k < bn) a.brec[bp + k] = (unsigned long long)(a.row0 + t) | (m << 32);
-      else atomicOr(a.fault, 64u);
+      else atomicOr(a.fault, kFaultListRoom);
     });
   }
 }
@@ -326,7 +327,7 @@ __device__ __forceinline__ void wu_claim(const WuArgs& a, uint32_t i, uint32_t s
   } else {
     const unsigned long long at = a.uptr[i] + atomicAdd(&a.cur[i], 1u);
     if (at >= a.uptr[i + 1]) {  // more entries than were counted: dropped
-      atomicOr(a.fault, 64u);
+      atomicOr(a.fault, kFaultListRoom);
       return;
     }
     a.uset[at] = s;
@@ -398,7 +399,7 @@ __global__ __launch_bounds__(kThreads) void wu_records_kernel(WuArgs a) {
   const uint32_t* nh = e != kNone ? a.rnh + (size_t)e * a.W : a.rbnh + (size_t)s * a.W;
   wu_walk<LDS>(a, i, wu_fail(a, i), nh, [&](uint32_t k, uint32_t t) {
     if (k < rn) a.urec[rp + k] = (unsigned long long)(a.row0 + t) | (m << 32);
-    else atomicOr(a.fault, 64u);
+    else atomicOr(a.fault, kFaultListRoom);
   });
 }
 

@@ -32,8 +32,9 @@
 //  no failure kind makes a node reachable.
 // ============================================================================
 #include "engine_internal.h"
+#include "grid_ops.h"
 #include "wave_ops.h"
-#include "whatif_owner.h"
+#include "list_owner.h"
 #include "whatif_routes_host.h"
 
 #include <numeric>
@@ -146,7 +147,7 @@ __device__ __forceinline__ unsigned long long wr_claim(const WrArgs& a, uint32_t
   } else {
     const unsigned long long at = a.rptr[i] + atomicAdd(&a.cur[i], 1u);
     if (at >= a.rptr[i + 1]) {  // more entries than were counted: dropped
-      atomicOr(a.fault, 64u);
+      atomicOr(a.fault, kFaultListRoom);
       return kNoRoute;
     }
     return at;
