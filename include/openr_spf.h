@@ -986,8 +986,10 @@ spf_status spf_whatif_route_update_timing(const spf_whatif_plan* plan, double* m
 spf_status spf_whatif_route_update_stats(spf_whatif_plan* plan, uint32_t* n_touched,
                                          uint64_t* base_records);
 /* Launch constants the tests cross: the sets a workgroup of the sweep takes per
- * round, and the counts the pools' scan takes per round. */
+ * round, the counts the pools' scan takes per round, and the longest row of
+ * src that the walking kernels stage in LDS (a longer one is read from L2). */
 uint32_t spf_whatif_route_update_sweep_sets(void);
+uint32_t spf_whatif_route_update_lds_slots(void);
 uint32_t spf_whatif_scan_tile(void);
 /* ---- what-if impact by destination: the lists above, keyed by what is hit.
  * The change and route lists are keyed by the failure.  "Which failures touch

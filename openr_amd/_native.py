@@ -309,6 +309,7 @@ PROTOTYPES = {
     "spf_whatif_route_update_timing": (C.c_int, [_vp, C.POINTER(C.c_double)]),
     "spf_whatif_route_update_stats": (C.c_int, [_vp, _u32p, _u64p]),
     "spf_whatif_route_update_sweep_sets": (C.c_uint32, []),
+    "spf_whatif_route_update_lds_slots": (C.c_uint32, []),
     "spf_whatif_scan_tile": (C.c_uint32, []),
     "spf_whatif_impact_timing": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_double)]),
     **{f"spf_whatif_by_{flavour}{call}": (C.c_int, list(args))

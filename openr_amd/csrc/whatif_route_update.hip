@@ -735,6 +735,7 @@ spf_status spf_whatif_route_update_db(spf_whatif_plan* p, uint32_t i, uint32_t* 
 }
 
 uint32_t spf_whatif_route_update_sweep_sets(void) { return kThreads; }
+uint32_t spf_whatif_route_update_lds_slots(void) { return kLdsSlots; }
 uint32_t spf_whatif_scan_tile(void) { return kWhatifScanTile; }
 
 }  // extern "C"

@@ -5,7 +5,11 @@ for the failures that touch the source's row and a hundred seeded others per
 kind also ground truth that passes through no what-if code: a second engine
 loaded with the same arrays and the failure applied in place (a removed link
 becomes dead self-loop slots of metric 1, so CSR slots keep their positions),
-spf_routes there against spf_routes on the unfailed engine."""
+spf_routes there against spf_routes on the unfailed engine.
+
+Every case here has source 0, a row of at most 44 live slots and no overloaded
+node; test_gpu_whatif_route_update_edges.py takes the same Bench to the other
+sources, rows and graphs."""
 
 import ctypes as C
 

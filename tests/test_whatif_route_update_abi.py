@@ -54,6 +54,12 @@ def test_declared_exported_and_bound():
         assert callable(getattr(engine.WhatIfRouteUpdate, method))
     # the constants the GPU tests cross come from the code
     assert N.lib.spf_whatif_scan_tile() >= 1024 and N.lib.spf_whatif_route_update_sweep_sets() >= 64
+    for name in ("spf_whatif_route_update_lds_slots", "spf_whatif_route_update_sweep_sets",
+                 "spf_whatif_scan_tile"):
+        m = re.search(r"\buint32_t\s+" + name + r"\s*\(\s*void\s*\)\s*;", text)
+        assert m and hasattr(lib, name) and N.PROTOTYPES[name] == (C.c_uint32, []), name
+    # a staged slot is 16 bytes, and a workgroup may take 64 KB of LDS
+    assert 64 <= N.lib.spf_whatif_route_update_lds_slots() <= 4096
 
 
 def test_null_plan_is_invalid():

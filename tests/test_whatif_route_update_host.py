@@ -163,6 +163,34 @@ def test_the_seeded_multigraph_has_what_the_gpu_tests_rely_on(seeded):
     assert extra >= 20 and touching_with_changes >= 1, (extra, touching_with_changes)
 
 
+@pytest.fixture(scope="module")
+def hub():
+    g, h = U.hub_graph(8)
+    c = Case(g, h.hub, U.hub_sets(g, h))
+    c.h = h
+    return c
+
+
+def test_the_checker_meets_the_oracle_with_the_source_in_the_middle(hub):
+    """row0 != 0, and the source is the higher end of the links to half of its
+    neighbours: Row.weights' m_lo / m_hi convention against the oracle."""
+    c, g, h = hub, hub.g, hub.h
+    assert len(g.names) == 9 and int(g.rp[h.hub]) > 0 and c.row.q[0] == int(g.rp[h.hub])
+    assert min(h.nbrs) < h.hub < max(h.nbrs) and len(c.row.q) == 8
+    for x in (h.lower_bundle, h.upper_bundle):
+        assert sorted(int(c.row.w[t]) for t in range(8) if c.row.head[t] == x) == [2, 2, 4]
+    ecmp = [k for k, r in enumerate(c.base_recs) if len(set(c.row.head[(r & np.uint64(0xFFFFFFFF)).astype(np.int64) - c.row.q[0]])) > 1]
+    assert len(ecmp) >= 2  # sets with next hops towards two neighbours
+    fails = U.hub_failures(g, h)
+    lists = []
+    for fail in fails:
+        _, _, upd, orc = c.under(fail)
+        c.check_oracle(fail, upd, orc)
+        lists.append(upd)
+    assert any(len(u[0]) for f, u in zip(fails, lists) if f[0] == "link")
+    U.one_direction_moves(g, h, fails, lists)
+
+
 def test_row_tables_against_brute_force_under_sanitizers(tmp_path):
     cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
     if cxx is None:

@@ -170,6 +170,97 @@ def wide_graph():
     return Graph(topology("wide81", 81, links, w, w))
 
 
+class Hub:
+    """Where hub_graph put things: the source `hub`, its distinct neighbours
+    `nbrs` in bit order (the first `n_lower` of them have smaller ids than the
+    hub), the ring node behind nbrs[j] and nbrs[(j + 1) % k], and the two
+    bundled neighbours, one on each side of the hub."""
+
+    def __init__(self, hub, nbrs, n_lower, ring):
+        self.hub, self.nbrs, self.n_lower, self.ring = hub, nbrs, n_lower, ring
+        self.lower_bundle, self.upper_bundle = nbrs[n_lower - 1], nbrs[n_lower]
+
+
+def hub_graph(slots, nbrs=None):
+    """A source in the middle of the id range with exactly `slots` slots in its
+    row: `nbrs` distinct neighbours (metric 2), half with smaller ids than the
+    source and half with larger ones, and parallel links for the rest of the
+    row -- a bundle of two equal members and a heavier one (metric 4) to the
+    nearest neighbour on each side, then further equal members dealt out from
+    the last neighbour downwards.  Behind the neighbours a ring of as many
+    nodes, ring node j behind neighbours j (metric 1) and j + 1 (metric 1 or
+    2), so every second one has ECMP across two neighbours; half of the ring
+    has smaller ids than every neighbour, half larger ones.  Returns (Graph,
+    Hub); graph.rp[hub] > 0."""
+    k = max(4, slots - 4 - slots // 40) if nbrs is None else nbrs
+    assert k >= 4 and slots >= k + 4
+    a = k // 2
+    hub = 2 * a
+    nb = list(range(a, 2 * a)) + list(range(hub + 1, hub + 1 + k - a))
+    ring = list(range(a)) + list(range(hub + 1 + k - a, 2 * k + 1))
+    links, w = [], []
+    for x in nb:
+        links.append((hub, x))
+        w.append(2)
+    for x in (nb[a - 1], nb[a]):
+        links += [(hub, x), (hub, x)]
+        w += [2, 4]
+    for e in range(slots - k - 4):
+        links.append((hub, nb[k - 1 - e % k]))
+        w.append(2)
+    for j in range(k):
+        links += [(nb[j], ring[j]), (nb[(j + 1) % k], ring[j])]
+        w += [1, 1 + j % 2]
+    g = Graph(topology(f"hub{slots}_{k}", 2 * k + 1, links, w, w))
+    assert int(g.rp[hub + 1] - g.rp[hub]) == slots and int(g.rp[hub]) > 0
+    return g, Hub(hub, nb, a, ring)
+
+
+def hub_sets(g, h):
+    """Every node alone (the source's own prefix among them), anycast sets over
+    the ring and over the bundled neighbours on both sides, and an empty set."""
+    return [[v] for v in range(len(g.names))] + [
+        [h.ring[0], h.ring[2]], [h.nbrs[0], h.ring[-1]], [h.lower_bundle, h.upper_bundle],
+        [h.ring[1], h.hub], []]
+
+
+def hub_failures(g, h):
+    """Of the small hub graph: every up link failed and re-weighed in either
+    direction and in both, above and below its metric, and every other node
+    down and drained."""
+    w = {int(l): int(m) for l, m in zip(g.lid, g.met)}  # (the same in both directions)
+    fails = []
+    for l in g.up_links():
+        fails.append(("link", l))
+        for m in (1, 2, 3, 5):
+            if m != w[l]:
+                fails += [("metric", l, m, KEEP), ("metric", l, KEEP, m), ("metric", l, m, m)]
+    fails += [(kind, x) for kind in ("down", "drain") for x in range(len(g.names)) if x != h.hub]
+    return fails
+
+
+def one_direction_moves(g, h, fails, lists):
+    """The direction facts of a source that is the higher end of some of its
+    links: of the one-direction metric changes on the source's own links, the
+    one out of the source -- m_hi towards a neighbour of smaller id, m_lo
+    towards a larger one -- changes some set's records for some link on either
+    side, and the matching change of the direction into the source never does.
+    `lists[i]` is the update list of fails[i]."""
+    at = {f: i for i, f in enumerate(fails)}
+    moved = {True: 0, False: 0}
+    for e in range(int(g.rp[h.hub]), int(g.rp[h.hub + 1])):
+        x, l = int(g.col[e]), int(g.lid[e])
+        for f, i in at.items():
+            if f[0] != "metric" or f[1] != l or (f[2] == KEEP) == (f[3] == KEEP):
+                continue
+            outward = (f[3] != KEEP) if x < h.hub else (f[2] != KEEP)
+            if outward:
+                moved[x < h.hub] += len(lists[i][0]) > 0
+            else:
+                assert len(lists[i][0]) == 0, (f, lists[i])
+    assert moved[True] and moved[False], moved
+
+
 def seeded_graph(n=200, n_links=420, seed=3):
     """A seeded multigraph, metrics 1 to 4 (the same in both directions, so
     ties abound), a quarter of the links doubled; the source n000 gets three
