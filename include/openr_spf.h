@@ -1343,6 +1343,94 @@ spf_status spf_mplan_label_route_buffers(spf_mplan* mp, uint32_t member, const u
                                          const uint64_t** d_ptr, const uint64_t** d_rec,
                                          uint64_t* n_records, uint32_t* slots, uint32_t cap,
                                          uint32_t* n_slots);
+/* ---- prefix routes: the unicast route decision from prefix entries --------- */
+/* Every me's SP_ECMP / IP unicast route decision from the resident pass: what
+ * createRouteForPrefix (Decision.cpp:390-554) decides per me, which a fixed
+ * destination set per prefix (spf_mplan_route_records) cannot express.  One
+ * area, perDestination = false, no prepend labels.
+ * The prefix table is a CSR: prefix p's entries are [pfx_ptr[p], pfx_ptr[p+1])
+ * of ent_node (advertiser), ent_pp / ent_sp / ent_dist (PrefixMetrics'
+ * path_preference, source_preference, distance) and ent_min_nh (minNexthop;
+ * <= 0: none); overloaded[n_nodes] marks the drained nodes.  n_pfx == 0 and
+ * empty prefixes are valid (the arrays of a table without entries may be NULL).
+ * Per me = srcs[me_req[t]] and prefix p, on me's owning device:
+ *   R   the entries whose node is me or has a finite distance in me's row
+ *       (:411-424)
+ *   B0  the entries of R with the greatest (path_preference,
+ *       source_preference, -distance) that is >= (0, 0, 0) (selectBestRoutes
+ *       :725-752, selectBestPrefixMetrics Util.h:541-570: an entry under that
+ *       floor never enters, :544, 555); with SPF_PREFIX_ALL_BEST (best-route
+ *       selection off, :743-748) B0 = R
+ *   best  me when me is in B0, else B0's smallest id (selectBestNodeArea); with
+ *       SPF_PREFIX_ALL_BEST B0's smallest id (:747).  The drained filter never
+ *       moves it (:786-789 compares a copy with its source).
+ *   B   B0 without its overloaded nodes, or B0 when that would be empty
+ *       (maybeFilterDrainedNodes :771-792)
+ *   status, in this order:
+ *       SPF_PREFIX_NONE         B0 is empty
+ *       SPF_PREFIX_SELF         me is in B (:510-513; B, not B0: a drained me
+ *                               beside undrained peers routes to them, best = me)
+ *       SPF_PREFIX_NO_NEXTHOP   no next hop towards B
+ *       SPF_PREFIX_MIN_NEXTHOP  fewer next hops than the largest positive
+ *                               ent_min_nh over B (getMinNextHopThreshold
+ *                               :755-768, addBestPaths :1031-1041)
+ *       SPF_PREFIX_ROUTE        the next hops of spf_mplan_route_records'
+ *                               selection for the set B (SPF_ROUTE_LFA
+ *                               included), one u64 record each = CSR edge |
+ *                               metric << 32 in me's link order
+ *   Only SPF_PREFIX_ROUTE has records.
+ * Layout per member (CSR, as spf_mplan_label_routes): info[n * P] u64 = best |
+ * |B| << 32 | status << 56 (best = SPF_UNREACHABLE for SPF_PREFIX_NONE),
+ * ptr[n * P + 1] u64, rec[ptr[n * P]] u64, n = the member's me slots, P =
+ * n_pfx; route (slot k, p) holds rec[ptr[k * P + p] .. ptr[k * P + p + 1]).
+ * Built by three passes -- count, an exclusive scan, fill -- so the pool is
+ * sized exactly: *pool_bytes (optional) = over the members with a me, 8
+ * records + 8 (n P + 1) + 8 n P.  *n_records = records over every me,
+ * *kernel_ms = the slowest member's kernels (optional).  flags: SPF_ROUTE_LFA,
+ * SPF_PREFIX_ALL_BEST.
+ * SPF_E_INVALID, before anything is uploaded or launched and with the prefix
+ * named in the error: pfx_ptr not starting at 0 or decreasing, a node id >=
+ * n_nodes, the same node twice in one prefix, a distance of INT32_MIN.
+ * SPF_E_UNSUPPORTED for SPF_FLAG_HOP_COUNT / SPF_FLAG_DIST64 plans, a prefix
+ * of 2^24 entries or more, and when a metric exceeds 2^32 - 1.  After a call
+ * that failed the plan holds no prefix database.  The call leaves the plan's
+ * other databases (route records, label routes, snapshots, deltas) alone; the
+ * databases stay resident until the next call. */
+#define SPF_PREFIX_ALL_BEST 0x4u
+#define SPF_PREFIX_NONE 0u
+#define SPF_PREFIX_SELF 1u
+#define SPF_PREFIX_NO_NEXTHOP 2u
+#define SPF_PREFIX_MIN_NEXTHOP 3u
+#define SPF_PREFIX_ROUTE 4u
+spf_status spf_mplan_prefix_routes(spf_mplan* mp, const uint32_t* me_req, uint32_t n_me,
+                                   const uint32_t* pfx_ptr /* [n_pfx + 1] */, const uint32_t* ent_node,
+                                   const int32_t* ent_pp, const int32_t* ent_sp, const int32_t* ent_dist,
+                                   const int64_t* ent_min_nh, uint32_t n_pfx,
+                                   const uint8_t* overloaded /* [n_nodes] */, uint32_t flags,
+                                   uint64_t* n_records, uint64_t* pool_bytes, double* kernel_ms);
+/* me t's prefix routes from the last spf_mplan_prefix_routes: info = [P], ptr =
+ * [P + 1] rebased to 0, rec = its records (cap entries; SPF_E_NOMEM when fewer
+ * than *n); any may be NULL; *n = its record count.  SPF_E_INVALID when the
+ * plan holds no prefix database or t is not one of its me.  Waits. */
+spf_status spf_mplan_prefix_route_db(spf_mplan* mp, uint32_t t, uint64_t* info, uint64_t* ptr,
+                                     uint64_t* rec, uint64_t cap, uint64_t* n);
+/* A member's share of the last spf_mplan_prefix_routes, for device-side
+ * consumers: its info / ptr / rec device arrays (NULL when it holds no me),
+ * its record count, and slots[k] = the index t (into that call's me_req) of
+ * its k-th me slot (cap entries; SPF_E_NOMEM when fewer than *n_slots).  Every
+ * output may be NULL. */
+spf_status spf_mplan_prefix_route_buffers(spf_mplan* mp, uint32_t member, const uint64_t** d_info,
+                                          const uint64_t** d_ptr, const uint64_t** d_rec,
+                                          uint64_t* n_records, uint32_t* slots, uint32_t cap,
+                                          uint32_t* n_slots);
+/* ms[3] = count, scan, fill of the last spf_mplan_prefix_routes that asked for
+ * kernel_ms (the slowest member each); SPF_E_STATE without a prefix database. */
+spf_status spf_mplan_prefix_routes_timing(const spf_mplan* mp, double* ms);
+/* The prefixes of one block of the prefix-routes kernel, the links of me it
+ * stages on chip at a time, and the entries of one tile of the scan. */
+uint32_t spf_prefix_routes_threads(void);
+uint32_t spf_prefix_routes_links(void);
+uint32_t spf_prefix_routes_scan_tile(void);
 /* ---- route-database delta between two passes ------------------------------ */
 /* What Decision publishes after a rebuild is not the database but its
  * difference from the previous one: DecisionRouteDb::calculateUpdate

@@ -39,6 +39,9 @@ SPF_WHATIF_METRIC_KEEP = 0
 KSP2_KIND_NAMES = ("EXACT", "HBM", "LDS_U32", "LDS_U16")  # spf_ksp2_kind
 SPF_ROUTE_LFA = 0x1
 SPF_ROUTE_COMPACT = 0x2
+SPF_PREFIX_ALL_BEST = 0x4
+# status field of a prefix route's info word (spf_mplan_prefix_routes)
+SPF_PREFIX_NONE, SPF_PREFIX_SELF, SPF_PREFIX_NO_NEXTHOP, SPF_PREFIX_MIN_NEXTHOP, SPF_PREFIX_ROUTE = range(5)
 SPF_DELTA_DELETE = 0x80000000
 SPF_PARTITION_AUTO = 0
 SPF_PARTITION_CONTIGUOUS = 1
@@ -364,6 +367,19 @@ PROTOTYPES = {
     "spf_mplan_label_route_buffers": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp), C.POINTER(_vp),
                                                 C.POINTER(_vp), C.POINTER(C.c_uint64), _u32p,
                                                 C.c_uint32, _u32p]),
+    "spf_mplan_prefix_routes": (C.c_int, [_vp, _u32p, C.c_uint32, _u32p, _u32p, _i32p, _i32p, _i32p,
+                                          C.POINTER(C.c_int64), C.c_uint32, _u8p, C.c_uint32,
+                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_double)]),
+    "spf_mplan_prefix_route_db": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64)]),
+    "spf_mplan_prefix_route_buffers": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp), C.POINTER(_vp),
+                                                 C.POINTER(_vp), C.POINTER(C.c_uint64), _u32p,
+                                                 C.c_uint32, _u32p]),
+    "spf_mplan_prefix_routes_timing": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "spf_prefix_routes_threads": (C.c_uint32, []),
+    "spf_prefix_routes_links": (C.c_uint32, []),
+    "spf_prefix_routes_scan_tile": (C.c_uint32, []),
     "spf_mplan_route_snapshot": (C.c_int, [_vp, _u64p, C.c_uint32, C.POINTER(_vp)]),
     "spf_route_snapshot_destroy": (None, [_vp]),
     "spf_route_snapshot_bytes": (C.c_uint64, [_vp]),

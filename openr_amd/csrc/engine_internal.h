@@ -753,8 +753,23 @@ spf_status launch_label_routes(spf_ctx* c, bool fill, const unsigned long long* 
 // d_ptr[0 .. n) -> its exclusive scan in place, d_ptr[n] = the total; d_sums =
 // label_scan_tiles(n) words of scratch.  Deterministic.
 uint64_t label_scan_tiles(uint64_t n);
+uint32_t label_scan_tile();  // entries per tile
 spf_status launch_label_scan(spf_ctx* c, unsigned long long* d_ptr, uint64_t n,
                              unsigned long long* d_sums, hipStream_t s);
+// Prefix routes of many `me` over resident rows (prefix_routes.hip): the count
+// pass (fill = false: d_info[n_me * P] = best | |B| << 32 | status << 56, the
+// counts into d_ptr) or the fill pass (d_rec at the scanned d_ptr); d_flags bit
+// 1: a metric past 2^32 - 1.  Prefix p = d_ent[d_pfx_ptr[p] .. d_pfx_ptr[p + 1])
+// (prefix_table_host.h).  prefix_routes_threads / _links: the prefixes of a
+// block, the links it stages at a time.
+struct PrefixEnt;
+spf_status launch_prefix_routes(spf_ctx* c, bool fill, const unsigned long long* d_rowp,
+                                const unsigned long long* d_nhp, const uint32_t* d_me, uint32_t n_me,
+                                const uint32_t* d_pfx_ptr, const PrefixEnt* d_ent, uint32_t P, bool lfa,
+                                bool all_best, unsigned long long* d_info, unsigned long long* d_ptr,
+                                unsigned long long* d_rec, uint32_t* d_flags, hipStream_t s);
+uint32_t prefix_routes_threads();
+uint32_t prefix_routes_links();
 // Route-database delta between two generations (route_delta.hip), per member:
 // its me slots' node ids, where each me's OLD row started and how long it was,
 // key[e] = link_hash[link_id[e]] over the old and the new CSR, and same[slot]

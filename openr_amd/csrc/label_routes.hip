@@ -239,6 +239,7 @@ __global__ __launch_bounds__(kLrThreads) void scan_apply_kernel(
 namespace spfi {
 
 uint64_t label_scan_tiles(uint64_t n) { return (n + kScanTile - 1) / kScanTile; }
+uint32_t label_scan_tile() { return kScanTile; }
 
 spf_status launch_label_routes(spf_ctx* c, bool fill, const unsigned long long* d_rowp,
                                const unsigned long long* d_nhp, const uint32_t* d_me, uint32_t n_me,

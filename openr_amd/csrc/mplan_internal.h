@@ -3,8 +3,8 @@
 //  as multi.cpp (context, plan creation, execute, reads, graphs, enqueue
 //  threads, timing) and mplan_routes.cpp (the route-database pipeline over the
 //  resident pass) share them.  A plan's route state is grouped by the stage
-//  that writes it -- selection tables, route records, label routes, delta,
-//  update -- once per member (spf_mplan::Part) and once per plan.  Not part of
+//  that writes it -- selection tables, route records, label routes, prefix
+//  routes, delta, update -- once per member (spf_mplan::Part) and once per plan.  Not part of
 //  the C-ABI.
 // ============================================================================
 #pragma once
@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "engine_internal.h"
+#include "prefix_table_host.h"
 
 // One generation of every me's route databases, moved out of the plan that
 // materialised them (spf_mplan_route_snapshot): the pools per member, and by
@@ -114,6 +115,16 @@ struct spf_mplan {
       std::vector<uint32_t> req;  // per me slot: its index t in the call's me list
       uint64_t records = 0;
     } lr;
+    // prefix routes (spf_mplan_prefix_routes): the uploaded prefix table, per
+    // (me slot, prefix) the info word and the u64 offset of its records (CSR
+    // form), the exactly sized record pool, the scan's tile sums
+    struct Prefixes {
+      spfi::DevBuf<uint32_t> pptr, me, flags;
+      spfi::DevBuf<spfi::PrefixEnt> ent;
+      spfi::DevBuf<unsigned long long> info, ptr, rec, sums;
+      std::vector<uint32_t> req;  // per me slot: its index t in the call's me list
+      uint64_t records = 0;
+    } px;
     // route-database delta (spf_mplan_route_delta): per me slot where its old
     // database lives, the kind bytes and scanned block counts of the IP ([0])
     // and label ([1]) passes, the lists
@@ -160,6 +171,14 @@ struct spf_mplan {
     uint32_t rflags = 0, groups = 0;
     bool moved = false;
   } lr;
+  // ... the last spf_mplan_prefix_routes: its prefixes, and the count / scan /
+  // fill ms (slowest member each).  have: the plan holds a prefix database.
+  struct Prefixes {
+    Loc loc;
+    bool have = false;
+    uint32_t n_pfx = 0;
+    double ms[3] = {0, 0, 0};
+  } px;
   // The last spf_mplan_route_delta.  gen: db_gen as it was then (the update
   // resolves the delta's lists in those same databases); labels / uni / tot:
   // whether it had label routes, its label union's size, its totals.
@@ -181,6 +200,7 @@ struct spf_mplan {
   // "the plan holds a generation of X": what the readers and the later stages ask
   bool has_records() const { return !db.loc.empty() && !db.moved; }
   bool has_label_routes() const { return !lr.loc.empty() && !lr.moved; }
+  bool has_prefix_routes() const { return px.have; }
   bool has_delta() const { return !dl.loc.empty(); }
   bool has_update() const { return has_delta() && up.done; }
   std::unique_ptr<Part[]> parts;  // [n_parts]

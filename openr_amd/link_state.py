@@ -30,6 +30,23 @@ class LinkStateChange:
     nodeLabelChanged: bool = False
 
 
+@dataclass
+class PrefixTable:
+    """The prefix table of allSourcesPrefixRoutes (spf_mplan_prefix_routes), in
+    CSR form: prefix p's entries are [pfx_ptr[p], pfx_ptr[p + 1]) of node (csr
+    id of the advertiser), path_preference, source_preference, distance (int32
+    each) and min_nexthop (int64; <= 0: none).  prefixes: a name per prefix
+    (spf_solver.prefixTable fills it; optional)."""
+
+    pfx_ptr: "object"
+    node: "object"
+    path_preference: "object"
+    source_preference: "object"
+    distance: "object"
+    min_nexthop: "object"
+    prefixes: Optional[List[str]] = None
+
+
 class Link:
     """Snapshot of ``openr::Link`` (LinkState.h:82-175) taken at query time."""
 
@@ -639,6 +656,70 @@ class LinkState(N.NativeHandle):
                                                    N.ptr(rec, C.c_uint64), n.value, C.byref(n)),
                     N.global_error())
         return owner[:g], ptr, rec[: n.value]
+
+    def allSourcesPrefixRoutes(self, table: "PrefixTable", lfa: bool, mes=None, allBest: bool = False):
+        """Every node's (or the csr ids in `mes`) SP_ECMP / IP unicast route
+        decision for every prefix of `table` (createRouteForPrefix,
+        Decision.cpp:390-554: reachable advertisers, best entries by
+        PrefixMetrics, the drained filter, no route to oneself, minNexthop),
+        materialised on its owning GPU from the resident all-sources pass
+        (spf_mplan_prefix_routes); the overload flags are this link state's.
+        allBest: best-route selection off (SPF_PREFIX_ALL_BEST).  Returns
+        (records over every node, the pools' bytes, the slowest member's
+        kernel ms); read one node's with allSourcesPrefixRouteDb."""
+        import numpy as np
+
+        mp = N.lib.ls_all_sources_plan(self._h)
+        if not mp:
+            raise RuntimeError("allSourcesPrefixRoutes: no resident all-sources pass")
+        self._px = None
+        n = self._csr_sizes()[0]
+        ovl = np.ascontiguousarray(self.flatten()[5], np.uint8)
+        ovl = ovl if len(ovl) else np.zeros(1, np.uint8)
+        mes = np.arange(n, dtype=np.uint32) if mes is None else np.ascontiguousarray(mes, np.uint32)
+        pp = np.ascontiguousarray(table.pfx_ptr, np.uint32)
+
+        def col(a, dt):
+            a = np.ascontiguousarray(a, dt)
+            return a if len(a) else np.zeros(1, dt)
+
+        tot, nbytes, ms = C.c_uint64(), C.c_uint64(), C.c_double()
+        st = N.lib.spf_mplan_prefix_routes(
+            C.c_void_p(mp), N.ptr(mes), len(mes), N.ptr(pp), N.ptr(col(table.node, np.uint32)),
+            N.ptr(col(table.path_preference, np.int32), C.c_int32),
+            N.ptr(col(table.source_preference, np.int32), C.c_int32),
+            N.ptr(col(table.distance, np.int32), C.c_int32),
+            N.ptr(col(table.min_nexthop, np.int64), C.c_int64), len(pp) - 1, N.ptr(ovl, C.c_uint8),
+            (N.SPF_ROUTE_LFA if lfa else 0) | (N.SPF_PREFIX_ALL_BEST if allBest else 0),
+            C.byref(tot), C.byref(nbytes), C.byref(ms))
+        N.raise_for(st, N.global_error())
+        self._px = len(pp) - 1
+        return int(tot.value), int(nbytes.value), ms.value
+
+    def allSourcesPrefixRouteDb(self, t: int):
+        """Node t's (index into the last allSourcesPrefixRoutes' node list)
+        prefix routes: (info u64 [P] = best node | |B| << 32 | status << 56 --
+        status one of N.SPF_PREFIX_NONE / SELF / NO_NEXTHOP / MIN_NEXTHOP /
+        ROUTE, best SPF_UNREACHABLE for NONE --, ptr u64 [P + 1], records u64 =
+        CSR edge | metric << 32): prefix p's next hops are rec[ptr[p] :
+        ptr[p + 1]], none unless its status is ROUTE."""
+        import numpy as np
+
+        mp = N.lib.ls_all_sources_plan(self._h)
+        if not mp or getattr(self, "_px", None) is None:
+            raise RuntimeError("allSourcesPrefixRouteDb: no prefix routes (call allSourcesPrefixRoutes)")
+        P = self._px
+        n = C.c_uint64()
+        info = np.zeros(max(1, P), np.uint64)
+        ptr = np.zeros(P + 1, np.uint64)
+        N.raise_for(N.lib.spf_mplan_prefix_route_db(C.c_void_p(mp), int(t), N.ptr(info, C.c_uint64),
+                                                    N.ptr(ptr, C.c_uint64), None, 0, C.byref(n)),
+                    N.global_error())
+        rec = np.zeros(max(1, n.value), np.uint64)
+        N.raise_for(N.lib.spf_mplan_prefix_route_db(C.c_void_p(mp), int(t), None, None,
+                                                    N.ptr(rec, C.c_uint64), n.value, C.byref(n)),
+                    N.global_error())
+        return info[:P], ptr, rec[: n.value]
 
     def allSourcesRouteSnapshot(self) -> "RouteSnapshot":
         """The resident pass's route databases (the last

@@ -259,6 +259,43 @@ class PrefixState:
         return self._p
 
 
+def prefixTable(prefixState: "PrefixState", area: str, names: Sequence[str]):
+    """The arrays of LinkState.allSourcesPrefixRoutes from a PrefixState:
+    (table, left).  table (link_state.PrefixTable; table.prefixes names its
+    rows) covers the prefixes whose route decision is the SP_ECMP / IP one of
+    area `area`; `left` lists the prefixes the host solver keeps: any entry of
+    type BGP or with a metric vector, SR_MPLS forwarding, KSP2_ED_ECMP, a
+    prepend label, or an entry in another area.  names: the link state's nodes
+    in id order (flatten()[0]); an advertiser that is none of them is reached
+    by nobody and is left out of its prefix."""
+    from .link_state import PrefixTable
+
+    id_of = {s: i for i, s in enumerate(names)}
+    ptr, node, pp, sp, dist, mn = [0], [], [], [], [], []
+    covered: List[str] = []
+    left: List[str] = []
+    for prefix, entries in prefixState.prefixes().items():
+        if any(na[1] != area or e.type == "BGP" or e.mv is not None or e.forwardingType != "IP" or
+               e.forwardingAlgorithm != "SP_ECMP" or e.prependLabel is not None
+               for na, e in entries.items()):
+            left.append(prefix)
+            continue
+        for na, e in entries.items():
+            if na[0] not in id_of:
+                continue
+            node.append(id_of[na[0]])
+            pp.append(e.metrics.path_preference)
+            sp.append(e.metrics.source_preference)
+            dist.append(e.metrics.distance)
+            mn.append(0 if e.minNexthop is None else e.minNexthop)
+        ptr.append(len(node))
+        covered.append(prefix)
+    table = PrefixTable(np.asarray(ptr, np.uint32), np.asarray(node, np.uint32), np.asarray(pp, np.int32),
+                        np.asarray(sp, np.int32), np.asarray(dist, np.int32), np.asarray(mn, np.int64),
+                        covered)
+    return table, left
+
+
 @dataclass
 class RibUnicastEntry:
     prefix: str
